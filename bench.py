@@ -4,13 +4,19 @@ resnet50 bf16 forward, batch 256 per MI355X; `--model vit_base` = configs[2]).
 
 Contract (driver): `python bench.py --gpus N --steps K --warmup W`; for N>1 it is launched through
 `torch.distributed.run` (one rank per GPU, RCCL) -- or spawns those ranks itself when WORLD_SIZE is unset.
-At 1 GPU the same invocation also times vit_base (B=256, the other half of the headline metric), swin_t (B=128) and
-alexnet (B=256, configs[0]'s model) and reports them under "extra".  A step = one forward of the per-GPU batch through the
-HIP path (hipGraph replay of the recorded launch list) + the all-gather of the fp32 logits; images are
-already resident in HBM.  W untimed warm-up steps, then exactly K timed steps bracketed by
-barrier + synchronize; MAX over ranks; rank 0 prints ONE JSON line.
+A step = one forward of the per-GPU batch through the HIP path (hipGraph replay of the recorded launch list) + the
+all-gather of the fp32 logits; images are already resident in HBM.  W untimed warm-up steps, then exactly K timed steps
+bracketed by barrier + synchronize; MAX over ranks; rank 0 prints ONE JSON line.  A plain run does only that: set-up,
+warm-up, the K timed steps and the line (`value`, `ms_per_step`, `config`).
 
-Extra objects in the line:
+`--dump-outputs DIR` writes the fp32 logits of the last timed step (all ranks' rows, what a caller of the timed forward
+receives) to DIR/logits.npy.  Images, weights and keys are seeded, so the same arguments give the same inputs in every run.
+
+`--full` adds everything else the benchmark measures: at 1 GPU it also times vit_base (B=256, the other half of the headline
+metric), swin_t (B=128) and alexnet (B=256, configs[0]'s model) and reports them under "extra" (`--extra` picks other
+models); the objects below; and `--layers`.
+
+Extra objects in the line (--full):
   roofline     the dominant kernel = the GEMM-type kernel (one name per kernel symbol) with the largest summed duration in the
                model traced as ONE launch list (the only setting in which per-kernel durations add up to a step and in which HIP
                events and rocprofv3 agree to 1-3 %).  `achieved` = its algorithmic FLOPs per launch (2 x MACs, `flop_per_launch`) /
@@ -423,8 +429,9 @@ def cpu_baseline(model_name, net, threads):
                       f"best of {reps} after 1 warm-up ({time.time() - t_all:.1f}s of CPU work)"}
 
 
-def run_model(a, name, B, rank, world, soak_s):
-    """Build `name`, trace + capture its forward, (soak), W warm-up steps, K timed steps -> result dict (rank 0) + net."""
+def run_model(a, name, B, rank, world, soak_s, dump_dir=None):
+    """Build `name`, trace + capture its forward, (soak), W warm-up steps, K timed steps -> result dict (rank 0) + net.
+    `dump_dir`: write the last timed step's logits there (--dump-outputs)."""
     import eqxvision_amd as eqv
     from eqxvision_amd import _lib, dist as D
     from eqxvision_amd._act import stream_ptr
@@ -472,7 +479,7 @@ def run_model(a, name, B, rank, world, soak_s):
     t0 = time.perf_counter()
     _lib.call("mv_event_record", e0, stream_ptr())
     for _ in range(a.steps):
-        step()
+        out = step()
     _lib.call("mv_event_record", e1, stream_ptr())
     torch.cuda.synchronize()
     D.barrier()
@@ -485,6 +492,19 @@ def run_model(a, name, B, rank, world, soak_s):
     compiled = fwd._entries()[0]
     if rank != 0:
         return None, net
+    if dump_dir:                             # the last timed step's logits (all ranks' rows), before anything replays the graph again
+        os.makedirs(dump_dir, exist_ok=True)
+        np.save(os.path.join(dump_dir, "logits.npy"), out.float().cpu().numpy())
+    step_ms = 1e3 * dt / a.steps
+    res = {"value": round(B * world * a.steps / dt, 1), "ms_per_step": round(step_ms, 4),
+           "config": {"workload": f"{name} {a.dtype} forward, batch={B}/GPU, 3x224x224, 1000 classes",
+                      "global_batch": B * world, "parallelism": f"dp{world}", "launches_per_step": len(compiled.calls),
+                      "graph": compiled.graph is not None,
+                      "lanes": len(compiled.lane_calls) if compiled.lane_calls else 1,
+                      "collective": ("mv_allgather (RCCL)" if D._state["native"] else "torch.distributed") if use_comm else None,
+                      "collective_forced_1rank": bool(use_comm and world == 1)}}
+    if not a.full:
+        return res, net
     # ---- the same forward with the lanes NOT joined per call (filter_jit(join="stream"), an opt-in): reported beside the line, never
     # as `value` -- the returned logits are futures until `ready()`, a different contract from the default's
     pipelined = None
@@ -511,7 +531,6 @@ def run_model(a, name, B, rank, world, soak_s):
             del fp
         except Exception as e:  # noqa: BLE001
             pipelined = {"error": f"{type(e).__name__}: {e}"}
-    step_ms = 1e3 * dt / a.steps
     flop_per_launch = GFLOP_PER_IMG[name] * 1e9 * B
     achieved = flop_per_launch / (dev_ms_per_step * 1e-3) / 1e12
     # ---- roofline of the dominant kernel, measured live with HIP events on the launch streams (docstring) -----------------------
@@ -628,14 +647,7 @@ def run_model(a, name, B, rank, world, soak_s):
         ik, iv = dominant_family(iso)
         roof["isolated"] = {"kernel": ik, "avg_launch_us": round(iv["us"] / max(1, iv["n"]), 2),
                             "frac": round(iv["gflop"] / iv["us"] * 1e3 / MFMA_PEAK_TFLOPS, 4) if iv["us"] else 0.0}
-    res = {"value": round(B * world * a.steps / dt, 1), "ms_per_step": round(step_ms, 4),
-           "config": {"workload": f"{name} {a.dtype} forward, batch={B}/GPU, 3x224x224, 1000 classes",
-                      "global_batch": B * world, "parallelism": f"dp{world}", "launches_per_step": len(compiled.calls),
-                      "graph": compiled.graph is not None,
-                      "lanes": len(compiled.lane_calls) if compiled.lane_calls else 1,
-                      "collective": ("mv_allgather (RCCL)" if D._state["native"] else "torch.distributed") if use_comm else None,
-                      "collective_forced_1rank": bool(use_comm and world == 1)},
-           "roofline": roof}
+    res["roofline"] = roof
     if pipelined is not None:
         res["lanes_not_joined"] = pipelined
     return res, net
@@ -677,7 +689,16 @@ def main():
     ap.add_argument("--lanes", type=int, default=2,
                     help="sub-batches captured as parallel hipGraph branches (fills the last, partial round of CUs of "
                          "one kernel with the other lane's next kernel); 1 = a single launch list")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every measurement beyond the headline line: the CPU baseline, the --extra models, the roofline "
+                         "passes, the lanes-not-joined figure and --layers")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write the logits of the last timed step to DIR/logits.npy (float32)")
     a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
+    if not a.full and (a.layers or a.extra not in (None, "none")):
+        ap.error("--layers and --extra are part of the --full measurements")
     if a.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(respawn(a))
 
@@ -699,20 +720,20 @@ def main():
     eqv.set_compute_dtype(a.dtype)
     default_batch = {"swin_t": 128}
     extras = []
-    if world == 1 and a.extra != "none":
+    if world == 1 and a.full and a.extra != "none":
         extras = [m for m in (a.extra.split(",") if a.extra else (["vit_base", "swin_t", "alexnet"] if a.model == "resnet50" else [])) if m]
     soak = a.soak if a.soak is not None else (5.0 if world == 1 else 2.0)
 
     # CPU baseline FIRST (rank 0, 1 GPU only), so that the GPU phase is the tail of the run
     cpu = {}
-    if world == 1 and not a.no_cpu:
+    if world == 1 and a.full and not a.no_cpu:
         for m in [a.model] + [e for e in extras if e in ("vit_base", "swin_t", "alexnet")]:
             try:
                 cpu[m] = cpu_baseline(m, build_model(m), torch.get_num_threads())
             except Exception as e:  # noqa: BLE001
                 cpu[m] = {"error": f"{type(e).__name__}: {e}"}
 
-    res, _ = run_model(a, a.model, a.batch or default_batch.get(a.model, 256), rank, world, soak)
+    res, _ = run_model(a, a.model, a.batch or default_batch.get(a.model, 256), rank, world, soak, dump_dir=a.dump_outputs)
     extra_out = {}
     for m in extras:
         try:
@@ -725,7 +746,9 @@ def main():
     if rank == 0:
         line = {"metric": "images/sec", "value": res["value"], "unit": "images/s", "n_gpus": world, "steps": a.steps,
                 "warmup": a.warmup, "ms_per_step": res["ms_per_step"], "higher_is_better": True, "scaling": "weak",
-                "vs_baseline": None, "dtype": a.dtype, "data": "synthetic", "config": res["config"], "roofline": res["roofline"]}
+                "vs_baseline": None, "dtype": a.dtype, "data": "synthetic", "config": res["config"]}
+        if "roofline" in res:
+            line["roofline"] = res["roofline"]
         if "lanes_not_joined" in res:        # opt-in filter_jit(join="stream"): beside the line, never its `value`
             line["lanes_not_joined"] = res["lanes_not_joined"]
         if a.model in cpu:

@@ -8,6 +8,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 import torch
 
@@ -94,15 +95,18 @@ def test_bench_spawns_its_ranks():
     assert line["value"] > 0
 
 
-def test_bench_one_rank_logits_through_mv_allgather():
+def test_bench_one_rank_logits_through_mv_allgather(tmp_path):
     """Round-4 review, item 7: `bench.py --gpus 1` with EQV_FORCE_COMM=1 pushes the logits through mv_allgather on a 1-rank RCCL
     communicator INSIDE the timed region (bench.py asserts the gathered buffer equals the local logits bit for bit) -- the code
-    path of BASELINE configs[3]'s 8-GPU line, executed at N = 1."""
+    path of BASELINE configs[3]'s 8-GPU line, executed at N = 1.  `--dump-outputs` writes the gathered logits of the last step."""
     env = dict(os.environ)
     env.update(EQV_FORCE_COMM="1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "5", "--warmup", "2", "--batch", "64",
-                        "--soak", "0", "--no-cpu", "--extra", "none", "--no-lanes1"], env=env, capture_output=True, text=True, timeout=900)
+                        "--soak", "0", "--no-cpu", "--extra", "none", "--no-lanes1", "--dump-outputs", str(tmp_path)],
+                       env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     line = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
     assert line["n_gpus"] == 1 and line["config"]["collective"] == "mv_allgather (RCCL)" and line["config"]["collective_forced_1rank"], line
     assert line["value"] > 0
+    logits = np.load(tmp_path / "logits.npy")
+    assert logits.shape == (64, 1000) and logits.dtype == np.float32 and np.isfinite(logits).all() and logits.std() > 0

@@ -7,7 +7,7 @@ cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 O=gpurun_out/$TAG; mkdir -p $O
 for spec in resnet50:256 vit_base:256 swin_t:128 alexnet:256; do
   M=${spec%%:*}; B=${spec##*:}
-  CMD="python bench.py --model $M --batch $B --steps 20 --warmup 5 --no-cpu --extra none --soak 1 --no-lanes1"
+  CMD="python bench.py --full --model $M --batch $B --steps 20 --warmup 5 --no-cpu --extra none --soak 1 --no-lanes1"
   timeout 400 $CMD --layers $O/${M}_per_launch.txt > $O/${M}_bench_layers.json 2> $O/${M}_bench.err
   # THE profiled command (its own JSON line is what roofline.frac is checked against): no --layers, no lanes1 pass -> the trace
   # holds only the two-lane launches (graph replays + the in-situ event pass)
@@ -16,14 +16,14 @@ for spec in resnet50:256 vit_base:256 swin_t:128 alexnet:256; do
   t=$(find $O/${M}_trace -name "*kernel_trace.csv" | head -1); [ -n "$t" ] && python tools/rocprof_trim.py $t $O/${M}_rocprofv3_warm_stats.txt
   s=$(find $O/${M}_trace -name "*kernel_stats.csv" | head -1); [ -n "$s" ] && cp $s $O/${M}_rocprofv3_kernel_stats.csv
   # the same model as ONE launch list (--lanes 1): per-kernel durations whose sum compares with a step
-  CMD1="python bench.py --model $M --batch $B --steps 20 --warmup 5 --no-cpu --extra none --soak 1 --lanes 1"
+  CMD1="python bench.py --full --model $M --batch $B --steps 20 --warmup 5 --no-cpu --extra none --soak 1 --lanes 1"
   timeout 400 rocprofv3 --kernel-trace --stats --output-format csv -d $O/${M}_trace1 -o t -- $CMD1 > $O/${M}_trace1.log 2>&1
   grep '^{' $O/${M}_trace1.log | tail -1 > $O/${M}_lanes1_bench.json
   t=$(find $O/${M}_trace1 -name "*kernel_trace.csv" | head -1); [ -n "$t" ] && python tools/rocprof_trim.py $t $O/${M}_lanes1_rocprofv3_warm_stats.txt
   for C in FETCH_SIZE WRITE_SIZE; do
-    timeout 400 rocprofv3 --pmc $C --kernel-trace --output-format csv -d $O/${M}_$C -o t -- python bench.py --model $M --batch $B --steps 3 --warmup 2 --no-cpu --extra none --soak 0 --no-lanes1 > $O/${M}_$C.log 2>&1
+    timeout 400 rocprofv3 --pmc $C --kernel-trace --output-format csv -d $O/${M}_$C -o t -- python bench.py --full --model $M --batch $B --steps 3 --warmup 2 --no-cpu --extra none --soak 0 --no-lanes1 > $O/${M}_$C.log 2>&1
   done
-  timeout 400 rocprofv3 --pmc SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_VALU_MFMA_BUSY_CYCLES SQ_INSTS_MFMA SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY GRBM_GUI_ACTIVE --kernel-trace --output-format csv -d $O/${M}_SQ -o t -- python bench.py --model $M --batch $B --steps 2 --warmup 2 --no-cpu --extra none --soak 0 --no-graph --no-lanes1 > $O/${M}_SQ.log 2>&1
+  timeout 400 rocprofv3 --pmc SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_VALU_MFMA_BUSY_CYCLES SQ_INSTS_MFMA SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY GRBM_GUI_ACTIVE --kernel-trace --output-format csv -d $O/${M}_SQ -o t -- python bench.py --full --model $M --batch $B --steps 2 --warmup 2 --no-cpu --extra none --soak 0 --no-graph --no-lanes1 > $O/${M}_SQ.log 2>&1
 done
 for spec in resnet50 vit_base swin_t alexnet; do
   t=$(find $O/${spec}_trace -name "*kernel_trace.csv" | head -1)
