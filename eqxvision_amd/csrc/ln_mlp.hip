@@ -15,12 +15,17 @@
 //   * no block barrier after the weight fill: waves free-run over a strided tile list, loads / MFMA / GELU (the VALU-bound part:
 //     77 M activations per launch) of different waves overlap;
 //   * traffic: x once (+ an L2-hot re-read for the residual add), y once: 154 MB instead of 616 MB.
+// RES variant (ConvNeXt blocks, convnext.py:62-72 `x + layer_scale * block(x)`): the residual is NOT the LayerNorm input -- x is the
+// depthwise convolution's output d and `res` the fp32 stream; the fc2 accumulators start from `res` instead of x and y is fp32.
+#include <type_traits>
+
 #include "mfma_common.h"
 
 namespace mv {
 
 struct LnMlpP {
     const void* x;
+    const float* res;     // RES variant: [M][96] fp32 residual rows (else unused)
     const bf16_t* w1;     // [384][96], LayerNorm gamma folded in
     const float* b1;      // [384], b1 + W1 . beta
     const bf16_t* w2;     // [96][384]
@@ -56,9 +61,10 @@ template <> struct LmRow<bf16_t> {
     }
 };
 
-template <typename XT, int WAVES>
+template <typename XT, int WAVES, bool RES = false>
 __global__ __launch_bounds__(WAVES * 64) void ln_mlp96_kernel(const LnMlpP p) {
     using namespace lm;
+    using YT = typename std::conditional<RES, float, XT>::type;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     char* w1l = smem;
     char* w2l = smem + W1B;
@@ -105,7 +111,7 @@ __global__ __launch_bounds__(WAVES * 64) void ln_mlp96_kernel(const LnMlpP p) {
 
     const int fr = lane & 31, fh = lane >> 5;
     const XT* x = (const XT*)p.x;
-    XT* y = (XT*)p.y;
+    YT* y = (YT*)p.y;
     const char* w1f = w1l + fr * W1P + fh * 16;        // + chunk*32*W1P + t*32
     const char* w2f = w2l + fr * W2P + fh * 16;        // + r*32*W2P + (chunk*2 + s)*32
     const float* b1f = b1l + 4 * fh;                   // + 32*chunk + 8*g
@@ -156,12 +162,22 @@ __global__ __launch_bounds__(WAVES * 64) void ln_mlp96_kernel(const LnMlpP p) {
         // holds 16 t + 8 fh + 0..7; one v_permlane32_swap per register pair -- lanes 32..63 of the low half-group trade places with
         // lanes 0..31 of the high one -- leaves group g' = 2 t in the first register and g' = 2 t + 1 in the second, on both
         // halves.  (The residual used to be RE-READ in the epilogue: 77 MB more HBM traffic per launch, PMC 154 vs 77 MB read.)
+        // RES: the same exchange on the lane's share of the residual row (same channels as raw, read from `res`).
         f32x16 acc2[RB];
+        float rres[RES ? KC : 1][8];
+        if constexpr (RES) {
+            int m = tile * 32 + fr;
+            m = m < p.M ? m : p.M - 1;
+            const float* src = p.res + (long long)m * C + fh * 8;
+#pragma unroll
+            for (int t = 0; t < KC; ++t) LmRow<float>::ld8(src + t * 16, rres[t]);
+        }
 #pragma unroll
         for (int t = 0; t < KC; ++t)
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
-                const auto sw = __builtin_amdgcn_permlane32_swap(__float_as_uint(raw[t][e]), __float_as_uint(raw[t][e + 4]), false, false);
+                const float lo = RES ? rres[RES ? t : 0][e] : raw[t][e], hi = RES ? rres[RES ? t : 0][e + 4] : raw[t][e + 4];
+                const auto sw = __builtin_amdgcn_permlane32_swap(__float_as_uint(lo), __float_as_uint(hi), false, false);
                 const int ga = 2 * t, gb = 2 * t + 1;
                 acc2[ga >> 2][4 * (ga & 3) + e] = __uint_as_float(sw[0]);
                 acc2[gb >> 2][4 * (gb & 3) + e] = __uint_as_float(sw[1]);
@@ -238,7 +254,7 @@ __global__ __launch_bounds__(WAVES * 64) void ln_mlp96_kernel(const LnMlpP p) {
         // ---- epilogue: acc2[r][4g+i] = y^T[32r + 8g + 4fh + i][my row] (the residual is already inside); 4 consecutive channels per store
         const int m = tile * 32 + fr;
         if (m < p.M) {
-            XT* yr = y + (long long)m * C + 4 * fh;
+            YT* yr = y + (long long)m * C + 4 * fh;
 #pragma unroll
             for (int r = 0; r < RB; ++r)
 #pragma unroll
@@ -249,7 +265,7 @@ __global__ __launch_bounds__(WAVES * 64) void ln_mlp96_kernel(const LnMlpP p) {
 #ifdef MV_I8_PROF
                     if ((p.dbg & 16) && o.x != 12345.678f) continue;
 #endif
-                    Out4<XT>::st(yr + 32 * r + 8 * g, o);
+                    Out4<YT>::st(yr + 32 * r + 8 * g, o);
                 }
         }
     }
@@ -260,11 +276,11 @@ int ln_mlp_supported(long long M, int C, int hidden, int x_dtype) {
            !get_flag("no_ln_mlp");
 }
 
-template <typename XT, int WAVES>
+template <typename XT, int WAVES, bool RES = false>
 static int ln_mlp_go(const LnMlpP& p, hipStream_t st) {
     int grid = (p.tiles + WAVES - 1) / WAVES;
     if (grid > 256) grid = 256;                              // one block per CU: the weights fill its LDS
-    auto kern = ln_mlp96_kernel<XT, WAVES>;
+    auto kern = ln_mlp96_kernel<XT, WAVES, RES>;
     MV_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, lm::SMEM));
     hipLaunchKernelGGL(kern, dim3(grid), dim3(WAVES * 64), lm::SMEM, st, p);
     MV_LAUNCH_CHECK();
@@ -274,7 +290,7 @@ static int ln_mlp_go(const LnMlpP& p, hipStream_t st) {
 int ln_mlp_launch(const void* x, const void* w1, const float* b1, const void* w2, const float* b2, void* y, long long M,
                   float eps, int x_dtype, hipStream_t st) {
     LnMlpP p;
-    p.x = x; p.w1 = (const bf16_t*)w1; p.b1 = b1; p.w2 = (const bf16_t*)w2; p.b2 = b2; p.y = y;
+    p.x = x; p.res = nullptr; p.w1 = (const bf16_t*)w1; p.b1 = b1; p.w2 = (const bf16_t*)w2; p.b2 = b2; p.y = y;
     p.M = (int)M; p.tiles = (int)((M + 31) / 32); p.eps = eps;
     p.dbg = 0;
 #ifdef MV_I8_PROF
@@ -285,6 +301,19 @@ int ln_mlp_launch(const void* x, const void* w1, const float* b1, const void* w2
     if (x_dtype == MV_F32)
         return wv == 16 ? ln_mlp_go<float, 16>(p, st) : wv == 8 ? ln_mlp_go<float, 8>(p, st) : ln_mlp_go<float, 12>(p, st);
     return wv == 16 ? ln_mlp_go<bf16_t, 16>(p, st) : wv == 8 ? ln_mlp_go<bf16_t, 8>(p, st) : ln_mlp_go<bf16_t, 12>(p, st);
+}
+
+int ln_mlp_res_launch(const void* x, const float* res, const void* w1, const float* b1, const void* w2, const float* b2, float* y,
+                      long long M, float eps, int x_dtype, hipStream_t st) {
+    LnMlpP p;
+    p.x = x; p.res = res; p.w1 = (const bf16_t*)w1; p.b1 = b1; p.w2 = (const bf16_t*)w2; p.b2 = b2; p.y = y;
+    p.M = (int)M; p.tiles = (int)((M + 31) / 32); p.eps = eps;
+    p.dbg = 0;
+    set_kernel_name(x_dtype == MV_F32 ? "ln_mlp96_res_f32in" : "ln_mlp96_res_bf16in");
+    const int wv = get_flag("ln_mlp_waves");
+    if (x_dtype == MV_F32)
+        return wv == 16 ? ln_mlp_go<float, 16, true>(p, st) : wv == 8 ? ln_mlp_go<float, 8, true>(p, st) : ln_mlp_go<float, 12, true>(p, st);
+    return wv == 16 ? ln_mlp_go<bf16_t, 16, true>(p, st) : wv == 8 ? ln_mlp_go<bf16_t, 8, true>(p, st) : ln_mlp_go<bf16_t, 12, true>(p, st);
 }
 
 }  // namespace mv

@@ -32,6 +32,7 @@ struct LnMlpSP {
     const float* b1;      // [HID] (LayerNorm shift folded in)
     const bf16_t* w2f;    // [HID/256][C/32][16][64][8]
     const float* b2;      // [C]
+    const float* res;     // [M][C] rows added in the epilogue: x itself, or (the _res entry) a separate fp32 stream
     float* y;             // [M][C]
     long long M;
     float eps;
@@ -292,7 +293,7 @@ __global__ __launch_bounds__(512) void ln_mlp_stream_kernel(const LnMlpSP p) {
         static_assert(TM * QPR % 512 == 0, "whole passes");
         // rows past M: out-of-range buffer offsets (loads return zeros, stores are dropped) -- no branch, no load inside the store
         // loop, so the NIT stores stream behind each other instead of one L2 round trip each (tools/scan_store_waits.py)
-        const brsrc_t rx = make_brsrc(p.x + (long long)row0 * C), ry = make_brsrc(p.y + (long long)row0 * C), rb = make_brsrc(p.b2);
+        const brsrc_t rx = make_brsrc(p.res + (long long)row0 * C), ry = make_brsrc(p.y + (long long)row0 * C), rb = make_brsrc(p.b2);
         const int rows_left = p.M - (int)row0;
         float4 xr[NIT], b2[NIT];
 #pragma unroll
@@ -503,7 +504,7 @@ __global__ __launch_bounds__(512) void ln_mlp_stream192_kernel(const LnMlpSP p) 
     {
         constexpr int QPR = C / 4, NIT = TM * QPR / 512;
         static_assert(TM * QPR % 512 == 0, "whole passes");
-        const brsrc_t rx = make_brsrc(p.x + (long long)row0 * C), ry = make_brsrc(p.y + (long long)row0 * C), rb = make_brsrc(p.b2);
+        const brsrc_t rx = make_brsrc(p.res + (long long)row0 * C), ry = make_brsrc(p.y + (long long)row0 * C), rb = make_brsrc(p.b2);
         const int rows_left = p.M - (int)row0;
         float4 xr[NIT], b2[NIT];
 #pragma unroll
@@ -536,18 +537,44 @@ int mv_ln_mlp_stream_supported(int64_t M, int C, int hidden, int x_dtype) {
     return x_dtype == MV_F32 && (C == 384 || C == 192) && hidden == 4 * C && M >= 128;
 }
 
+static int ln_mlp_stream_go(const void* x, const void* res, const void* w1f, const float* b1, const void* w2f, const float* b2,
+                            void* y, int64_t M, int C, float eps, hipStream_t stream);
+
 int mv_ln_mlp_stream_fwd(const void* x, const void* w1f, const float* b1, const void* w2f, const float* b2, void* y, int64_t M,
                          int C, int hidden, float eps, int x_dtype, mv_stream_t stream_) {
     using namespace mv;
-    hipStream_t stream = (hipStream_t)stream_;
     MV_CHECK_ARG(x && w1f && b1 && w2f && b2 && y, "mv_ln_mlp_stream_fwd: null argument");
     MV_CHECK_ARG(x != y, "mv_ln_mlp_stream_fwd: not in place");
     if (!mv_ln_mlp_stream_supported(M, C, hidden, x_dtype)) {
         set_error("mv_ln_mlp_stream_fwd: unsupported M=%lld C=%d hidden=%d (ask mv_ln_mlp_stream_supported first)", (long long)M, C, hidden);
         return MV_E_UNSUPPORTED;
     }
+    return ln_mlp_stream_go(x, x, w1f, b1, w2f, b2, y, M, C, eps, (hipStream_t)stream_);
+}
+
+int mv_ln_mlp_stream_res_supported(int64_t M, int C, int hidden, int x_dtype) {
+    return mv_ln_mlp_stream_supported(M, C, hidden, x_dtype);
+}
+
+int mv_ln_mlp_stream_res_fwd(const void* x, const void* res, const void* w1f, const float* b1, const void* w2f, const float* b2, void* y,
+                             int64_t M, int C, int hidden, float eps, int x_dtype, mv_stream_t stream_) {
+    using namespace mv;
+    MV_CHECK_ARG(x && res && w1f && b1 && w2f && b2 && y, "mv_ln_mlp_stream_res_fwd: null argument");
+    MV_CHECK_ARG(x != y, "mv_ln_mlp_stream_res_fwd: x and y must not alias");
+    if (!mv_ln_mlp_stream_res_supported(M, C, hidden, x_dtype)) {
+        set_error("mv_ln_mlp_stream_res_fwd: unsupported M=%lld C=%d hidden=%d (ask mv_ln_mlp_stream_res_supported first)", (long long)M, C,
+                  hidden);
+        return MV_E_UNSUPPORTED;
+    }
+    return ln_mlp_stream_go(x, res, w1f, b1, w2f, b2, y, M, C, eps, (hipStream_t)stream_);
+}
+
+static int ln_mlp_stream_go(const void* x, const void* res, const void* w1f, const float* b1, const void* w2f, const float* b2,
+                            void* y, int64_t M, int C, float eps, hipStream_t stream) {
+    using namespace mv;
+    const bool own = res == x;                    // the kernel names tell the two entries apart in a trace
     LnMlpSP p;
-    p.x = (const float*)x; p.w1f = (const bf16_t*)w1f; p.b1 = b1; p.w2f = (const bf16_t*)w2f; p.b2 = b2; p.y = (float*)y;
+    p.x = (const float*)x; p.res = (const float*)res; p.w1f = (const bf16_t*)w1f; p.b1 = b1; p.w2f = (const bf16_t*)w2f; p.b2 = b2; p.y = (float*)y;
     p.M = M; p.eps = eps;
     p.prof = nullptr;
 #ifdef MV_I8_PROF              // debug build only
@@ -559,7 +586,7 @@ int mv_ln_mlp_stream_fwd(const void* x, const void* w1f, const float* b1, const 
         constexpr int SMEM = TM * (192 * 2 + 16) + TM * (256 * 2 + 16);
         auto kern = ln_mlp_stream192_kernel<TM>;
         MV_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, SMEM));
-        set_kernel_name("ln_mlp_stream_c192_f32stream");
+        set_kernel_name(own ? "ln_mlp_stream_c192_f32stream" : "ln_mlp_stream_c192_res");
         hipLaunchKernelGGL(kern, dim3((unsigned)((M + TM - 1) / TM)), dim3(512), SMEM, stream, p);
         MV_LAUNCH_CHECK();
         return MV_OK;
@@ -568,7 +595,7 @@ int mv_ln_mlp_stream_fwd(const void* x, const void* w1f, const float* b1, const 
     constexpr int SMEM = TM * (384 * 2 + 16) + 2 * TM * (256 * 2 + 16);
     auto kern = ln_mlp_stream_kernel<384, TM, 8, 8>;         // prefetch depths: (4, 4), (6, 6), (8, 4) measured equal or slower
     MV_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, SMEM));
-    set_kernel_name("ln_mlp_stream_c384_f32stream");
+    set_kernel_name(own ? "ln_mlp_stream_c384_f32stream" : "ln_mlp_stream_c384_res");
     hipLaunchKernelGGL(kern, dim3((unsigned)((M + TM - 1) / TM)), dim3(512), SMEM, stream, p);
     MV_LAUNCH_CHECK();
     return MV_OK;

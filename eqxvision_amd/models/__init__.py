@@ -1,5 +1,6 @@
 """Flat model namespace (reference eqxvision/models/__init__.py:1-105) for the hot-path families."""
 from .classification.alexnet import AlexNet, alexnet
+from .classification.convnext import ConvNeXt, convnext_base, convnext_large, convnext_small, convnext_tiny
 from .classification.efficientnet import (
     EfficientNet,
     efficientnet_b0,

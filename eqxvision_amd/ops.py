@@ -1698,6 +1698,145 @@ def patch_merge_gather(x: Act) -> Act:
     return Act(y, "map", x.batched)
 
 
+# ------------------------------------------------------------------ ConvNeXt block (models/classification/convnext.py)
+def prep_dw(conv, bn=None):
+    """Depthwise filters (C, 1, R, S) re-laid to [R][S][C] bf16 + folded scale / shift (cached: the "dw" entry conv2d uses)."""
+    cache = conv._cache()
+    hit = cache.get(("dw", _bn_id(bn)))
+    if hit is None:
+        _, scale, shift = prep_conv(conv, bn, "oihw", "bf16")
+        wr = np.ascontiguousarray(np.asarray(conv.weight, np.float32)[:, 0].transpose(1, 2, 0))     # (C,1,R,S) -> [R][S][C]
+        hit = (_dev(wr, torch.bfloat16), scale, shift)
+        cache[("dw", _bn_id(bn))] = hit
+    return hit
+
+
+def _cnblock_layers(blk):
+    """(dwconv, norm, fc1, fc2) when the block is the reference's Sequential[Conv2d 7x7 depthwise, LayerNorm, Linear, gelu, Linear]
+    with every bias / affine present, else None."""
+    from . import nn
+    L = getattr(blk.block, "layers", None)
+    if L is None or len(L) != 5:
+        return None
+    dw, ln, fc1, act, fc2 = L
+    C = getattr(dw, "in_channels", -1)
+    ok = (isinstance(dw, nn.Conv2d) and type(dw) is nn.Conv2d and dw.groups == C == dw.out_channels and tuple(dw.kernel_size) == (7, 7)
+          and tuple(dw.stride) == (1, 1) and tuple(dw.padding) == (3, 3) and tuple(dw.dilation) == (1, 1) and dw.bias is not None
+          and isinstance(ln, nn.LayerNorm) and ln.weight is not None and ln.bias is not None and int(np.prod(ln.shape)) == C
+          and isinstance(fc1, nn.Linear) and isinstance(fc2, nn.Linear) and fc1.bias is not None and fc2.bias is not None
+          and fc1.in_features == C and fc2.out_features == C and fc2.in_features == fc1.out_features
+          and isinstance(act, nn.Lambda) and nn.act_name(act.fn) == "gelu")
+    return (dw, ln, fc1, fc2) if ok else None
+
+
+def _cnblock_mlp(blk, ln, fc1, fc2, form: str):
+    """The block's MLP with the LayerNorm affine folded into fc1 (W1 diag(g), b1 + W1 beta) and layer_scale into fc2 (diag(ls) W2 in
+    fp32, then one bf16 rounding; ls * b2).  form "lds" / "lin": row-major; "stream": mv_ln_mlp_stream_fwd's fragment order."""
+    ls = np.asarray(blk.layer_scale, np.float32).reshape(-1)
+    key = ("cnb_mlp", form) + tuple(id(a) for a in (ln.weight, ln.bias, fc1.weight, fc1.bias, fc2.weight, fc2.bias, blk.layer_scale))
+    cache = blk._cache()
+    hit = cache.get(key)
+    if hit is None:
+        w1 = np.asarray(fc1.weight, np.float32)
+        g, b = np.asarray(ln.weight, np.float32).reshape(-1), np.asarray(ln.bias, np.float32).reshape(-1)
+        w1f = w1 * g[None, :]
+        w2f = np.asarray(fc2.weight, np.float32) * ls[:, None]
+        if form == "stream":
+            w1f, w2f = ln_mlp_fragments(w1f, w2f)
+        hit = (_dev(w1f, torch.bfloat16), _dev(np.asarray(fc1.bias, np.float32).reshape(-1) + w1 @ b, torch.float32),
+               _dev(w2f, torch.bfloat16), _dev(np.asarray(fc2.bias, np.float32).reshape(-1) * ls, torch.float32),
+               (ln.weight, ln.bias, fc1.weight, fc1.bias, fc2.weight, fc2.bias, blk.layer_scale))      # keeps the ids alive
+        cache[key] = hit
+    return hit
+
+
+def _cnblock_dw(x: Act, dw, ln, normalize: int, y_dt: str) -> Act:
+    B, H, W, C = x.t.shape
+    w, _, bias = prep_dw(dw)
+    y = empty((B, H, W, C), TORCH_DT[y_dt])
+    _lib.call("mv_cnblock_dw_fwd", _ptr(x.t), _ptr(w), _ptr(bias), _ptr(y), B, H, W, C, float(ln.eps), normalize, x.dt, DT[y_dt],
+              stream_ptr())
+    return Act(y, "map", x.batched)
+
+
+def convnext_downsample(x: Act, ln, conv) -> Act:
+    """conv2x2/2(LayerNorm2d(x)) between ConvNeXt stages (convnext.py:179-193) back onto the fp32 stream.  Even maps: the 2x2 patches
+    do not overlap, so the convolution is patch gather + a Linear over 4C, run with split-precision weights and an fp32 store like
+    Swin's patch merging (its weight rounding is not damped by a residual add); odd maps: the convolution, then a cast."""
+    x = as_map(x)
+    B, H, W, C = x.t.shape
+    n = layernorm(x, ln)
+    if H % 2 or W % 2 or x.t.dtype != torch.float32 or tuple(conv.kernel_size) != (2, 2) or tuple(conv.stride) != (2, 2) \
+            or tuple(conv.padding) != (0, 0) or conv.groups != 1:
+        return cast(conv2d(n, conv), "fp32") if x.t.dtype == torch.float32 else conv2d(n, conv)
+    cache = conv._cache()
+    lin = cache.get("patch_linear")
+    if lin is None:
+        from . import nn
+        K = conv.out_channels
+        lin = nn.Linear.__new__(nn.Linear)
+        w = np.asarray(conv.weight, np.float32)                  # (K, C, dh, dw) -> [K][dw][dh][C]: the gather's (dh, dw) order
+        for f, v in (("weight", np.ascontiguousarray(w.transpose(0, 3, 2, 1).reshape(K, 4 * C))),
+                     ("bias", None if conv.bias is None else np.asarray(conv.bias, np.float32).reshape(-1)),
+                     ("in_features", 4 * C), ("out_features", K), ("use_bias", conv.bias is not None)):
+            object.__setattr__(lin, f, v)
+        cache["patch_linear"] = lin
+    return linear_split(patch_merge_gather(n), lin, out_fp32=True)
+
+
+def cnblock(x: Act, blk, drop=None) -> Act:
+    """x + layer_scale * block(x) (convnext.py:62-72).  `drop` = (DropPath, keys): the training-mode branch (stochastic depth
+    between the scale and the residual add), always on the composition of the generic entries.
+    Inference, bf16, the fp32 stream:  C = 96 / 192 / 384: mv_cnblock_dw_fwd (normalize 0) + mv_ln_mlp[_stream]_res_fwd (2 launches);
+    other widths: mv_cnblock_dw_fwd (normalize 1) + two mv_linear_fwd (3 launches)."""
+    x = as_map(x)
+    B, H, W, C = x.t.shape
+    parts = _cnblock_layers(blk)
+    lib = _lib.load()
+    if parts is not None and drop is None and compute_dtype() == "bf16" and x.t.dtype in (torch.float32, torch.bfloat16):
+        dw, ln, fc1, fc2 = parts
+        M, Hd = B * H * W, fc1.out_features
+        if x.t.dtype == torch.float32 and lib.mv_ln_mlp_res_supported(M, C, Hd, _lib.BF16) and \
+                lib.mv_cnblock_dw_supported(C, H, W, x.dt, _lib.BF16, 0):
+            d = _cnblock_dw(x, dw, ln, 0, "bf16")
+            w1, b1, w2, b2, _ = _cnblock_mlp(blk, ln, fc1, fc2, "lds")
+            y = empty((B, H, W, C), torch.float32)
+            _lib.call("mv_ln_mlp_res_fwd", _ptr(d.t), _ptr(x.t), _ptr(w1), _ptr(b1), _ptr(w2), _ptr(b2), _ptr(y), M, C, Hd,
+                      float(ln.eps), _lib.BF16, stream_ptr())
+            return Act(y, "map", x.batched)
+        if x.t.dtype == torch.float32 and lib.mv_ln_mlp_stream_res_supported(M, C, Hd, _lib.F32) and \
+                lib.mv_cnblock_dw_supported(C, H, W, x.dt, _lib.F32, 0):
+            # the stream kernel reads fp32 rows: d is written in fp32 (+8 B per element of d against bf16, in exchange for keeping
+            # the 577-line kernel single-typed)
+            d = _cnblock_dw(x, dw, ln, 0, "fp32")
+            w1, b1, w2, b2, _ = _cnblock_mlp(blk, ln, fc1, fc2, "stream")
+            y = empty((B, H, W, C), torch.float32)
+            _lib.call("mv_ln_mlp_stream_res_fwd", _ptr(d.t), _ptr(x.t), _ptr(w1), _ptr(b1), _ptr(w2), _ptr(b2), _ptr(y), M, C, Hd,
+                      float(ln.eps), _lib.F32, stream_ptr())
+            return Act(y, "map", x.batched)
+        if lib.mv_cnblock_dw_supported(C, H, W, x.dt, _lib.BF16, 1):
+            n = _cnblock_dw(x, dw, ln, 1, "bf16")
+            w1, b1, w2, b2, _ = _cnblock_mlp(blk, ln, fc1, fc2, "lin")
+            h = empty((B, H, W, Hd), torch.bfloat16)
+            _splitk_scratch(M, Hd, C)
+            _lib.call("mv_linear_fwd", _ptr(n.t), _ptr(w1), None, _ptr(b1), None, _ptr(h), M, Hd, C, _lib.ACT_GELU_TANH, _lib.BF16,
+                      _lib.BF16, stream_ptr())
+            y = empty((B, H, W, C), x.t.dtype)
+            _splitk_scratch(M, C, Hd)
+            _lib.call("mv_linear_fwd", _ptr(h), _ptr(w2), None, _ptr(b2), _ptr(x.t), _ptr(y), M, C, Hd, _lib.ACT_NONE, _lib.BF16,
+                      x.dt, stream_ptr())
+            return Act(y, "map", x.batched)
+    # the composition of the generic entries (the cross-check of the paths above)
+    dt = compute_dtype()
+    h = blk.block(x if x.t.dtype == TORCH_DT[dt] else cast(x, dt))
+    ls = np.broadcast_to(np.asarray(blk.layer_scale, np.float32).reshape(1, -1), (B, C))
+    h = channel_scale(h, Act(_dev(ls, h.t.dtype), "vec", x.batched))
+    if drop is not None:
+        sd, keys = drop
+        h = sd(h, key=keys)
+    return add(x, h)
+
+
 # ------------------------------------------------------------------ element-wise (unfused call sites)
 def _canon(x: Act) -> Act:
     return as_map(x) if x.kind == "img" else (x if x.kind == "map" else as_rows(x))

@@ -23,6 +23,8 @@ _DINO = "https://dl.fbaipublicfiles.com/dino/"
 # key -> checkpoint file stem; keys are the reference's (including its "sim_b" typo, utils.py:79)
 _STEMS = {
     "alexnet": "alexnet-owt-7be5be79",
+    "convnext_tiny": "convnext_tiny-983f1562", "convnext_small": "convnext_small-0c510722",
+    "convnext_base": "convnext_base-6075fbad", "convnext_large": "convnext_large-ea097f82",
     "resnet18": "resnet18-5c106cde", "resnet34": "resnet34-333f7ec4", "resnet50": "resnet50-19c8e357",
     "resnet101": "resnet101-5d3b4d8f", "resnet152": "resnet152-b121ed2d",
     "resnext50_32x4d": "resnext50_32x4d-7cdf4587", "resnext101_32x8d": "resnext101_32x8d-8ba56ff5",

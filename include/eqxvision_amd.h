@@ -54,8 +54,9 @@ enum { MV_OK = 0, MV_E_INVALID = -1, MV_E_UNSUPPORTED = -2, MV_E_OOM = -3 };
  *                   "no_chain_res" (last boundary on chain1x1's form), "no_chain_sub" (block output written whole, not sub-sampled),
  *                   "no_swin_precise" (host: plain bf16 block Linears for Swin widths off the fused kernels)
  *   whole blocks    "no_bneck_tail",
- *                   "no_ln_mlp", "ln_mlp_waves" (8 / 12 / 16), "no_ln_mlp_stream", "no_swin_block_attn", "swin_c96_shared" (the
- *                   two-windows-per-workgroup kernel at C = 96), "no_patch_merge_ln", "no_patch4_ln", "no_fc_stream"
+ *                   "no_ln_mlp", "ln_mlp_waves" (8 / 12 / 16), "no_ln_mlp_stream" (both also govern the _res entries),
+ *                   "no_swin_block_attn", "swin_c96_shared" (the two-windows-per-workgroup kernel at C = 96), "no_patch_merge_ln",
+ *                   "no_patch4_ln", "no_fc_stream", "no_cnblock_dw" (ConvNeXt blocks on the composition of the generic entries)
  *   entry / misc    "stem_v0", "no_stem_pool", "no_stem_pool11", "no_patch_f32out", "no_ln_slim", "no_grouped64", "no_dwconv",
  *                   "dwconv_generic", "dwconv_no_tile", "dwconv_tile3", "no_oddc", "no_se_fused", "se_fused_always", "eltwise_scalar",
  *                   "affine_scalar", "dropout_x8", "dropout_scalar", "no_f32_mfma" (fp32 contractions back on the VALU kernel), "no_f32_lds" (only the direct fp32 matrix-core kernel), "no_attn_f32_lds" (fp32 attention back on the one-wave-per-query kernels),
@@ -313,6 +314,32 @@ int mv_swin_block_attn_fwd(const void* x, const void* wqkv_f, const float* bqkv,
 int mv_ln_mlp_stream_supported(int64_t M, int C, int hidden, int x_dtype);
 int mv_ln_mlp_stream_fwd(const void* x, const void* w1f, const float* b1, const void* w2f, const float* b2, void* y, int64_t M,
                          int C, int hidden, float eps, int x_dtype, mv_stream_t stream);
+
+/* The same two MLP kernels with the residual taken from ANOTHER tensor (the ConvNeXt block, convnext.py:62-72:
+ * res + layer_scale * (w2 . gelu(w1 . n(x) + b1) + b2), x = the 7x7 depthwise output of mv_cnblock_dw_fwd with normalize = 0):
+ *   y[m,:] = res[m,:] + w2 . gelu_tanh( w1 . n(x[m,:]) + b1 ) + b2
+ * The caller folds the LayerNorm affine into w1 / b1 as for mv_ln_mlp_fwd and layer_scale into fc2 (w2 = diag(ls) . W2 in fp32, then
+ * one bf16 rounding; b2 = ls * b2).  res and y are MV_F32 [M][C] (the residual stream; y may not alias x).  mv_ln_mlp_res_*: C = 96,
+ * x MV_F32 or MV_BF16, weights as mv_ln_mlp_fwd; mv_ln_mlp_stream_res_*: C = 192 / 384, x MV_F32, weights in the fragment order of
+ * mv_ln_mlp_stream_fwd.  Supported exactly where the entries without _res are (the same switches). */
+int mv_ln_mlp_res_supported(int64_t M, int C, int hidden, int x_dtype);
+int mv_ln_mlp_res_fwd(const void* x, const void* res, const void* w1, const float* b1, const void* w2, const float* b2, void* y,
+                      int64_t M, int C, int hidden, float eps, int x_dtype, mv_stream_t stream);
+int mv_ln_mlp_stream_res_supported(int64_t M, int C, int hidden, int x_dtype);
+int mv_ln_mlp_stream_res_fwd(const void* x, const void* res, const void* w1f, const float* b1, const void* w2f, const float* b2, void* y,
+                             int64_t M, int C, int hidden, float eps, int x_dtype, mv_stream_t stream);
+
+/* ConvNeXt block head (convnext.py:34-52: Conv2d(C, C, 7, padding=3, groups=C, bias) -> LayerNorm2d(C)) in one pass:
+ *   d[b,h,w,c] = bias[c] + sum_{r,s<7} x[b, h+r-3, w+s-3, c] * w_rsc[r][s][c]      (zero padding, fp32 accumulation)
+ *   normalize = 0: y = d (y_dtype MV_BF16 or MV_F32: the input of mv_ln_mlp_res_fwd / mv_ln_mlp_stream_res_fwd)
+ *   normalize = 1: y = (d - mean_c d) * rsqrt(var_c d + eps), biased var, two passes over the kept d (y_dtype MV_BF16; the affine
+ *                  is folded into the next Linear by the caller)
+ * x NHWC [N][H][W][C], MV_F32 (the residual stream) or MV_BF16; w_rsc the (C, 1, 7, 7) filters re-laid to [7][7][C] bf16 (as for
+ * mv_dwconv2d_nhwc_fwd); bias fp32 [C] or NULL; not in place.  Any C % 8 == 0 up to 1536, any H, W (maps smaller than the window
+ * included).  Flag "no_cnblock_dw". */
+int mv_cnblock_dw_supported(int C, int H, int W, int x_dtype, int y_dtype, int normalize);
+int mv_cnblock_dw_fwd(const void* x, const void* w_rsc, const float* bias, void* y, int N, int H, int W, int C, float eps,
+                      int normalize, int x_dtype, int y_dtype, mv_stream_t stream);
 
 /* eqx.nn.Linear over FEW rows with a big weight matrix -- the AlexNet / VGG classifiers (alexnet.py:62-70: Linear(9216, 4096),
  * Linear(4096, 4096), Linear(4096, classes), each behind `jax.vmap` = M rows) -- y[M][N] = act(x[M][K] . w^T + bias).  The layer is
