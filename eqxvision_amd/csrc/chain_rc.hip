@@ -52,18 +52,6 @@ struct ChainRcP {
     int dbg;               // ablations, debug build only ("rc_dbg", results wrong): 1 = y stores dropped, 2 = every tile reads the same 32 rows, 4 = t1 stores dropped
 };
 
-// the bf16 pair (relu(a), relu(b)): ONE v_cvt_pk_bf16_f32 + ONE v_pk_max_i16 (bf16 is sign-magnitude: max against 0 as int16 is ReLU).
-// The empty asm keeps the packed word a value of its own: without it hipcc turned conversion + vector max into two single conversions
-// and a v_perm_b32 per pair.  (Not an asm instruction on purpose: the hazard recogniser does not see into inline asm, and these
-// values come straight out of the matrix pipe.)
-typedef short s16x2 __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ uint32_t relu_pack_bf2(float a, float b) {
-    uint32_t w = pack_bf2(a, b);
-    asm volatile("" : "+v"(w));
-    const s16x2 z = {0, 0};
-    return __builtin_bit_cast(uint32_t, __builtin_elementwise_max(__builtin_bit_cast(s16x2, w), z));
-}
-
 template <int NPREV, int WAVES, int RD>
 __global__ __launch_bounds__(WAVES * 64) void chain_rc_kernel(const ChainRcP p) {
     constexpr int K = 256, N2 = 64, FPC = 12 + 4 * NPREV, NFRAG = 8 * FPC, PITCH = 144, NSH = 8 * (1 + NPREV) + 2, NT = WAVES * 64,

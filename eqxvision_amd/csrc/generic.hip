@@ -1347,7 +1347,8 @@ int mv_conv1x1_chain_sub_fwd(const void* x, const void* w3, const float* scale3,
 }
 
 int mv_conv1x1_chain_res_supported(int N, int H, int W, int C, int K, int N2, int sub, int dtype) {
-    return !get_flag("force_generic") && !get_flag("no_stream") && N > 0 && H > 0 && W > 0 && chain_res_supported(N, H, W, C, K, N2, sub, dtype);
+    return !get_flag("force_generic") && !get_flag("no_stream") && N > 0 && H > 0 && W > 0 &&
+           (chain_res_supported(N, H, W, C, K, N2, sub, dtype) || chain_l2_res_supported(N, H, W, C, K, N2, sub, dtype));
 }
 
 int mv_conv1x1_chain_res_fwd(const void* t2, const void* residual, const void* wfrag, const void* shifts, void* y, void* t1, int N, int H,
@@ -1359,7 +1360,25 @@ int mv_conv1x1_chain_res_fwd(const void* t2, const void* residual, const void* w
         return MV_E_UNSUPPORTED;
     }
     MV_CHECK_ARG(y != residual && y != t2 && t1 != y && t1 != residual && t1 != t2, "conv1x1_chain_res: outputs must not alias inputs");
+    if (C == 128)                                          // C = 128 / K = 512 (layer 2): weights streamed through LDS (chain_l2.hip)
+        return chain_l2_res_launch(t2, residual, wfrag, shifts, y, t1, N, H, W, N2, sub, (hipStream_t)stream);
     return chain_res_launch(t2, residual, wfrag, shifts, y, t1, N, H, W, sub, (hipStream_t)stream);
+}
+
+int mv_conv1x1_dual_chain_res_supported(int64_t M, int C1, int C2, int K, int N2, int dtype) {
+    return !get_flag("force_generic") && !get_flag("no_stream") && chain_l2_dual_supported(M, C1, C2, K, N2, dtype);
+}
+
+int mv_conv1x1_dual_chain_res_fwd(const void* t2, const void* x, const void* wfrag, const void* shifts, void* y, void* t1, int64_t M,
+                                  int C1, int C2, int K, int N2, int dtype, mv_stream_t stream) {
+    MV_CHECK_ARG(t2 && x && wfrag && shifts && y && t1, "conv1x1_dual_chain_res: NULL pointer");
+    if (!mv_conv1x1_dual_chain_res_supported(M, C1, C2, K, N2, dtype)) {
+        set_error("conv1x1_dual_chain_res: unsupported shape M=%lld C1=%d C2=%d K=%d N2=%d (ask mv_conv1x1_dual_chain_res_supported first)",
+                  (long long)M, C1, C2, K, N2);
+        return MV_E_UNSUPPORTED;
+    }
+    MV_CHECK_ARG(y != t2 && y != x && t1 != y && t1 != t2 && t1 != x, "conv1x1_dual_chain_res: outputs must not alias inputs");
+    return chain_l2_dual_launch(t2, x, wfrag, shifts, y, t1, M, (hipStream_t)stream);
 }
 
 int mv_conv1x1_chain_rc_supported(int64_t M, int C, int K, int N2, int dtype) {

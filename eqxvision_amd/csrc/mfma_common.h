@@ -21,6 +21,18 @@ __device__ __forceinline__ void wave_lds_fence() {
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
+// the bf16 pair (relu(a), relu(b)): ONE v_cvt_pk_bf16_f32 + ONE v_pk_max_i16 (bf16 is sign-magnitude: max against 0 as int16 is ReLU).
+// The empty asm keeps the packed word a value of its own: without it hipcc turned conversion + vector max into two single conversions
+// and a v_perm_b32 per pair.  (Not an asm instruction on purpose: the hazard recogniser does not see into inline asm, and these
+// values come straight out of the matrix pipe.)
+typedef short s16x2 __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ uint32_t relu_pack_bf2(float a, float b) {
+    uint32_t w = pack_bf2(a, b);
+    asm volatile("" : "+v"(w));
+    const s16x2 z = {0, 0};
+    return __builtin_bit_cast(uint32_t, __builtin_elementwise_max(__builtin_bit_cast(s16x2, w), z));
+}
+
 // Raw buffer descriptors for branch-free bounds handling (round 5): an element outside the tensor gets the offset BUF_OOB, which is
 // >= num_records, so the buffer unit drops the store / returns zeros -- no exec-masked region around the access, which is what lets
 // hipcc count vmcnt exactly instead of falling back to `s_waitcnt vmcnt(0)` between the stores of an epilogue (igemm_pipe.h).

@@ -451,10 +451,10 @@ def conv1x1_chain(x: Act, conv3, bn3, residual: Act, conv1n, bn1n, sub: int = 0)
     if C != conv3.in_channels or tuple(residual.t.shape) != (B, H, W, K) or x.t.dtype != torch.bfloat16 \
             or residual.t.dtype != torch.bfloat16:
         return None
-    if not _lib.load().mv_conv1x1_chain_supported(M, C, K, N2, DT[dt]):
-        return None
     lib = _lib.load()
-    for sb in ((2, 0) if sub == 2 else (0,)):      # the accumulator-layout kernel (csrc/chain_rc.hip: chain_res) where it has the shape
+    # the accumulator-layout kernels (csrc/chain_rc.hip: chain_res; csrc/chain_l2.hip for C = 128 / K = 512, which also serves N2 = 256,
+    # a width mv_conv1x1_chain_supported refuses) where they have the shape
+    for sb in ((2, 0) if sub == 2 else (0,)):
         if lib.mv_conv1x1_chain_res_supported(B, H, W, C, K, N2, sb, DT[dt]):
             wf, shf, _ = chain_res_fragments(conv3, bn3, conv1n, bn1n)
             y = empty((B, H // 2, W // 2, K) if sb else (B, H, W, K), torch.bfloat16)
@@ -465,6 +465,8 @@ def conv1x1_chain(x: Act, conv3, bn3, residual: Act, conv1n, bn1n, sub: int = 0)
             out.sub = 2 if sb else None
             out.pre = (conv1n, Act(t1, "map", x.batched))
             return out
+    if not lib.mv_conv1x1_chain_supported(M, C, K, N2, DT[dt]):
+        return None
     w3, s3, h3 = prep_conv(conv3, bn3, "krsc", dt)
     w1, s1, h1 = prep_conv(conv1n, bn1n, "krsc", dt)
     t1 = empty((B, H, W, N2), torch.bfloat16)
@@ -545,20 +547,44 @@ def chain_res_fragments(conv3, bn3, conv1n, bn1n):
     if hit is None:
         w3, h3 = _scaled_rows(conv3, bn3)
         w1n, hn = _scaled_rows(conv1n, bn1n)
-        K, T2 = w3.shape[0], w1n.shape[0] // 32
-        frags = np.empty((K // 32, 4 + 2 * T2, 2, 32, 8), np.float32)
-        e8 = np.arange(8)
-        for c in range(K // 32):
-            rows = slice(32 * c, 32 * c + 32)
-            for fh in range(2):
-                for kk in range(4):
-                    frags[c, kk, fh] = w3[rows][:, 16 * kk + 8 * fh + e8]
-                for s_ in range(2):
-                    cols = 32 * c + 16 * s_ + 4 * fh + np.array([0, 1, 2, 3, 8, 9, 10, 11])
-                    for a2 in range(T2):
-                        frags[c, 4 + T2 * s_ + a2, fh] = w1n[32 * a2:32 * a2 + 32][:, cols]
         sh = _rc_shift_rows(h3, hn)
-        hit = (_dev(frags.reshape(-1), torch.bfloat16), torch.from_numpy(sh.view(np.int32)).to(device()), conv1n)
+        hit = (_dev(_res_fragments(w3, w1n).reshape(-1), torch.bfloat16), torch.from_numpy(sh.view(np.int32)).to(device()), conv1n)
+        cache[key] = hit
+    return hit
+
+
+def _res_fragments(w3, w1n) -> np.ndarray:
+    """(K / 32, C / 16 + 2 N2 / 32, 2, 32, 8): per 32-channel chunk c of y, the C / 16 fragments of w3[32 c .., :] (k-step kk), then those
+    of the next conv1 w1n[:, 32 c ..] as (k-step s, row tile a2) with the reduction index in accumulator order.  A fragment is
+    [lane = 32 fh + r][8] = W[row0 + r][k0 + 8 fh ..] (mv_conv1x1_chain_res_fwd, mv_conv1x1_dual_chain_res_fwd)."""
+    K, KX, T2 = w3.shape[0], w3.shape[1] // 16, w1n.shape[0] // 32
+    frags = np.empty((K // 32, KX + 2 * T2, 2, 32, 8), np.float32)
+    e8 = np.arange(8)
+    for c in range(K // 32):
+        rows = slice(32 * c, 32 * c + 32)
+        for fh in range(2):
+            for kk in range(KX):
+                frags[c, kk, fh] = w3[rows][:, 16 * kk + 8 * fh + e8]
+            for s_ in range(2):
+                cols = 32 * c + 16 * s_ + 4 * fh + np.array([0, 1, 2, 3, 8, 9, 10, 11])
+                for a2 in range(T2):
+                    frags[c, KX + T2 * s_ + a2, fh] = w1n[32 * a2:32 * a2 + 32][:, cols]
+    return frags
+
+
+def chain_l2_dual_fragments(conv3, bn3, ds_conv, ds_bn, conv1n, bn1n):
+    """mv_conv1x1_dual_chain_res_fwd's operands: per 32-channel chunk the (C1 + C2) / 16 fragments of [scale3 W3 | scale_d W_d] and the
+    2 N2 / 32 of the scaled next conv1 (as _res_fragments), then the shift rows shift3 + shift_d | shiftN (cached on conv3)."""
+    cache = conv3._cache()
+    key = ("chain_l2_dual", _bn_id(bn3), id(ds_conv), _bn_id(ds_bn), id(conv1n), _bn_id(bn1n))
+    hit = cache.get(key)
+    if hit is None:
+        w3, h3 = _scaled_rows(conv3, bn3)
+        wd, hd = _scaled_rows(ds_conv, ds_bn)
+        w1n, hn = _scaled_rows(conv1n, bn1n)
+        frags = _res_fragments(np.concatenate([w3, wd], axis=1), w1n)
+        sh = _rc_shift_rows(h3 + hd, hn)
+        hit = (_dev(frags.reshape(-1), torch.bfloat16), torch.from_numpy(sh.view(np.int32)).to(device()), (ds_conv, conv1n))
         cache[key] = hit
     return hit
 
@@ -769,7 +795,8 @@ def conv1x1_dual_chain(x: Act, conv3, bn3, xin: Act, ds_conv, ds_bn, conv1n, bn1
     the same output run as one GEMM over the concatenated reduction [x | xin], the BatchNorm scales folded into the bf16
     weight rows.  Returns the block output with the next conv1's result attached (`.pre`), or None if unsupported."""
     dt = compute_dtype()
-    if dt != "bf16" or not (_pointwise(conv3) and _pointwise(ds_conv) and _pointwise(conv1n)):
+    if dt != "bf16" or not (_pointwise(conv3) and _pointwise(conv1n)) or tuple(ds_conv.kernel_size) != (1, 1) \
+            or tuple(ds_conv.padding) != (0, 0) or tuple(ds_conv.dilation) != (1, 1) or ds_conv.groups != 1:
         return None
     if conv3.out_channels != ds_conv.out_channels or conv3.out_channels != conv1n.in_channels:
         return None
@@ -782,7 +809,19 @@ def conv1x1_dual_chain(x: Act, conv3, bn3, xin: Act, ds_conv, ds_bn, conv1n, bn1
     if tuple(xin.t.shape[:3]) != (B, H, W) or C1 != conv3.in_channels or C2 != ds_conv.in_channels \
             or x.t.dtype != torch.bfloat16 or xin.t.dtype != torch.bfloat16:
         return None
-    if not _lib.load().mv_conv1x1_dual_chain_supported(M, C1, C2, K, N2, DT[dt]):
+    ds_stride = tuple(ds_conv.stride)
+    if store_y and (ds_stride == (1, 1) or (xin.sub is not None and ds_stride == (xin.sub, xin.sub))) \
+            and _lib.load().mv_conv1x1_dual_chain_res_supported(M, C1, C2, K, N2, DT[dt]):
+        # C = 128 / K = 512 (layer 2 entry): y stored, weights streamed (csrc/chain_l2.hip); xin is the map the downsample branch reads
+        wf, tab, _ = chain_l2_dual_fragments(conv3, bn3, ds_conv, ds_bn, conv1n, bn1n)
+        y = empty((B, H, W, K), torch.bfloat16)
+        t1 = empty((B, H, W, N2), torch.bfloat16)
+        _lib.call("mv_conv1x1_dual_chain_res_fwd", _ptr(x.t), _ptr(xin.t), _ptr(wf), _ptr(tab), _ptr(y), _ptr(t1), M, C1, C2, K, N2,
+                  DT[dt], stream_ptr())
+        out = Act(y, "map", x.batched)
+        out.pre = (conv1n, Act(t1, "map", x.batched))
+        return out
+    if not _pointwise(ds_conv) or not _lib.load().mv_conv1x1_dual_chain_supported(M, C1, C2, K, N2, DT[dt]):
         return None
     if not store_y and not _lib.get_flag("no_chain_rc0") and _lib.load().mv_conv1x1_chain_rc_supported(M, C1, K, N2, DT[dt]):
         wf, tab, _ = chain_rc0_fragments(conv3, bn3, ds_conv, ds_bn, conv1n, bn1n)      # the same function without its output map

@@ -51,6 +51,7 @@ enum { MV_OK = 0, MV_E_INVALID = -1, MV_E_UNSUPPORTED = -2, MV_E_OOM = -3 };
  *   streaming 1x1   "no_stream", "no_stream_narrow", "no_chain", "no_chain_stream", "no_dual_chain", "no_ln_stream", "ln_stream_192",
  *                   "no_chain_rc" (the layer-1 plan that leaves the first block output un-written: mv_conv1x1_chain_rc*_supported say no),
  *                   "no_chain_rc0" (host: first boundary on mv_conv1x1_dual_chain_fwd with y = NULL instead of mv_conv1x1_chain_rc0_fwd),
+ *                   "no_chain_l2" (layer 2's streamed boundaries of chain_l2.hip off: today's dual GEMM / chain_stream / dense launches),
  *                   "no_chain_res" (last boundary on chain1x1's form), "no_chain_sub" (block output written whole, not sub-sampled),
  *                   "no_swin_precise" (host: plain bf16 block Linears for Swin widths off the fused kernels)
  *   whole blocks    "no_bneck_tail",
@@ -202,6 +203,17 @@ int mv_conv1x1_dual_chain_fwd(const void* x, const void* x2, const void* wcat, c
 int mv_conv1x1_chain_res_supported(int N, int H, int W, int C, int K, int N2, int sub, int dtype);
 int mv_conv1x1_chain_res_fwd(const void* t2, const void* residual, const void* wfrag, const void* shifts, void* y, void* t1, int N, int H,
                              int W, int C, int K, int N2, int sub, int dtype, mv_stream_t stream);
+/* ---- a C = 128 / K = 512 stage (ResNet-50 / 101 / 152 layer2), weights streamed through LDS (csrc/chain_l2.hip): (3') also takes
+ * C = 128, K = 512, N2 = 128 or 256 (the last boundary, into layer3's conv1), sub = 0 or 2, N H W >= 16384, wfrag = 16 x (8 + 2 N2 / 32)
+ * fragments, shifts = 16 + N2 / 32 rows; and the stage's first boundary WITH its output stored:
+ *   mv_conv1x1_dual_chain_res_fwd: y = relu([t2 | x] . wcat^T + shift) (wcat = [scale3 w3 | scale_d w_d], shift = shift3 + shift_d),
+ *       t1 = relu(y . (scaleN w1n)^T + shiftN).  x is the map the downsample branch reads (the previous stage's output written
+ *       sub-sampled), [M][C2].  wfrag = 16 x ((C1 + C2) / 16 + 2 N2 / 32) fragments, per chunk c of y the (C1 + C2) / 16 of wcat[32c.., :]
+ *       then those of w1n as in (3'); shifts = 16 rows of shift + N2 / 32 rows of shiftN.  C1 = 128, C2 = 256, K = 512, N2 = 128,
+ *       M >= 16384.  The flag "no_chain_l2" switches all of this stage's forms off (today's launches run). */
+int mv_conv1x1_dual_chain_res_supported(int64_t M, int C1, int C2, int K, int N2, int dtype);
+int mv_conv1x1_dual_chain_res_fwd(const void* t2, const void* x, const void* wfrag, const void* shifts, void* y, void* t1, int64_t M,
+                                  int C1, int C2, int K, int N2, int dtype, mv_stream_t stream);
 int mv_conv1x1_chain_rc_supported(int64_t M, int C, int K, int N2, int dtype);
 int mv_conv1x1_chain_rc0_fwd(const void* t2, const void* x0, const void* wfrag, const void* shifts, void* t1, int64_t M, int C, int K,
                              int N2, int dtype, mv_stream_t stream);
