@@ -6,7 +6,7 @@
 //   middle (C2 = 0,   RES = true):  y  = relu( (s3 W3) . t2 + shift3 + res ),  t1 as above     (= chain_stream.hip's function)
 //   exit   (C2 = 0,   RES = true):  the same with N2 = 256 (layer 3's conv1), y written whole or (SUB) only at even (h, w)
 //
-// From chain_rc.hip: weights in MFMA FRAGMENT ORDER (host: ops._res_fragments), every BatchNorm scale folded into the bf16 rows, every
+// From chain_rc.hip: weights in MFMA FRAGMENT ORDER (host: ops.chain_acc_operands), every BatchNorm scale folded into the bf16 rows, every
 // shift one more k-step through the matrix pipe, the identity the C operand that STARTS y's accumulation, y kept in the accumulator
 // layout so that its packed bf16 chunk IS the B operand of the next conv1 (host-side permutation of that layer's reduction index),
 // the A fragments fetched RD matrix instructions ahead into a register ring, bf16 LDS patches only for the row-major stores.
@@ -19,7 +19,7 @@
 // Every s_waitcnt vmcnt inside a tile must be exact: no conditional load inside a chunk step (rows are clamped, stores past the end
 // get BUF_OOB), the chunk loop is unrolled by two (buffer parity is a compile-time constant), the last pair is peeled.
 #include <type_traits>
-#include "mfma_common.h"
+#include "chain_acc.h"
 
 namespace mv {
 
@@ -67,24 +67,7 @@ __global__ __launch_bounds__(WAVES * 64) void chain_l2_kernel(const ChainL2P p) 
     block_sync();
 
     const int fr = lane & 31, fh = lane >> 5;
-    typedef __attribute__((address_space(3))) const char* lds_cp;
-    unsigned wb0 = (unsigned)(uintptr_t)(lds_cp)wbuf + lane * 16;
-    unsigned wb1 = wb0 + CB;
-    unsigned sbase = (unsigned)(uintptr_t)(lds_cp)(const char*)shl + lane * 4;
-    asm volatile("" : "+v"(wb0), "+v"(wb1), "+v"(sbase));
-    auto afrag = [&](int buf, int f) -> bf16x8 {
-        const lds_cp b = (lds_cp)(uintptr_t)(buf ? wb1 : wb0);
-        return __builtin_bit_cast(bf16x8, *(const __attribute__((address_space(3))) u32x4_t*)(b + f * 1024));
-    };
-    auto sfrag = [&](int row) -> bf16x8 {                        // A of a shift step: lane r < 32 = [hi(shift[r]), lo(shift[r]), 0 ...]
-        u32x4_t v;
-        v[0] = *(const __attribute__((address_space(3))) unsigned*)((lds_cp)(uintptr_t)sbase + row * 256);
-        v[1] = 0u; v[2] = 0u; v[3] = 0u;
-        return __builtin_bit_cast(bf16x8, v);
-    };
-    u32x4_t onesv;                                               // its B operand: k-slots 0 and 1 are 1.0
-    onesv[0] = fh ? 0u : 0x3f803f80u; onesv[1] = 0u; onesv[2] = 0u; onesv[3] = 0u;
-    const bf16x8 ones = __builtin_bit_cast(bf16x8, onesv);
+    const AccOperands lds(wbuf, CB, 2 * CB, lane);               // the two chunk buffers, then the shift rows
 
     auto load_x = [&](uint4* xf, int tile) {                     // xf[kk]: k-step kk of [xa | xb] for pixel fr
         int m = tile * 32 + fr;
@@ -153,12 +136,7 @@ __global__ __launch_bounds__(WAVES * 64) void chain_l2_kernel(const ChainL2P p) 
         }
         f32x16 acc2[T2];                                         // the next conv1's accumulators start at its shift
 #pragma unroll
-        for (int a2 = 0; a2 < T2; ++a2) {
-            f32x16 z;
-#pragma unroll
-            for (int e = 0; e < 16; ++e) z[e] = 0.f;
-            acc2[a2] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(sfrag(NCH + a2), ones, z, 0, 0, 0);
-        }
+        for (int a2 = 0; a2 < T2; ++a2) acc2[a2] = lds.shift(NCH + a2);
 
         // one chunk: c & 1 == CI; LAST: the tile's last chunk, which also fetches the next round's x fragments (peeled: no branch)
         auto step = [&](auto CI, const int c, auto LAST) {
@@ -169,11 +147,11 @@ __global__ __launch_bounds__(WAVES * 64) void chain_l2_kernel(const ChainL2P p) 
             }
             bf16x8 ring[RD];
 #pragma unroll
-            for (int d = 0; d < RD; ++d) ring[d] = afrag(ci, d);
+            for (int d = 0; d < RD; ++d) ring[d] = lds.afrag(ci, d);
             auto take = [&](int i) -> bf16x8 {                   // fragment i of the chunk; its slot is refilled with i + RD
                 __builtin_amdgcn_sched_barrier(0);
                 const bf16x8 a = ring[i % RD];
-                if (i + RD < FPC) ring[i % RD] = afrag(ci, i + RD);
+                if (i + RD < FPC) ring[i % RD] = lds.afrag(ci, i + RD);
                 return a;
             };
             f32x16 a;
@@ -187,17 +165,14 @@ __global__ __launch_bounds__(WAVES * 64) void chain_l2_kernel(const ChainL2P p) 
 #pragma unroll
                 for (int g = 0; g < 4; ++g) {
                     const uint2 u = *(const uint2*)(ep + fr * PITCH + (8 * g + 4 * fh) * 2);
-                    a[4 * g] = __uint_as_float(u.x << 16);
-                    a[4 * g + 1] = __uint_as_float(u.x & 0xffff0000u);
-                    a[4 * g + 2] = __uint_as_float(u.y << 16);
-                    a[4 * g + 3] = __uint_as_float(u.y & 0xffff0000u);
+                    acc_set_quad(a, g, u.x, u.y);
                 }
                 wave_lds_fence();                                // the patch is free again (y staging below)
             } else {
 #pragma unroll
                 for (int e = 0; e < 16; ++e) a[e] = 0.f;
             }
-            a = __builtin_amdgcn_mfma_f32_32x32x16_bf16(sfrag(c), ones, a, 0, 0, 0);
+            a = lds.add_shift(c, a);
 #pragma unroll
             for (int kk = 0; kk < KX; ++kk) {
                 const bf16x8 af = take(kk);
@@ -266,21 +241,13 @@ template <int C1, int C2, bool RES, int N2, bool SUB, int WAVES, int AHEAD, int 
 static int chain_l2_go(ChainL2P& p, long long M, hipStream_t st) {
     constexpr int FPC = (C1 + C2) / 16 + N2 / 16;
     constexpr int SMEM = 2 * FPC * 1024 + (16 + N2 / 32) * 256 + WAVES * 32 * 144;
-    static_assert(SMEM <= 160 * 1024, "LDS");
     p.M = (int)M;
     p.tiles_m = (int)((M + 31) / 32);
-    int gx = 256;
-    const int need = (p.tiles_m + WAVES - 1) / WAVES;
-    if (gx > need) gx = need;
+    const int gx = chain_acc_grid(p.tiles_m, WAVES);
     const int per_block = (p.tiles_m + gx - 1) / gx;            // the largest share of a block
     p.rounds = (per_block + WAVES - 1) / WAVES;
     p.act = (per_block + p.rounds - 1) / p.rounds;
-    auto kern = chain_l2_kernel<C1, C2, RES, N2, SUB, WAVES, AHEAD, RD>;
-    static LdsAttrSite attr;
-    MV_HIP(attr.ensure((const void*)kern, SMEM));
-    hipLaunchKernelGGL(kern, dim3(gx), dim3(WAVES * 64), SMEM, st, p);
-    MV_LAUNCH_CHECK();
-    return MV_OK;
+    return chain_acc_go<chain_l2_kernel<C1, C2, RES, N2, SUB, WAVES, AHEAD, RD>, WAVES, SMEM>(p, gx, st);
 }
 
 static bool chain_l2_m_ok(long long M) { return M >= 16384 && M < (1LL << 31) - (1 << 20); }

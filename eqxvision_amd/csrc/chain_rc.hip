@@ -16,7 +16,7 @@
 // These kernels are not HBM-bound -- block 0's boundary took the same 90 us with and without its 205 MB store -- they are bound by
 // what ONE WAVE has to issue per 32-pixel tile: the matrix, vector and LDS instructions of a tile add up (profiles/r06/
 // resnet50_layer1_recompute_plan_ab.txt).  So everything here is about a short instruction stream per tile:
-//   * weights sit in LDS in MFMA FRAGMENT ORDER (host: ops.chain_rc_fragments): fragment f = 64 lanes x 16 bytes, so the copy in is
+//   * weights sit in LDS in MFMA FRAGMENT ORDER (host: ops.chain_acc_operands): fragment f = 64 lanes x 16 bytes, so the copy in is
 //     linear and every A operand is one conflict-free ds_read_b128 at a compile-time offset from an opaque base register;
 //   * the whole chain stays in the ACCUMULATOR layout (a lane holds 4 consecutive channels of one pixel per accumulator quad): a
 //     bf16 chunk of y IS the B operand of the next conv1 once the host has permuted that layer's reduction index to the
@@ -36,7 +36,7 @@
 // Measured alone, 128 images (profiles/r06/resnet50_layer1_recompute_plan_ab.txt): NPREV = 0 41-44 us (chain1x1_dual: 94 with y, 88
 // without), NPREV = 1 102-114 us (chain1x1: 109) -- of which ~35 us are its 205 MB of y stores, which do not overlap its 65 us of
 // instruction stream (debug-build ablations, same file); resnet50 B = 256: +2.5 ... 3.1 % with the plan on, same box.
-#include "mfma_common.h"
+#include "chain_acc.h"
 
 namespace mv {
 
@@ -61,48 +61,13 @@ __global__ __launch_bounds__(WAVES * 64) void chain_rc_kernel(const ChainRcP p) 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     char* ep = smem + NFRAG * 1024 + NSH * 256 + wave * (32 * PITCH);
 
-    {   // fragments + shift rows -> LDS: straight copies, several loads in flight per thread
-        constexpr int N16 = NFRAG * 64, U = 4;
-        for (int base = 0; base < N16; base += U * NT) {
-            uint4 v[U];
-#pragma unroll
-            for (int u = 0; u < U; ++u) {
-                const int i = base + u * NT + tid;
-                v[u] = ((const uint4*)p.wf)[i < N16 ? i : N16 - 1];
-            }
-#pragma unroll
-            for (int u = 0; u < U; ++u) {
-                const int i = base + u * NT + tid;
-                if (i < N16) ((uint4*)wl)[i] = v[u];
-            }
-        }
-        for (int i = tid; i < NSH * 64; i += NT) ((unsigned*)(wl + NFRAG * 1024))[i] = p.sh[i];
-    }
+    acc_copy_fragments<NFRAG, NT>(wl, p.wf, tid);                // fragments + shift rows -> LDS
+    for (int i = tid; i < NSH * 64; i += NT) ((unsigned*)(wl + NFRAG * 1024))[i] = p.sh[i];
     __syncthreads();
 
     const int fr = lane & 31, fh = lane >> 5;
-    typedef __attribute__((address_space(3))) const char* lds_cp;
-    // LDS bases as OPAQUE 32-bit addresses: every read below is then base + compile-time immediate.  (Left to itself hipcc
-    // materialised one address register per table read and spilled them; scratch reloads count in vmcnt and put
-    // `s_waitcnt vmcnt(0)` between the MFMAs.)
-    unsigned wbase0 = (unsigned)(uintptr_t)(lds_cp)wl + lane * 16;             // fragments 0 .. 63
-    unsigned wbase1 = wbase0 + 65536u;                                            // fragments 64 .. 127 (NPREV = 1)
-    unsigned sbase = (unsigned)(uintptr_t)(lds_cp)wl + NFRAG * 1024 + lane * 4;  // shift row r: + 256 r
-    asm volatile("" : "+v"(wbase0), "+v"(wbase1), "+v"(sbase));
-    auto afrag = [&](int f) -> bf16x8 {
-        const lds_cp b = (lds_cp)(uintptr_t)(f < 64 ? wbase0 : wbase1);
-        return __builtin_bit_cast(bf16x8, *(const __attribute__((address_space(3))) u32x4_t*)(b + (f & 63) * 1024));
-    };
-    // the A operand of a shift step: lane r < 32 holds [hi(shift[row r]), lo(shift[row r]), 0 x 6], lanes 32 .. 63 zeros
-    auto sfrag = [&](int row) -> bf16x8 {
-        u32x4_t v;
-        v[0] = *(const __attribute__((address_space(3))) unsigned*)((lds_cp)(uintptr_t)sbase + row * 256);
-        v[1] = 0u; v[2] = 0u; v[3] = 0u;
-        return __builtin_bit_cast(bf16x8, v);
-    };
-    u32x4_t onesv;                                               // its B operand: k-slots 0 and 1 (lanes fh = 0) are 1.0
-    onesv[0] = fh ? 0u : 0x3f803f80u; onesv[1] = 0u; onesv[2] = 0u; onesv[3] = 0u;
-    const bf16x8 ones = __builtin_bit_cast(bf16x8, onesv);
+    const AccOperands lds(wl, 65536u, NFRAG * 1024, lane);       // one resident table: fragment f -> (f >> 6, f & 63)
+    auto afrag = [&](int f) -> bf16x8 { return lds.afrag(f >> 6, f & 63); };
 
     // xf[0..3] = t2_0, xf[4..7] = x0 (the two K-sources of block 0's GEMM, in Wcat's column order), xf[8..11] = t2_1 (NPREV = 1)
     auto load_x = [&](uint4* xf, int tile) {
@@ -127,12 +92,7 @@ __global__ __launch_bounds__(WAVES * 64) void chain_rc_kernel(const ChainRcP p) 
         const int rows_left = p.M - tile_u * 32;
         f32x16 acc2[2];
 #pragma unroll
-        for (int a2 = 0; a2 < 2; ++a2) {                         // the next conv1's accumulators start at its shift
-            f32x16 z;
-#pragma unroll
-            for (int e = 0; e < 16; ++e) z[e] = 0.f;
-            acc2[a2] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(sfrag(NSH - 2 + a2), ones, z, 0, 0, 0);
-        }
+        for (int a2 = 0; a2 < 2; ++a2) acc2[a2] = lds.shift(NSH - 2 + a2);     // the next conv1's accumulators start at its shift
         // The tile's weight fragments are consumed in ONE fixed order (step i -> fragment fid(i)) and fetched RD steps ahead into a
         // rolling register ring; `sched_barrier` pins [take fragment, refill slot, MFMA].  Left to hipcc every fragment was read
         // right before its MFMA: one LDS round trip (~100 cycles) per 32-cycle matrix instruction, ~15k cycles per tile -- the
@@ -163,11 +123,7 @@ __global__ __launch_bounds__(WAVES * 64) void chain_rc_kernel(const ChainRcP p) 
             f32x16 a0[2];
             uint32_t pk[2][8];
 #pragma unroll
-            for (int cc = 0; cc < 2; ++cc) {
-#pragma unroll
-                for (int e = 0; e < 16; ++e) a0[cc][e] = 0.f;
-                a0[cc] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(sfrag(ps * 2 + cc), ones, a0[cc], 0, 0, 0);
-            }
+            for (int cc = 0; cc < 2; ++cc) a0[cc] = lds.shift(ps * 2 + cc);
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
                 const bf16x8 a = take(s0 + r);
@@ -177,22 +133,14 @@ __global__ __launch_bounds__(WAVES * 64) void chain_rc_kernel(const ChainRcP p) 
 #pragma unroll
             for (int cc = 0; cc < 2; ++cc)
 #pragma unroll
-                for (int g = 0; g < 4; ++g) {                    // y0 = bf16(relu(.)), as block 0 would have stored it
-                    pk[cc][2 * g] = relu_pack_bf2(a0[cc][4 * g], a0[cc][4 * g + 1]);
-                    pk[cc][2 * g + 1] = relu_pack_bf2(a0[cc][4 * g + 2], a0[cc][4 * g + 3]);
-                }
+                for (int g = 0; g < 4; ++g) acc_relu_pack_quad(a0[cc], g, pk[cc]);     // y0 = bf16(relu(.)), as block 0 would have stored it
             if constexpr (NPREV == 1) {
                 f32x16 a1[2];                                    // y1's accumulation STARTS at y0 (the identity), then shift1, then W3_1 . t2_1
 #pragma unroll
                 for (int cc = 0; cc < 2; ++cc) {
 #pragma unroll
-                    for (int g = 0; g < 4; ++g) {
-                        a1[cc][4 * g] = __uint_as_float(pk[cc][2 * g] << 16);
-                        a1[cc][4 * g + 1] = __uint_as_float(pk[cc][2 * g] & 0xffff0000u);
-                        a1[cc][4 * g + 2] = __uint_as_float(pk[cc][2 * g + 1] << 16);
-                        a1[cc][4 * g + 3] = __uint_as_float(pk[cc][2 * g + 1] & 0xffff0000u);
-                    }
-                    a1[cc] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(sfrag(8 + ps * 2 + cc), ones, a1[cc], 0, 0, 0);
+                    for (int g = 0; g < 4; ++g) acc_set_quad(a1[cc], g, pk[cc][2 * g], pk[cc][2 * g + 1]);
+                    a1[cc] = lds.add_shift(8 + ps * 2 + cc, a1[cc]);
                 }
 #pragma unroll
                 for (int r = 0; r < 8; ++r) {
@@ -204,8 +152,7 @@ __global__ __launch_bounds__(WAVES * 64) void chain_rc_kernel(const ChainRcP p) 
                 for (int cc = 0; cc < 2; ++cc)
 #pragma unroll
                     for (int g = 0; g < 4; ++g) {
-                        pk[cc][2 * g] = relu_pack_bf2(a1[cc][4 * g], a1[cc][4 * g + 1]);
-                        pk[cc][2 * g + 1] = relu_pack_bf2(a1[cc][4 * g + 2], a1[cc][4 * g + 3]);
+                        acc_relu_pack_quad(a1[cc], g, pk[cc]);
                         // row-major staging for the store: row = pixel fr, 4 consecutive channels = 8 bytes
                         *(uint2*)(ep + fr * PITCH + (cc * 32 + 8 * g + 4 * fh) * 2) = make_uint2(pk[cc][2 * g], pk[cc][2 * g + 1]);
                     }
@@ -271,16 +218,7 @@ int chain_rc_supported(long long M, int C, int K, int N2, int dtype) {
 template <int NPREV, int WAVES, int RD>
 static int chain_rc_go(ChainRcP& p, hipStream_t st) {
     constexpr int SMEM = 8 * (12 + 4 * NPREV) * 1024 + (8 * (1 + NPREV) + 2) * 256 + WAVES * 32 * 144;
-    static_assert(SMEM <= 160 * 1024, "LDS");
-    int gx = 256;
-    const int need = (p.tiles_m + WAVES - 1) / WAVES;
-    if (gx > need) gx = need;
-    auto kern = chain_rc_kernel<NPREV, WAVES, RD>;
-    static LdsAttrSite attr;
-    MV_HIP(attr.ensure((const void*)kern, SMEM));
-    hipLaunchKernelGGL(kern, dim3(gx), dim3(WAVES * 64), SMEM, st, p);
-    MV_LAUNCH_CHECK();
-    return MV_OK;
+    return chain_acc_go<chain_rc_kernel<NPREV, WAVES, RD>, WAVES, SMEM>(p, chain_acc_grid(p.tiles_m, WAVES), st);
 }
 
 int chain_rc_launch(const void* t2, const void* t2_prev, const void* x0, const void* wfrag, const void* shifts, void* y, void* t1,
@@ -338,44 +276,13 @@ __global__ __launch_bounds__(WAVES * 64) void chain_res_kernel(const ChainResP p
     char* wl = smem;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     char* ep = smem + NFRAG * 1024 + NSH * 256 + wave * (32 * PITCH);
-    {
-        constexpr int N16 = NFRAG * 64, U = 4;
-        for (int base = 0; base < N16; base += U * NT) {
-            uint4 v[U];
-#pragma unroll
-            for (int u = 0; u < U; ++u) {
-                const int i = base + u * NT + tid;
-                v[u] = ((const uint4*)p.wf)[i < N16 ? i : N16 - 1];
-            }
-#pragma unroll
-            for (int u = 0; u < U; ++u) {
-                const int i = base + u * NT + tid;
-                if (i < N16) ((uint4*)wl)[i] = v[u];
-            }
-        }
-        for (int i = tid; i < NSH * 64; i += NT) ((unsigned*)(wl + NFRAG * 1024))[i] = p.sh[i];
-    }
+    acc_copy_fragments<NFRAG, NT>(wl, p.wf, tid);
+    for (int i = tid; i < NSH * 64; i += NT) ((unsigned*)(wl + NFRAG * 1024))[i] = p.sh[i];
     __syncthreads();
 
     const int fr = lane & 31, fh = lane >> 5;
-    typedef __attribute__((address_space(3))) const char* lds_cp;
-    unsigned wbase0 = (unsigned)(uintptr_t)(lds_cp)wl + lane * 16;
-    unsigned wbase1 = wbase0 + 65536u;
-    unsigned sbase = (unsigned)(uintptr_t)(lds_cp)wl + NFRAG * 1024 + lane * 4;
-    asm volatile("" : "+v"(wbase0), "+v"(wbase1), "+v"(sbase));
-    auto afrag = [&](int f) -> bf16x8 {
-        const lds_cp b = (lds_cp)(uintptr_t)(f < 64 ? wbase0 : wbase1);
-        return __builtin_bit_cast(bf16x8, *(const __attribute__((address_space(3))) u32x4_t*)(b + (f & 63) * 1024));
-    };
-    auto sfrag = [&](int row) -> bf16x8 {
-        u32x4_t v;
-        v[0] = *(const __attribute__((address_space(3))) unsigned*)((lds_cp)(uintptr_t)sbase + row * 256);
-        v[1] = 0u; v[2] = 0u; v[3] = 0u;
-        return __builtin_bit_cast(bf16x8, v);
-    };
-    u32x4_t onesv;
-    onesv[0] = fh ? 0u : 0x3f803f80u; onesv[1] = 0u; onesv[2] = 0u; onesv[3] = 0u;
-    const bf16x8 ones = __builtin_bit_cast(bf16x8, onesv);
+    const AccOperands lds(wl, 65536u, NFRAG * 1024, lane);
+    auto afrag = [&](int f) -> bf16x8 { return lds.afrag(f >> 6, f & 63); };
 
     auto load_x = [&](uint4* xf, int tile) {
         int m = tile * 32 + fr;
@@ -434,12 +341,7 @@ __global__ __launch_bounds__(WAVES * 64) void chain_res_kernel(const ChainResP p
         };
         f32x16 acc2[T2];
 #pragma unroll
-        for (int a2 = 0; a2 < T2; ++a2) {
-            f32x16 z;
-#pragma unroll
-            for (int e = 0; e < 16; ++e) z[e] = 0.f;
-            acc2[a2] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(sfrag(8 + a2), ones, z, 0, 0, 0);
-        }
+        for (int a2 = 0; a2 < T2; ++a2) acc2[a2] = lds.shift(8 + a2);
 #pragma unroll
         for (int ps = 0; ps < 4; ++ps) {
             const int s0 = ps * SL;
@@ -456,12 +358,9 @@ __global__ __launch_bounds__(WAVES * 64) void chain_res_kernel(const ChainResP p
 #pragma unroll
                 for (int g = 0; g < 4; ++g) {
                     const uint2 u = *(const uint2*)(ep + fr * PITCH + (cc * 32 + 8 * g + 4 * fh) * 2);
-                    a[cc][4 * g] = __uint_as_float(u.x << 16);
-                    a[cc][4 * g + 1] = __uint_as_float(u.x & 0xffff0000u);
-                    a[cc][4 * g + 2] = __uint_as_float(u.y << 16);
-                    a[cc][4 * g + 3] = __uint_as_float(u.y & 0xffff0000u);
+                    acc_set_quad(a[cc], g, u.x, u.y);
                 }
-                a[cc] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(sfrag(ps * 2 + cc), ones, a[cc], 0, 0, 0);
+                a[cc] = lds.add_shift(ps * 2 + cc, a[cc]);
             }
             wave_lds_fence();                                    // the patch is free again (y staging below)
 #pragma unroll
@@ -475,8 +374,7 @@ __global__ __launch_bounds__(WAVES * 64) void chain_res_kernel(const ChainResP p
             for (int cc = 0; cc < 2; ++cc)
 #pragma unroll
                 for (int g = 0; g < 4; ++g) {
-                    pk[cc][2 * g] = relu_pack_bf2(a[cc][4 * g], a[cc][4 * g + 1]);
-                    pk[cc][2 * g + 1] = relu_pack_bf2(a[cc][4 * g + 2], a[cc][4 * g + 3]);
+                    acc_relu_pack_quad(a[cc], g, pk[cc]);
                     *(uint2*)(ep + fr * PITCH + (cc * 32 + 8 * g + 4 * fh) * 2) = make_uint2(pk[cc][2 * g], pk[cc][2 * g + 1]);
                 }
             if (ps == 3) load_x(xf, refill);
@@ -546,7 +444,6 @@ int chain_res_launch(const void* t2, const void* residual, const void* wfrag, co
                      int sub, hipStream_t st) {
     constexpr int WAVES = 8, N2 = 128, RD = 6;
     constexpr int SMEM = 8 * (4 + 2 * N2 / 32) * 1024 + (8 + N2 / 32) * 256 + WAVES * 32 * 144;
-    static_assert(SMEM <= 160 * 1024, "LDS");
     ChainResP p;
     p.t2 = (const bf16_t*)t2; p.res = (const bf16_t*)residual; p.wf = (const bf16_t*)wfrag; p.sh = (const unsigned*)shifts;
     p.y = (bf16_t*)y; p.t1 = (bf16_t*)t1;
@@ -554,24 +451,13 @@ int chain_res_launch(const void* t2, const void* residual, const void* wfrag, co
     p.M = (int)M;
     p.tiles_m = (int)((M + 31) / 32);
     p.subH = H; p.subW = W;
-    int gx = 256;
-    const int need = (p.tiles_m + WAVES - 1) / WAVES;
-    if (gx > need) gx = need;
+    const int gx = chain_acc_grid(p.tiles_m, WAVES);
     if (sub) {
-        auto kern = chain_res_kernel<N2, true, WAVES, RD>;
-        static LdsAttrSite attr;
-        MV_HIP(attr.ensure((const void*)kern, SMEM));
         set_kernel_name("chain_res_bf16_64_256_128_ysub2");
-        hipLaunchKernelGGL(kern, dim3(gx), dim3(WAVES * 64), SMEM, st, p);
-    } else {
-        auto kern = chain_res_kernel<N2, false, WAVES, RD>;
-        static LdsAttrSite attr;
-        MV_HIP(attr.ensure((const void*)kern, SMEM));
-        set_kernel_name("chain_res_bf16_64_256_128");
-        hipLaunchKernelGGL(kern, dim3(gx), dim3(WAVES * 64), SMEM, st, p);
+        return chain_acc_go<chain_res_kernel<N2, true, WAVES, RD>, WAVES, SMEM>(p, gx, st);
     }
-    MV_LAUNCH_CHECK();
-    return MV_OK;
+    set_kernel_name("chain_res_bf16_64_256_128");
+    return chain_acc_go<chain_res_kernel<N2, false, WAVES, RD>, WAVES, SMEM>(p, gx, st);
 }
 
 }  // namespace mv

@@ -105,21 +105,19 @@ class _ResNetBottleneck(Module):
         conv1 output attached to its input."""
         pre = x.pre if ops.is_act(x) else None
         x = ops.as_map(x)
-        ds = self.downsample
-        conv_ds = isinstance(ds, nn.Sequential) and len(ds) == 2 and isinstance(ds[0], nn.Conv2d) and \
-            isinstance(ds[1], nn.BatchNorm)
+        ds = _conv_downsample(self)
         if pre is not None and pre[0] is self.conv1:
             out = pre[1]
         else:
             out = ops.conv2d(x, self.conv1, self.bn1, "relu")
-        if isinstance(ds, nn.Identity):
+        if isinstance(self.downsample, nn.Identity):
             # identity block on a map that fits a CU: conv2 + conv3 + identity in one launch, the `width`-channel intermediate
             # stays in LDS (ops.bottleneck_tail; None when the library has no such path for the shapes)
             y = ops.bottleneck_tail(out, self.conv2, self.bn2, self.conv3, self.bn3, x)
             if y is not None:
                 return y
         out = ops.conv2d(out, self.conv2, self.bn2, "relu")
-        if conv_ds:
+        if ds is not None:
             # identity = BN(conv1x1(x)) (resnet.py:295-303): it and conv3 add into one output -> one GEMM over the
             # concatenated reduction [out | x]; the identity map is never materialised
             if isinstance(nxt, _ResNetBottleneck):
@@ -155,8 +153,7 @@ def _reads_strided_only(nxt, out) -> bool:
     if cd is None or not ops._pointwise(nxt.conv1):
         return False
     conv, bn = cd
-    if tuple(conv.kernel_size) != (1, 1) or tuple(conv.stride) != (2, 2) or tuple(conv.padding) != (0, 0) \
-            or tuple(conv.dilation) != (1, 1) or conv.groups != 1:
+    if not ops._strided_pointwise(conv) or tuple(conv.stride) != (2, 2):
         return False
     B, H, W, _ = out.t.shape
     if H % 2 or W % 2 or tuple(nxt.conv2.stride) != (2, 2):

@@ -427,9 +427,24 @@ def _conv2d_padded_k(x: Act, conv, bn, act, prep, dims) -> Act:
     return Act(y, "map", x.batched)
 
 
-def _pointwise(conv) -> bool:
-    return (tuple(conv.kernel_size) == (1, 1) and tuple(conv.stride) == (1, 1) and tuple(conv.padding) == (0, 0)
+def _strided_pointwise(conv) -> bool:
+    """1x1, no padding, no dilation, one group, the same stride along both axes."""
+    s = tuple(conv.stride)
+    return (tuple(conv.kernel_size) == (1, 1) and s[0] == s[1] and tuple(conv.padding) == (0, 0)
             and tuple(conv.dilation) == (1, 1) and conv.groups == 1)
+
+
+def _pointwise(conv) -> bool:
+    return _strided_pointwise(conv) and tuple(conv.stride) == (1, 1)
+
+
+def _chained(y: torch.Tensor, conv1n, t1: torch.Tensor, batched, sub=None) -> Act:
+    """What a chain entry returns: the block output y (`.sub`: written only at every sub-th row and column) with the next
+    block's conv1 result attached as `.pre = (conv1n, Act)`."""
+    out = Act(y, "map", batched)
+    out.sub = sub
+    out.pre = (conv1n, Act(t1, "map", batched))
+    return out
 
 
 def conv1x1_chain(x: Act, conv3, bn3, residual: Act, conv1n, bn1n, sub: int = 0) -> Optional[Act]:
@@ -456,15 +471,12 @@ def conv1x1_chain(x: Act, conv3, bn3, residual: Act, conv1n, bn1n, sub: int = 0)
     # a width mv_conv1x1_chain_supported refuses) where they have the shape
     for sb in ((2, 0) if sub == 2 else (0,)):
         if lib.mv_conv1x1_chain_res_supported(B, H, W, C, K, N2, sb, DT[dt]):
-            wf, shf, _ = chain_res_fragments(conv3, bn3, conv1n, bn1n)
+            wf, shf, _ = chain_acc_operands(conv3, [[(conv3, bn3)]], conv1n, bn1n)
             y = empty((B, H // 2, W // 2, K) if sb else (B, H, W, K), torch.bfloat16)
             t1 = empty((B, H, W, N2), torch.bfloat16)
             _lib.call("mv_conv1x1_chain_res_fwd", _ptr(x.t), _ptr(residual.t), _ptr(wf), _ptr(shf), _ptr(y), _ptr(t1), B, H, W, C, K, N2,
                       sb, DT[dt], stream_ptr())
-            out = Act(y, "map", x.batched)
-            out.sub = 2 if sb else None
-            out.pre = (conv1n, Act(t1, "map", x.batched))
-            return out
+            return _chained(y, conv1n, t1, x.batched, sub=2 if sb else None)
     if not lib.mv_conv1x1_chain_supported(M, C, K, N2, DT[dt]):
         return None
     w3, s3, h3 = prep_conv(conv3, bn3, "krsc", dt)
@@ -474,15 +486,11 @@ def conv1x1_chain(x: Act, conv3, bn3, residual: Act, conv1n, bn1n, sub: int = 0)
         y = empty((B, H // 2, W // 2, K), torch.bfloat16)
         _lib.call("mv_conv1x1_chain_sub_fwd", _ptr(x.t), _ptr(w3), _ptr(s3), _ptr(h3), _ptr(residual.t), _ptr(y), _ptr(w1), _ptr(s1),
                   _ptr(h1), _ptr(t1), B, H, W, C, K, N2, DT[dt], stream_ptr())
-        out = Act(y, "map", x.batched)
-        out.sub = 2
-    else:
-        y = empty((B, H, W, K), torch.bfloat16)
-        _lib.call("mv_conv1x1_chain_fwd", _ptr(x.t), _ptr(w3), _ptr(s3), _ptr(h3), _ptr(residual.t), _ptr(y), _ptr(w1), _ptr(s1),
-                  _ptr(h1), _ptr(t1), M, C, K, N2, DT[dt], stream_ptr())
-        out = Act(y, "map", x.batched)
-    out.pre = (conv1n, Act(t1, "map", x.batched))
-    return out
+        return _chained(y, conv1n, t1, x.batched, sub=2)
+    y = empty((B, H, W, K), torch.bfloat16)
+    _lib.call("mv_conv1x1_chain_fwd", _ptr(x.t), _ptr(w3), _ptr(s3), _ptr(h3), _ptr(residual.t), _ptr(y), _ptr(w1), _ptr(s1),
+              _ptr(h1), _ptr(t1), M, C, K, N2, DT[dt], stream_ptr())
+    return _chained(y, conv1n, t1, x.batched)
 
 
 def _rc_shift_rows(*vecs) -> np.ndarray:
@@ -500,55 +508,23 @@ def _rc_shift_rows(*vecs) -> np.ndarray:
     return np.concatenate(rows, 0)
 
 
-def _rc_conv1n_frags(frags, base, w1n, c):
-    for fh in range(2):
-        for s_ in range(2):
-            cols = 32 * c + 16 * s_ + 4 * fh + np.array([0, 1, 2, 3, 8, 9, 10, 11])
-            for a2 in range(w1n.shape[0] // 32):
-                frags[c, base + 2 * s_ + a2, fh] = w1n[32 * a2:32 * a2 + 32][:, cols]
-
-
-def chain_rc_fragments(conv3_0, bn3_0, ds_conv, ds_bn, conv3_1, bn3_1, conv1n, bn1n):
-    """Operands of mv_conv1x1_chain_rc_fwd (header): per 32-channel chunk c of the block output, 16 MFMA A fragments
-    [lane = 32 fh + r][8] -- 8 of [scale3 W3_0 | scale_d W_d][32 c + r, 16 kk + 8 fh ..], 4 of scale1 W3_1[32 c + r, ...], 4 of the
-    scaled next conv1 (k-step s, row tile a2) with the reduction index in accumulator order -- and the 18 shift rows (cached on conv3_1)."""
-    cache = conv3_1._cache()
-    key = ("chain_rc", _bn_id(bn3_1), id(conv3_0), _bn_id(bn3_0), id(ds_conv), _bn_id(ds_bn), id(conv1n), _bn_id(bn1n))
+def chain_acc_operands(cache_on, y_blocks, conv1n, bn1n):
+    """The (fragments, shift rows, kept modules) of the accumulator-layout chain kernels (csrc/chain_acc.h; header:
+    mv_conv1x1_chain_rc_fwd, _chain_rc0_fwd, _chain_res_fwd, _dual_chain_res_fwd), cached on `cache_on`.  `y_blocks` lists the
+    pointwise (conv, bn) groups that produce y, in the order of the kernel's reduction: the groups of ONE inner list add into the
+    same accumulation, so their shifts are summed into one block of shift rows; every inner list has a block of its own.  Per
+    32-channel chunk of y: the k-step fragments of the groups' scaled weight rows side by side, then the next conv1's
+    (_res_fragments); shift rows: one block per inner list, then the next conv1's (_rc_shift_rows)."""
+    cache = cache_on._cache()
+    key = ("chain_acc", tuple(tuple((id(c), _bn_id(b)) for c, b in blk) for blk in y_blocks), id(conv1n), _bn_id(bn1n))
     hit = cache.get(key)
     if hit is None:
-        w30, h30 = _scaled_rows(conv3_0, bn3_0)
-        wd, hd = _scaled_rows(ds_conv, ds_bn)
-        wcat = np.concatenate([w30, wd], axis=1)                                  # [256][128], as ops._dual_weights
-        w31, h1 = _scaled_rows(conv3_1, bn3_1)                                    # [256][64]
-        w1n, hn = _scaled_rows(conv1n, bn1n)                                      # [64][256]
-        K = wcat.shape[0]
-        frags = np.empty((K // 32, 16, 2, 32, 8), np.float32)                      # (chunk, fragment, fh, r, e)
-        e8 = np.arange(8)
-        for c in range(K // 32):
-            rows = slice(32 * c, 32 * c + 32)
-            for fh in range(2):
-                for kk in range(8):
-                    frags[c, kk, fh] = wcat[rows][:, 16 * kk + 8 * fh + e8]
-                for kk in range(4):
-                    frags[c, 8 + kk, fh] = w31[rows][:, 16 * kk + 8 * fh + e8]
-            _rc_conv1n_frags(frags, 12, w1n, c)
-        sh = _rc_shift_rows(h30 + hd, h1, hn)
-        hit = (_dev(frags.reshape(-1), torch.bfloat16), torch.from_numpy(sh.view(np.int32)).to(device()), (conv3_0, ds_conv, conv1n))
-        cache[key] = hit
-    return hit
-
-
-def chain_res_fragments(conv3, bn3, conv1n, bn1n):
-    """mv_conv1x1_chain_res_fwd's operands: per 32-channel chunk 4 fragments of scale3 W3 and 2 N2 / 32 of the scaled next conv1
-    (k-step s, row tile a2; accumulator order), then the shift rows shift3 | shiftN (cached on conv3)."""
-    cache = conv3._cache()
-    key = ("chain_res", _bn_id(bn3), id(conv1n), _bn_id(bn1n))
-    hit = cache.get(key)
-    if hit is None:
-        w3, h3 = _scaled_rows(conv3, bn3)
+        blocks = [[_scaled_rows(c, b) for c, b in blk] for blk in y_blocks]
+        wy = np.concatenate([w for blk in blocks for w, _ in blk], axis=1)
         w1n, hn = _scaled_rows(conv1n, bn1n)
-        sh = _rc_shift_rows(h3, hn)
-        hit = (_dev(_res_fragments(w3, w1n).reshape(-1), torch.bfloat16), torch.from_numpy(sh.view(np.int32)).to(device()), conv1n)
+        sh = _rc_shift_rows(*[np.add.reduce([h for _, h in blk]) for blk in blocks], hn)
+        others = tuple(c for blk in y_blocks for c, _ in blk if c is not cache_on) + (conv1n,)   # keeps the id()s in the key alive
+        hit = (_dev(_res_fragments(wy, w1n).reshape(-1), torch.bfloat16), torch.from_numpy(sh.view(np.int32)).to(device()), others)
         cache[key] = hit
     return hit
 
@@ -572,49 +548,6 @@ def _res_fragments(w3, w1n) -> np.ndarray:
     return frags
 
 
-def chain_l2_dual_fragments(conv3, bn3, ds_conv, ds_bn, conv1n, bn1n):
-    """mv_conv1x1_dual_chain_res_fwd's operands: per 32-channel chunk the (C1 + C2) / 16 fragments of [scale3 W3 | scale_d W_d] and the
-    2 N2 / 32 of the scaled next conv1 (as _res_fragments), then the shift rows shift3 + shift_d | shiftN (cached on conv3)."""
-    cache = conv3._cache()
-    key = ("chain_l2_dual", _bn_id(bn3), id(ds_conv), _bn_id(ds_bn), id(conv1n), _bn_id(bn1n))
-    hit = cache.get(key)
-    if hit is None:
-        w3, h3 = _scaled_rows(conv3, bn3)
-        wd, hd = _scaled_rows(ds_conv, ds_bn)
-        w1n, hn = _scaled_rows(conv1n, bn1n)
-        frags = _res_fragments(np.concatenate([w3, wd], axis=1), w1n)
-        sh = _rc_shift_rows(h3 + hd, hn)
-        hit = (_dev(frags.reshape(-1), torch.bfloat16), torch.from_numpy(sh.view(np.int32)).to(device()), (ds_conv, conv1n))
-        cache[key] = hit
-    return hit
-
-
-def chain_rc0_fragments(conv3_0, bn3_0, ds_conv, ds_bn, conv1n, bn1n):
-    """mv_conv1x1_chain_rc0_fwd's operands: 12 fragments per 32-channel chunk (the 8 of [scale3 W3_0 | scale_d W_d], the 4 of the scaled
-    next conv1 in accumulator order) and the 10 shift rows (cached on conv3_0)."""
-    cache = conv3_0._cache()
-    key = ("chain_rc0", _bn_id(bn3_0), id(ds_conv), _bn_id(ds_bn), id(conv1n), _bn_id(bn1n))
-    hit = cache.get(key)
-    if hit is None:
-        w30, h30 = _scaled_rows(conv3_0, bn3_0)
-        wd, hd = _scaled_rows(ds_conv, ds_bn)
-        wcat = np.concatenate([w30, wd], axis=1)
-        w1n, hn = _scaled_rows(conv1n, bn1n)
-        K = wcat.shape[0]
-        frags = np.empty((K // 32, 12, 2, 32, 8), np.float32)
-        e8 = np.arange(8)
-        for c in range(K // 32):
-            rows = slice(32 * c, 32 * c + 32)
-            for fh in range(2):
-                for kk in range(8):
-                    frags[c, kk, fh] = wcat[rows][:, 16 * kk + 8 * fh + e8]
-            _rc_conv1n_frags(frags, 8, w1n, c)
-        sh = _rc_shift_rows(h30 + hd, hn)
-        hit = (_dev(frags.reshape(-1), torch.bfloat16), torch.from_numpy(sh.view(np.int32)).to(device()), (ds_conv, conv1n))
-        cache[key] = hit
-    return hit
-
-
 def conv1x1_chain_rc(t2: Act, t2_prev: Act, x0: Act, conv3_0, bn3_0, ds_conv, ds_bn, conv3_1, bn3_1, conv1n, bn1n) -> Optional[Act]:
     """The boundary between the second and the third bottleneck of a stage whose FIRST block output was not written
     (ops.conv1x1_dual_chain(..., store_y=False)): y0 = relu(bn3_0(conv3_0(t2_prev)) + ds_bn(ds_conv(x0))) is recomputed from its
@@ -635,14 +568,13 @@ def conv1x1_chain_rc(t2: Act, t2_prev: Act, x0: Act, conv3_0, bn3_0, ds_conv, ds
         return None
     if not _lib.load().mv_conv1x1_chain_rc_supported(M, C, K, N2, DT[dt]):
         return None
-    wf, tab, _ = chain_rc_fragments(conv3_0, bn3_0, ds_conv, ds_bn, conv3_1, bn3_1, conv1n, bn1n)
+    # y0's two sources share an accumulation (one shift block, shift3_0 + shift_d); conv3_1 continues from bf16(y0) with its own
+    wf, tab, _ = chain_acc_operands(conv3_1, [[(conv3_0, bn3_0), (ds_conv, ds_bn)], [(conv3_1, bn3_1)]], conv1n, bn1n)
     y = empty((B, H, W, K), torch.bfloat16)
     t1 = empty((B, H, W, N2), torch.bfloat16)
     _lib.call("mv_conv1x1_chain_rc_fwd", _ptr(t2.t), _ptr(t2_prev.t), _ptr(x0.t), _ptr(wf), _ptr(tab), _ptr(y), _ptr(t1), M, C, K, N2,
               DT[dt], stream_ptr())
-    out = Act(y, "map", t2.batched)
-    out.pre = (conv1n, Act(t1, "map", t2.batched))
-    return out
+    return _chained(y, conv1n, t1, t2.batched)
 
 
 def _fold(conv, bn):
@@ -705,13 +637,8 @@ def bottleneck_tail(t1: Act, conv2, bn2, conv3, bn3, identity: Act) -> Optional[
 def _scaled_rows(conv, bn) -> Tuple[np.ndarray, np.ndarray]:
     """A pointwise conv + BatchNorm(inference) as (scale[k] * W[k, :], shift[k]) in fp32."""
     w = np.asarray(conv.weight, np.float32).reshape(conv.out_channels, -1)
-    bias = None if conv.bias is None else np.asarray(conv.bias, np.float32).reshape(-1)
-    if bn is not None:
-        scale, shift = bn_fold(bn)
-        if bias is not None:
-            shift = shift + bias * scale
-        return w * scale[:, None], shift
-    return w, (np.zeros(conv.out_channels, np.float32) if bias is None else bias)
+    scale, shift = _fold(conv, bn)
+    return w * scale[:, None], shift
 
 
 def _dual_weights(conv3, bn3, ds_conv, ds_bn):
@@ -734,8 +661,7 @@ def conv1x1_dual(x: Act, conv3, bn3, xin: Act, ds_conv, ds_bn, act="relu") -> Op
     if dt != "bf16" or not _pointwise(conv3):
         return None
     sd = tuple(ds_conv.stride)
-    if tuple(ds_conv.kernel_size) != (1, 1) or tuple(ds_conv.padding) != (0, 0) or tuple(ds_conv.dilation) != (1, 1) \
-            or ds_conv.groups != 1 or sd[0] != sd[1] or conv3.out_channels != ds_conv.out_channels:
+    if not _strided_pointwise(ds_conv) or conv3.out_channels != ds_conv.out_channels:
         return None
     if _bn_training(bn3) or _bn_training(ds_bn):
         return None
@@ -795,8 +721,7 @@ def conv1x1_dual_chain(x: Act, conv3, bn3, xin: Act, ds_conv, ds_bn, conv1n, bn1
     the same output run as one GEMM over the concatenated reduction [x | xin], the BatchNorm scales folded into the bf16
     weight rows.  Returns the block output with the next conv1's result attached (`.pre`), or None if unsupported."""
     dt = compute_dtype()
-    if dt != "bf16" or not (_pointwise(conv3) and _pointwise(conv1n)) or tuple(ds_conv.kernel_size) != (1, 1) \
-            or tuple(ds_conv.padding) != (0, 0) or tuple(ds_conv.dilation) != (1, 1) or ds_conv.groups != 1:
+    if dt != "bf16" or not (_pointwise(conv3) and _pointwise(conv1n)) or not _strided_pointwise(ds_conv):
         return None
     if conv3.out_channels != ds_conv.out_channels or conv3.out_channels != conv1n.in_channels:
         return None
@@ -813,18 +738,16 @@ def conv1x1_dual_chain(x: Act, conv3, bn3, xin: Act, ds_conv, ds_bn, conv1n, bn1
     if store_y and (ds_stride == (1, 1) or (xin.sub is not None and ds_stride == (xin.sub, xin.sub))) \
             and _lib.load().mv_conv1x1_dual_chain_res_supported(M, C1, C2, K, N2, DT[dt]):
         # C = 128 / K = 512 (layer 2 entry): y stored, weights streamed (csrc/chain_l2.hip); xin is the map the downsample branch reads
-        wf, tab, _ = chain_l2_dual_fragments(conv3, bn3, ds_conv, ds_bn, conv1n, bn1n)
+        wf, tab, _ = chain_acc_operands(conv3, [[(conv3, bn3), (ds_conv, ds_bn)]], conv1n, bn1n)
         y = empty((B, H, W, K), torch.bfloat16)
         t1 = empty((B, H, W, N2), torch.bfloat16)
         _lib.call("mv_conv1x1_dual_chain_res_fwd", _ptr(x.t), _ptr(xin.t), _ptr(wf), _ptr(tab), _ptr(y), _ptr(t1), M, C1, C2, K, N2,
                   DT[dt], stream_ptr())
-        out = Act(y, "map", x.batched)
-        out.pre = (conv1n, Act(t1, "map", x.batched))
-        return out
+        return _chained(y, conv1n, t1, x.batched)
     if not _pointwise(ds_conv) or not _lib.load().mv_conv1x1_dual_chain_supported(M, C1, C2, K, N2, DT[dt]):
         return None
     if not store_y and not _lib.get_flag("no_chain_rc0") and _lib.load().mv_conv1x1_chain_rc_supported(M, C1, K, N2, DT[dt]):
-        wf, tab, _ = chain_rc0_fragments(conv3, bn3, ds_conv, ds_bn, conv1n, bn1n)      # the same function without its output map
+        wf, tab, _ = chain_acc_operands(conv3, [[(conv3, bn3), (ds_conv, ds_bn)]], conv1n, bn1n)   # the same function without its output map
         t1 = empty((B, H, W, N2), torch.bfloat16)
         _lib.call("mv_conv1x1_chain_rc0_fwd", _ptr(x.t), _ptr(xin.t), _ptr(wf), _ptr(tab), _ptr(t1), M, C1, K, N2, DT[dt], stream_ptr())
         return Act(t1, "map", x.batched)
@@ -836,9 +759,7 @@ def conv1x1_dual_chain(x: Act, conv3, bn3, xin: Act, ds_conv, ds_bn, conv1n, bn1
               _ptr(h1), _ptr(t1), M, C1, C2, K, N2, DT[dt], stream_ptr())
     if not store_y:                     # the block output stays un-written (the next boundary recomputes it: ops.conv1x1_chain_rc):
         return Act(t1, "map", x.batched)        # the caller gets the next block's conv1 output itself
-    out = Act(y, "map", x.batched)
-    out.pre = (conv1n, Act(t1, "map", x.batched))
-    return out
+    return _chained(y, conv1n, t1, x.batched)
 
 
 def stem_conv_pool(x: Act, conv, bn, act, pool) -> Act:

@@ -1,4 +1,5 @@
-"""Host side of the layer-2 streamed boundaries (csrc/chain_l2.hip): fragment order and which C-ABI entries a forward calls.  No GPU."""
+"""Host side of the accumulator-layout boundary kernels (csrc/chain_rc.hip, csrc/chain_l2.hip): operand layouts and which C-ABI entries
+a forward calls.  No GPU."""
 import numpy as np
 import pytest
 
@@ -38,6 +39,58 @@ def test_l2_fragment_order(C, N2):
     w1n = rng.standard_normal((N2, K)).astype(np.float32)
     got = ops._res_fragments(w3, w1n).reshape(K // 32, C // 16 + N2 // 16, 64, 8)
     np.testing.assert_array_equal(got, _restated_fragments(w3, w1n))
+
+
+def _conv_bn(rng, cin, cout, bias):
+    """A pointwise Conv2d + inference BatchNorm with random parameters and statistics, and its fp32 (scaled rows, shift) restated."""
+    import eqxvision_amd as eqv
+    conv = eqv.nn.Conv2d(cin, cout, 1, use_bias=bias, key=eqv.random.PRNGKey(0))
+    conv.weight = (rng.standard_normal((cout, cin, 1, 1)) / np.sqrt(cin)).astype(np.float32)
+    if bias:
+        conv.bias = (0.3 * rng.standard_normal((cout, 1, 1))).astype(np.float32)
+    bn = eqv.nn.BatchNorm(cout, inference=True)
+    bn.weight = rng.uniform(0.5, 1.5, cout).astype(np.float32)
+    bn.weight[::7] *= -1.0
+    bn.bias = (0.2 * rng.standard_normal(cout)).astype(np.float32)
+    mean, var = (0.3 * rng.standard_normal(cout)).astype(np.float32), rng.uniform(0.3, 2.0, cout).astype(np.float32)
+    bn.state_index.value = (mean, var)
+    scale = bn.weight * (np.float32(1.0) / np.sqrt(var + np.float32(bn.eps)))
+    shift = bn.bias - mean * scale
+    if bias:
+        shift = shift + conv.bias.reshape(-1) * scale
+    return conv, bn, conv.weight.reshape(cout, cin) * scale[:, None], shift
+
+
+@pytest.mark.parametrize("bias", [False, True])
+def test_rc_operands_from_modules(monkeypatch, bias):
+    """The operands of mv_conv1x1_chain_rc_fwd (16 fragments per chunk, 18 shift rows) and mv_conv1x1_chain_rc0_fwd (12 and 10) as
+    ops.chain_acc_operands packs them from Conv2d / BatchNorm modules, against the header's layouts restated in tests/_cases.py
+    (the ones the GPU cases hand to the kernels); rc0 is rc without conv3_1's fragments and shift rows, as chain_rc_case takes it."""
+    import torch
+    from eqxvision_amd import ops
+    from tests._cases import _rc_fragments, _rc_shifts
+    monkeypatch.setattr(ops, "device", lambda: torch.device("cpu"))
+    monkeypatch.setattr(ops, "_dev", lambda a, dt: torch.from_numpy(np.ascontiguousarray(a)).to(dt))
+    rng = np.random.default_rng(5)
+    C, K, N2 = 64, 256, 64
+    c30, b30, w30, h30 = _conv_bn(rng, C, K, bias)
+    cd, bd, wd, hd = _conv_bn(rng, C, K, bias)
+    c31, b31, w31, h31 = _conv_bn(rng, C, K, bias)
+    c1n, b1n, w1n, h1n = _conv_bn(rng, K, N2, bias)
+    bits = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(torch.bfloat16).view(torch.int16).numpy()
+    ref_f = _rc_fragments(np.concatenate([w30, wd], axis=1), w31, w1n).reshape(K // 32, 16, 64 * 8)
+    ref_s = _rc_shifts(h30 + hd, h31, h1n)
+
+    wf, sh, _ = ops.chain_acc_operands(c31, [[(c30, b30), (cd, bd)], [(c31, b31)]], c1n, b1n)
+    assert wf.dtype == torch.bfloat16 and sh.dtype == torch.int32 and tuple(sh.shape) == (18, 64)
+    np.testing.assert_array_equal(wf.view(torch.int16).numpy().reshape(K // 32, 16, 64 * 8), bits(ref_f))
+    np.testing.assert_array_equal(sh.numpy().view(np.uint32), ref_s)
+
+    wf0, sh0, _ = ops.chain_acc_operands(c30, [[(c30, b30), (cd, bd)]], c1n, b1n)
+    assert tuple(sh0.shape) == (10, 64)
+    np.testing.assert_array_equal(wf0.view(torch.int16).numpy().reshape(K // 32, 12, 64 * 8),
+                                  bits(np.concatenate([ref_f[:, :8], ref_f[:, 12:]], axis=1)))
+    np.testing.assert_array_equal(sh0.numpy().view(np.uint32), np.concatenate([ref_s[:8], ref_s[16:]], axis=0))
 
 
 def _r50(monkeypatch, B, flags=()):
