@@ -84,6 +84,9 @@ PROTOTYPES = {
     "mv_ln_mlp_stream_res_fwd": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i, _i, _f, _i, _vp],
     "mv_cnblock_dw_supported": [_i, _i, _i, _i, _i, _i],
     "mv_cnblock_dw_fwd": [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _i, _i, _i, _vp],
+    "mv_shuffle_dwpw_supported": [_i] * 7,
+    "mv_shuffle_dwpw_fwd": [_vp] * 8 + [_i] * 4 + [_vp] + [_i] * 12 + [_vp],
+    "mv_channel_gather_nhwc_fwd": [_vp, _vp, _vp, _i64, _i, _i, _i, _vp],
     "mv_conv2d_nchw_split_fwd": [_vp, _vp, _vp, _vp, _vp, _vp] + [_i] * 11 + [_i, _i, _i, _vp],
     "mv_resize_bilinear_nhwc_fwd": [_vp, _vp] + [_i] * 6 + [_i, _i, _i, _vp],
     "mv_copy_rows": [_vp, _vp, _i64, _i64, _i64, _i64, _vp],

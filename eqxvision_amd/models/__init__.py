@@ -47,6 +47,13 @@ from .classification.resnet import (
     wide_resnet50_2,
     wide_resnet101_2,
 )
+from .classification.shufflenetv2 import (
+    ShuffleNetV2,
+    shufflenet_v2_x0_5,
+    shufflenet_v2_x1_0,
+    shufflenet_v2_x1_5,
+    shufflenet_v2_x2_0,
+)
 from .segmentation.deeplabv3 import ASPP, DeepLabHead, DeepLabV3, deeplabv3
 from .segmentation.fcn import FCN, FCNHead, fcn
 from .segmentation.lraspp import LRASPP, LRASPPHead, lraspp_mobilenet_v3_large

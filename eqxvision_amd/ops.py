@@ -1797,6 +1797,300 @@ def cnblock(x: Act, blk, drop=None) -> Act:
     return add(x, h)
 
 
+# ------------------------------------------------------------------ ShuffleNetV2 unit (models/classification/shufflenetv2.py)
+# The FOLDED layout of a unit output with branch width bf: one bf16 NHWC tensor [B, H, W, 2P], P = bf rounded up to SHUFFLE_GRANULE.
+# Channels [0, bf) hold the left half L (branch1's output / the pass-through), [P, P + bf) the right half R (branch2's output), every
+# other channel is an exact zero.  The reference's tensor after its channel shuffle is logical[2i] = L[i], logical[2i + 1] = R[i], so
+# logical channel j sits at physical channel j // 2 (even j) or P + j // 2 (odd j): the shuffle, the split and the concatenation
+# become permutations of the NEXT unit's weight columns and nothing is launched for them.  A layout is None (plain channels) or the
+# pair (bf, P).
+# The granule is 8: the kernel needs 16-byte channel chunks, and pads its own operands further on the inside (the k-step 32 and the
+# 16-row tile of v_mfma_f32_16x16x32_bf16: zeros in LDS and in the packed weight, never in HBM).
+SHUFFLE_GRANULE = 8
+
+
+def shuffle_layout(bf: int):
+    return (int(bf), (int(bf) + SHUFFLE_GRANULE - 1) // SHUFFLE_GRANULE * SHUFFLE_GRANULE)
+
+
+def shuffle_phys_index(C: int, layout) -> np.ndarray:
+    """The physical channel of every logical channel of a C-channel tensor kept in `layout`."""
+    j = np.arange(C)
+    if layout is None:
+        return j
+    bf, P = layout
+    if C != 2 * bf:
+        raise ValueError(f"a folded tensor of branch width {bf} has {2 * bf} logical channels, not {C}")
+    return np.where(j % 2 == 0, j // 2, P + j // 2)
+
+
+def _shuffle_parts(unit):
+    """((dw, bn, pw, bn) of branch1 or None, (pw1, bn, dw, bn, pw2, bn) of branch2) when the unit is the reference's pair of
+    Sequentials (shufflenetv2.py:44-112), else None."""
+    from . import nn
+
+    def conv_bn(L, i, dw):
+        c, b = L[i], L[i + 1]
+        ok = type(c) is nn.Conv2d and isinstance(b, nn.BatchNorm) and c.bias is None and tuple(c.dilation) == (1, 1)
+        if dw:
+            return ok and c.groups == c.in_channels == c.out_channels and tuple(c.kernel_size) == (3, 3) and tuple(c.padding) == (1, 1) \
+                and tuple(c.stride) == (unit.stride, unit.stride)
+        return ok and _pointwise(c)
+
+    def relu(L, i):
+        return isinstance(L[i], nn.Lambda) and nn.act_name(L[i].fn) == "relu"
+
+    L1, L2 = getattr(unit.branch1, "layers", None), getattr(unit.branch2, "layers", None)
+    if L1 is None or L2 is None or len(L2) != 8 or unit.stride not in (1, 2):
+        return None
+    if not (conv_bn(L2, 0, False) and relu(L2, 2) and conv_bn(L2, 3, True) and conv_bn(L2, 5, False) and relu(L2, 7)):
+        return None
+    b2 = (L2[0], L2[1], L2[3], L2[4], L2[5], L2[6])
+    if not (b2[0].out_channels == b2[2].in_channels == b2[4].in_channels == b2[4].out_channels):
+        return None
+    if unit.stride == 1:
+        return (None, b2)
+    if len(L1) != 5 or not (conv_bn(L1, 0, True) and conv_bn(L1, 2, False) and relu(L1, 4)) or L1[2].out_channels != b2[4].out_channels \
+            or L1[0].out_channels != L1[2].in_channels:
+        return None
+    return ((L1[0], L1[1], L1[2], L1[3]), b2)
+
+
+def _place(v: np.ndarray, pos: np.ndarray, size: int, axis: int = -1) -> np.ndarray:
+    """zeros of `size` along `axis` with v's entries at `pos`."""
+    v = np.moveaxis(np.asarray(v, np.float32), axis, -1)
+    out = np.zeros(v.shape[:-1] + (size,), np.float32)
+    out[..., pos] = v
+    return np.moveaxis(out, -1, axis)
+
+
+def _shuffle_tail_fold(dw, bn_d, pw, bn_p, pos: np.ndarray, Cx: int, P: int):
+    """depthwise 3x3 + BN -> 1x1 + BN (+ relu) over a physical input of Cx channels whose logical channel j sits at pos[j]:
+    (dw weight [3][3][Cx], dw scale, dw shift [Cx], 1x1 weight [P][Cx], scale, shift [P]); zeros at every pad."""
+    wd = np.asarray(dw.weight, np.float32)[:, 0].transpose(1, 2, 0)                      # (C,1,3,3) -> [3][3][C]
+    sd, hd = _fold(dw, bn_d)
+    wp = np.asarray(pw.weight, np.float32).reshape(pw.out_channels, pw.in_channels)
+    sp, hp = _fold(pw, bn_p)
+    rows = np.arange(pw.out_channels)
+    return (_place(wd, pos, Cx), _place(sd, pos, Cx), _place(hd, pos, Cx), _place(_place(wp, pos, Cx), rows, P, axis=0),
+            _place(sp, rows, P), _place(hp, rows, P))
+
+
+def shuffle_fold_unit(unit, layout_in, C_in: int):
+    """One ShuffleNetV2 unit as fp32 numpy operands on the folded layout (no device): what ops.shuffle_unit uploads and what
+    shuffle_unit_numpy applies.  `layout_in` / `C_in`: the layout and the LOGICAL channel count of the unit input.  None when the unit
+    is not the reference's structure (or a stride-1 unit on a plain input, which the reference's networks never have)."""
+    parts = _shuffle_parts(unit)
+    if parts is None or (unit.stride == 1 and layout_in is None):
+        return None
+    b1, b2 = parts
+    bf, P = shuffle_layout(b2[4].out_channels)
+    idx = shuffle_phys_index(C_in, layout_in)
+    Cp = C_in if layout_in is None else 2 * layout_in[1]
+    pw1 = b2[0]
+    if unit.stride == 1:
+        if layout_in != (bf, P) or pw1.in_channels != bf or C_in != 2 * bf:
+            return None
+        cols = idx[bf:]                                    # branch2 reads logical[bf:2bf]
+    else:
+        if pw1.in_channels != C_in or b1[0].in_channels != C_in:
+            return None
+        cols = idx
+    w1 = np.asarray(pw1.weight, np.float32).reshape(bf, -1)
+    s1, h1 = _fold(pw1, b2[1])
+    rows = np.arange(bf)
+    F = dict(stride=unit.stride, bf=bf, P=P, Cp=Cp, layout_in=layout_in,
+             pw1=(_place(_place(w1, cols, Cp), rows, P, axis=0), _place(s1, rows, P), _place(h1, rows, P)),
+             tail2=_shuffle_tail_fold(b2[2], b2[3], b2[4], b2[5], rows, P, P),
+             tail1=None if b1 is None else _shuffle_tail_fold(b1[0], b1[1], b1[2], b1[3], idx, Cp, P))
+    return F
+
+
+def shuffle_fold_head(conv, bn, layout_in):
+    """conv5 (1x1 + BN + relu) on a folded input: (weight [K][Cp] with permuted columns, scale, shift), fp32 numpy."""
+    C = conv.in_channels
+    idx = shuffle_phys_index(C, layout_in)
+    Cp = C if layout_in is None else 2 * layout_in[1]
+    s, h = _fold(conv, bn)
+    return _place(np.asarray(conv.weight, np.float32).reshape(conv.out_channels, C), idx, Cp), s, h
+
+
+def _np_dw3x3(x: np.ndarray, w: np.ndarray, stride: int) -> np.ndarray:
+    """[H][W][C] depthwise 3x3, pad 1, fp32 numpy."""
+    H, W, C = x.shape
+    Ho, Wo = (H - 1) // stride + 1, (W - 1) // stride + 1
+    xp = np.zeros((H + 2, W + 2, C), np.float32)
+    xp[1:-1, 1:-1] = x
+    y = np.zeros((Ho, Wo, C), np.float32)
+    for r in range(3):
+        for s in range(3):
+            y += xp[r:r + stride * (Ho - 1) + 1:stride, s:s + stride * (Wo - 1) + 1:stride] * w[r, s]
+    return y
+
+
+def shuffle_unit_numpy(x: np.ndarray, F) -> np.ndarray:
+    """A whole folded unit in fp32 numpy: physical [H][W][Cp] in, physical [Ho][Wo][2P] out -- the algebra of the device path
+    (first 1x1 with permuted columns; depthwise + 1x1 tails; the pass-through as an index), launch for launch."""
+    x = np.asarray(x, np.float32)
+    P, bf, s = F["P"], F["bf"], F["stride"]
+
+    def tail(t, T):
+        d = _np_dw3x3(t, T[0], s) * T[1] + T[2]
+        return np.maximum(d @ T[3].T * T[4] + T[5], 0.0).astype(np.float32)
+
+    w1, s1, h1 = F["pw1"]
+    t1 = np.maximum(x @ w1.T * s1 + h1, 0.0).astype(np.float32)
+    y = np.zeros(((x.shape[0] - 1) // s + 1, (x.shape[1] - 1) // s + 1, 2 * P), np.float32)
+    y[..., P:] = tail(t1, F["tail2"])
+    if s == 1:
+        y[..., :bf] = x[..., shuffle_phys_index(2 * bf, F["layout_in"])[:bf]]
+    else:
+        y[..., :P] = tail(x, F["tail1"])
+    return y
+
+
+def dwpw_fragments(w: np.ndarray) -> np.ndarray:
+    """A [N][Cx] 1x1 weight in the A-fragment order of mv_shuffle_dwpw_fwd (header): [Np / 16][Kp / 32][lane 64][8], lane
+    16 g + r = W[16 tile + r][32 step + 8 g ..], zero rows / columns up to Np = N rounded up to 16 and Kp = Cx rounded up to 32.
+    (The packer of the boundary chains, _res_fragments, lays out 32-row tiles of TWO matrices per chunk for v_mfma_f32_32x32x16:
+    16-row tiles keep the padding of the half-widths 24 .. 488 at 16 instead of 32.)"""
+    N, K = w.shape
+    Np, Kp = (N + 15) // 16 * 16, (K + 31) // 32 * 32
+    wp = np.zeros((Np, Kp), np.float32)
+    wp[:N, :K] = w
+    return np.ascontiguousarray(wp.reshape(Np // 16, 16, Kp // 32, 4, 8).transpose(0, 2, 3, 1, 4))
+
+
+def channel_gather(x: Act, idx: torch.Tensor) -> Act:
+    """y[..., j] = x[..., idx[j]] over the channel (last) axis; idx: device int32.  bf16 / fp32, any channel count."""
+    x = as_map(x) if x.kind in ("img", "map") else x
+    C, Co = x.t.shape[-1], idx.numel()
+    y = empty(tuple(x.t.shape[:-1]) + (Co,), x.t.dtype)
+    _lib.call("mv_channel_gather_nhwc_fwd", _ptr(x.t), _ptr(idx), _ptr(y), x.t.numel() // C, C, Co, x.dt, stream_ptr())
+    return Act(y, x.kind, x.batched)
+
+
+def _gather_index(mod, name, idx: np.ndarray) -> torch.Tensor:
+    cache = mod._cache()
+    hit = cache.get(("gather", name))
+    if hit is None:
+        hit = _dev(np.asarray(idx, np.int32), torch.int32)
+        cache[("gather", name)] = hit
+    return hit
+
+
+def _channel_slice(x: Act, c0: int, c1: int) -> Act:
+    B, H, W, C = x.t.shape
+    y = empty((B, H, W, c1 - c0), x.t.dtype)
+    es = y.element_size()
+    _lib.call("mv_copy_rows", x.t.data_ptr() + c0 * es, _ptr(y), B * H * W, (c1 - c0) * es, C * es, (c1 - c0) * es, stream_ptr())
+    return Act(y, "map", x.batched)
+
+
+def shuffle_unit_literal(x: Act, unit) -> Act:
+    """The reference's unit on the logical layout (shufflenetv2.py:104-112): split, branches, concatenate, channel shuffle."""
+    x = as_map(x)
+    C = x.t.shape[-1]
+    if unit.stride == 1:
+        out = concat_channels([_channel_slice(x, 0, C // 2), unit.branch2(_channel_slice(x, C // 2, C))])
+    else:
+        out = concat_channels([unit.branch1(x), unit.branch2(x)])
+    Co = out.t.shape[-1]
+    j = np.arange(Co)
+    return channel_gather(out, _gather_index(unit, "shuffle", (j % 2) * (Co // 2) + j // 2))     # _channel_shuffle(out, 2)
+
+
+def _shuffle_operands(unit, layout_in, C_in: int):
+    """shuffle_fold_unit's operands on the device (cached on the unit, keyed by its BatchNorms' statistics), or None."""
+    parts = _shuffle_parts(unit)
+    if parts is None:
+        return None
+    bns = tuple(_bn_id(m) for br in parts if br is not None for m in br[1::2])
+    key = ("shuffle_fold", layout_in, C_in, bns)
+    cache = unit._cache()
+    if key in cache:
+        return cache[key]
+    F = shuffle_fold_unit(unit, layout_in, C_in)
+    if F is not None:
+        def tail(T):
+            return (_dev(T[0], torch.bfloat16), _dev(T[1], torch.float32), _dev(T[2], torch.float32),
+                    _dev(dwpw_fragments(T[3]), torch.bfloat16), _dev(T[4], torch.float32), _dev(T[5], torch.float32))
+        w1, s1, h1 = F["pw1"]
+        F = dict(F, pw1=(_dev(w1, torch.bfloat16), _dev(s1, torch.float32), _dev(h1, torch.float32)), tail2=tail(F["tail2"]),
+                 tail1=None if F["tail1"] is None else tail(F["tail1"]))
+    cache[key] = F
+    return F
+
+
+def _conv1x1_folded(x: Act, w: torch.Tensor, scale: torch.Tensor, shift: torch.Tensor, K: int) -> Act:
+    """relu(scale * (w . x) + shift) with a prepared [K][C] weight: the ordinary NHWC convolution entry."""
+    B, H, W, C = x.t.shape
+    y = empty((B, H, W, K), torch.bfloat16)
+    _splitk_scratch(B * H * W, K, C)
+    _lib.call("mv_conv2d_nhwc_fwd", _ptr(x.t), _ptr(w), _ptr(scale), _ptr(shift), None, _ptr(y), B, H, W, C, K, 1, 1, 1, 1, 0, 0, 1, 1, 1,
+              _lib.ACT_RELU, _lib.BF16, _lib.BF16, stream_ptr())
+    return Act(y, "map", x.batched)
+
+
+def shuffle_unfold(x: Act, layout, mod) -> Act:
+    """Folded -> logical channels (one gather); a plain tensor passes through."""
+    if layout is None:
+        return x
+    return channel_gather(x, _gather_index(mod, ("unfold", layout), shuffle_phys_index(2 * layout[0], layout)))
+
+
+def shuffle_unit(x: Act, unit, layout_in):
+    """One ShuffleNetV2 unit -> (output, its layout).  bf16 inference where mv_shuffle_dwpw_fwd has the shapes: the folded layout,
+    2 launches at stride 1 (first 1x1; depthwise + 1x1 + pass-through), 3 at stride 2 (branch1's depthwise + 1x1; first 1x1;
+    branch2's depthwise + 1x1).  Otherwise (fp32 mode, training-mode BatchNorm, the switches "no_shuffle_dwpw" / "force_generic",
+    shapes without a kernel): the literal composition on logical channels."""
+    x = as_map(x)
+    B, H, W, Cphys = x.t.shape
+    C_in = Cphys if layout_in is None else 2 * layout_in[0]
+    parts = _shuffle_parts(unit)
+    F = None
+    if compute_dtype() == "bf16" and x.t.dtype == torch.bfloat16 and parts is not None and \
+            not any(_bn_training(m) for br in parts if br is not None for m in br[1::2]):
+        s = unit.stride
+        bf, P = shuffle_layout(parts[1][4].out_channels)
+        lib = _lib.load()
+        if lib.mv_shuffle_dwpw_supported(P, P, s, H, W, _lib.BF16, _lib.BF16) and \
+                (s == 1 or lib.mv_shuffle_dwpw_supported(Cphys, P, s, H, W, _lib.BF16, _lib.BF16)):
+            F = _shuffle_operands(unit, layout_in, C_in)
+    if F is None:
+        return shuffle_unit_literal(shuffle_unfold(x, layout_in, unit), unit), None
+    s, bf, P = F["stride"], F["bf"], F["P"]
+    Ho, Wo = (H - 1) // s + 1, (W - 1) // s + 1
+    y = empty((B, Ho, Wo, 2 * P), torch.bfloat16)
+    st = stream_ptr()
+    if s == 2:
+        T = F["tail1"]
+        _lib.call("mv_shuffle_dwpw_fwd", _ptr(x.t), *[_ptr(t) for t in T], _ptr(y), 2 * P, 0, P, bf, None, 0, 0, 0, 0, 0,
+                  B, H, W, Cphys, s, _lib.BF16, _lib.BF16, st)
+    t1 = _conv1x1_folded(x, *F["pw1"], P)
+    T = F["tail2"]
+    src = (_ptr(x.t), Cphys, layout_in[1], bf, 0, P) if s == 1 else (None, 0, 0, 0, 0, 0)
+    _lib.call("mv_shuffle_dwpw_fwd", _ptr(t1.t), *[_ptr(t) for t in T], _ptr(y), 2 * P, P, P, bf, *src, B, H, W, P, s, _lib.BF16,
+              _lib.BF16, st)
+    return Act(y, "map", x.batched), (bf, P)
+
+
+def shuffle_head(x: Act, conv, bn, layout_in) -> Act:
+    """conv5 + BatchNorm + relu (shufflenetv2.py:196-210) on a folded input: its weight columns permuted, the ordinary 1x1 path."""
+    if layout_in is None:
+        return conv2d(x, conv, bn, "relu")
+    if compute_dtype() != "bf16" or _bn_training(bn) or not _pointwise(conv) or conv.out_channels % 8:
+        return conv2d(shuffle_unfold(x, layout_in, conv), conv, bn, "relu")
+    cache = conv._cache()
+    key = ("shuffle_head", layout_in, _bn_id(bn))
+    hit = cache.get(key)
+    if hit is None:
+        w, s, h = shuffle_fold_head(conv, bn, layout_in)
+        hit = (_dev(w, torch.bfloat16), _dev(s, torch.float32), _dev(h, torch.float32))
+        cache[key] = hit
+    return _conv1x1_folded(as_map(x), *hit, conv.out_channels)
+
+
 # ------------------------------------------------------------------ element-wise (unfused call sites)
 def _canon(x: Act) -> Act:
     return as_map(x) if x.kind == "img" else (x if x.kind == "map" else as_rows(x))

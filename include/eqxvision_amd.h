@@ -358,6 +358,32 @@ int mv_cnblock_dw_supported(int C, int H, int W, int x_dtype, int y_dtype, int n
 int mv_cnblock_dw_fwd(const void* x, const void* w_rsc, const float* bias, void* y, int N, int H, int W, int C, float eps,
                       int normalize, int x_dtype, int y_dtype, mv_stream_t stream);
 
+/* ShuffleNetV2 unit tail (shufflenetv2.py:44-112: depthwise 3x3 + BatchNorm -> 1x1 + BatchNorm + ReLU) in one launch, writing one
+ * half of a unit output kept in the FOLDED layout [B][Ho][Wo][y_pitch] (eqxvision_amd/ops.py: shuffle_unit), and optionally the
+ * pass-through half of a stride-1 unit:
+ *   d[m, c]            = bf16( dw_scale[c] * sum_{r,s<3} x[b, stride*ho + r - 1, stride*wo + s - 1, c] * w_dw[r][s][c] + dw_shift[c] )
+ *   y[m, y_off + n]    = relu( pw_scale[n] * sum_c W[n][c] d[m, c] + pw_shift[n] )   for n < N_real,  exact 0 for N_real <= n < N
+ *   y[m, pass_off + i] = src[m, phys(i)]   for i < n_pass,  exact 0 for n_pass <= i < pass_pad   (src != NULL, stride 1; a bit copy)
+ *   phys(i) = i / 2 for even i, P_src + i / 2 for odd i   (the previous unit's channel shuffle as an index into its folded output)
+ * m = b*Ho*Wo + ho*Wo + wo, Ho = (H - 1) / stride + 1 (pad 1).  x NHWC [B][H][W][Cx] bf16, dense; w_dw [3][3][Cx] bf16 (as for
+ * mv_dwconv2d_nhwc_fwd); dw_scale / dw_shift fp32 [Cx] or NULL; pw_scale / pw_shift fp32 [N] or NULL; src [B][Ho][Wo][src_pitch]
+ * bf16.  Every other channel of y is left untouched.  The intermediate d stays in LDS; fp32 accumulation in both stages.
+ * w_frag: the [N][Cx] 1x1 weight in the A-fragment order of v_mfma_f32_16x16x32_bf16, zero-padded to Np = N rounded up to 16 rows
+ * and Kp = Cx rounded up to 32 columns (eqxvision_amd/ops.py: dwpw_fragments):
+ *   w_frag[tile 0..Np/16-1][step 0..Kp/32-1][lane 0..63][e 0..7] = W[16*tile + lane%16][32*step + 8*(lane/16) + e]
+ * Cx, N: multiples of 8 in 8 .. 512; y_pitch, y_off, pass_off, pass_pad, P_src, src_pitch: multiples of 8; stride 1 or 2; bf16 only.
+ * Flag "no_shuffle_dwpw": _supported returns 0 (the caller composes mv_dwconv2d_nhwc_fwd + mv_conv2d_nhwc_fwd). */
+int mv_shuffle_dwpw_supported(int Cx, int N, int stride, int H, int W, int in_dtype, int out_dtype);
+int mv_shuffle_dwpw_fwd(const void* x, const void* w_dw, const float* dw_scale, const float* dw_shift, const void* w_frag,
+                        const float* pw_scale, const float* pw_shift, void* y, int y_pitch, int y_off, int N, int N_real,
+                        const void* src, int src_pitch, int P_src, int n_pass, int pass_off, int pass_pad, int B, int H, int W, int Cx,
+                        int stride, int in_dtype, int out_dtype, mv_stream_t stream);
+
+/* y[r, j] = x[r, idx[j]] over the channel axis of rows x C_in -> rows x C_out (the literal channel shuffle / split of ShuffleNetV2,
+ * shufflenetv2.py:16-23, where the folded layout is not used).  idx: C_out device int32 (an index outside 0 .. C_in-1 gives 0);
+ * MV_F32 or MV_BF16, any channel counts, not in place.  A bit copy. */
+int mv_channel_gather_nhwc_fwd(const void* x, const int* idx, void* y, int64_t rows, int C_in, int C_out, int dtype, mv_stream_t stream);
+
 /* eqx.nn.Linear over FEW rows with a big weight matrix -- the AlexNet / VGG classifiers (alexnet.py:62-70: Linear(9216, 4096),
  * Linear(4096, 4096), Linear(4096, classes), each behind `jax.vmap` = M rows) -- y[M][N] = act(x[M][K] . w^T + bias).  The layer is
  * bound by streaming w: w_frag is w in MFMA fragment order, prepared once by the caller (eqxvision_amd/ops.py:fc_fragments),
