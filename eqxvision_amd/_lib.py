@@ -87,6 +87,9 @@ PROTOTYPES = {
     "mv_shuffle_dwpw_supported": [_i] * 7,
     "mv_shuffle_dwpw_fwd": [_vp] * 8 + [_i] * 4 + [_vp] + [_i] * 12 + [_vp],
     "mv_channel_gather_nhwc_fwd": [_vp, _vp, _vp, _i64, _i, _i, _i, _vp],
+    "mv_fire_expand_supported": [_i] * 7,
+    "mv_fire_expand_fwd": [_vp] * 6 + [_i] * 8 + [_vp],
+    "mv_maxpool2d_out_nhwc_fwd": [_vp, _vp] + [_i] * 12 + [_i, _vp],
     "mv_conv2d_nchw_split_fwd": [_vp, _vp, _vp, _vp, _vp, _vp] + [_i] * 11 + [_i, _i, _i, _vp],
     "mv_resize_bilinear_nhwc_fwd": [_vp, _vp] + [_i] * 6 + [_i, _i, _i, _vp],
     "mv_copy_rows": [_vp, _vp, _i64, _i64, _i64, _i64, _vp],

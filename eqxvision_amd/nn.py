@@ -268,13 +268,27 @@ class MaxPool2d(Module):
     stride: Tuple[int, int]
     padding: Tuple[int, int]
 
-    def __init__(self, kernel_size, stride=1, padding=0, **kwargs):
+    use_ceil = False        # not a pytree field: a floor-mode module is attribute for attribute what it was without the argument
+
+    def __init__(self, kernel_size, stride=1, padding=0, use_ceil=False, **kwargs):
         self.kernel_size = _pair(kernel_size)
         self.stride = _pair(stride)
         self.padding = _pair(padding)
+        if use_ceil:
+            self.use_ceil = True
+
+    def output_size(self, H: int, W: int) -> Tuple[int, int]:
+        """equinox's rule: per axis, (size + 2 pad - kernel) % stride != 0 grows the right / bottom padding by `stride` (use_ceil)."""
+        out = []
+        for size, k, s, p in zip((H, W), self.kernel_size, self.stride, self.padding):
+            span = size + 2 * p - k
+            out.append(span // s + 1 + (1 if self.use_ceil and span % s else 0))
+        return tuple(out)
 
     @boundary
     def __call__(self, x, *, key=None):
+        if self.use_ceil:
+            return ops.maxpool2d_ceil(x, self)
         return ops.maxpool2d(x, self.kernel_size, self.stride, self.padding)
 
 
@@ -332,7 +346,7 @@ class Sequential(Module):
                 if j < len(L) and isinstance(L[j], Lambda) and act_name(L[j].fn):
                     a = act_name(L[j].fn)
                     j += 1
-                if x.kind == "img" and a == "relu" and j < len(L) and type(L[j]) is MaxPool2d:
+                if x.kind == "img" and a == "relu" and j < len(L) and type(L[j]) is MaxPool2d and not L[j].use_ceil:
                     # network entry from the raw image followed by a max-pool (alexnet.py:44-46): one launch where the
                     # library has the fused kernel for this configuration (ops.stem_conv_pool falls back to the pair)
                     x = ops.stem_conv_pool(x, layer, bn, a, L[j])

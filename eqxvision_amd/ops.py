@@ -1296,6 +1296,20 @@ def maxpool2d(x: Act, kernel_size, stride, padding) -> Act:
     return Act(y, "map", x.batched)
 
 
+def maxpool2d_ceil(x: Act, pool) -> Act:
+    """nn.MaxPool2d(use_ceil=True) (squeezenet.py:88-112): the output size is the module's (equinox's rule), the taps of the last
+    window that fall outside the map do not take part (mv_maxpool2d_out_nhwc_fwd)."""
+    x = as_map(x)
+    B, H, W, C = x.t.shape
+    kh, kw = _pair(pool.kernel_size)
+    sh, sw = _pair(pool.stride)
+    ph, pw = _pair(pool.padding)
+    Ho, Wo = pool.output_size(H, W)
+    y = empty((B, Ho, Wo, C), x.t.dtype)
+    _lib.call("mv_maxpool2d_out_nhwc_fwd", _ptr(x.t), _ptr(y), B, H, W, C, kh, kw, sh, sw, ph, pw, Ho, Wo, x.dt, stream_ptr())
+    return Act(y, "map", x.batched)
+
+
 def adaptive_avgpool2d(x: Act, target, out_fp32: bool = False) -> Act:
     x = as_map(x)
     B, H, W, C = x.t.shape
@@ -2089,6 +2103,82 @@ def shuffle_head(x: Act, conv, bn, layout_in) -> Act:
         hit = (_dev(w, torch.bfloat16), _dev(s, torch.float32), _dev(h, torch.float32))
         cache[key] = hit
     return _conv1x1_folded(as_map(x), *hit, conv.out_channels)
+
+
+# ------------------------------------------------------------------ SqueezeNet Fire module (fire_expand.hip)
+FIRE_S64_LITERAL_PIXELS = 256 * 512      # the pixel count from which mv_fire_expand_fwd uses its 256-pixel tile
+FIRE_TILE_ROW =16 * ((np.arange(32) >> 2) & 1) + 4 * (np.arange(32) >> 3) + (np.arange(32) & 3)     # header: chan(p)
+
+
+def fire_fragments(w: np.ndarray) -> np.ndarray:
+    """An [E][S][kh][kw] expand weight (1x1 or 3x3) in the A-fragment order of mv_fire_expand_fwd (header): with Wk[n][k],
+    k = (3 r + s) * S + c, the array [E / 32][K / 16][lane 64][8] holds Wk[32 tile + chan(lane % 32)][16 step + 8 (lane / 32) + e],
+    chan = FIRE_TILE_ROW: row p of a tile is accumulator register (p % 4) + 4 (p / 8) of lane half (p / 4) % 2, so a lane's 16
+    registers are 16 consecutive output channels.  E % 32 == 0 and S % 16 == 0: nothing is padded."""
+    E, S, kh, kw = w.shape
+    K = kh * kw * S
+    if E % 32 or S % 16:
+        raise ValueError(f"fire_fragments: E={E} (multiple of 32), S={S} (multiple of 16)")
+    wk = np.asarray(w, np.float32).transpose(0, 2, 3, 1).reshape(E // 32, 32, K // 16, 2, 8)[:, FIRE_TILE_ROW]
+    return np.ascontiguousarray(wk.transpose(0, 2, 3, 1, 4).reshape(E // 32, K // 16, 64, 8))
+
+
+def _fire_conv(x: Act, conv, lam) -> Act:
+    from .nn import act_name
+    a = act_name(lam.fn)
+    return conv2d(x, conv, None, a) if a is not None else lam(conv2d(x, conv))
+
+
+def fire_literal(x: Act, fire) -> Act:
+    """The reference's Fire (squeezenet.py:45-53): three convolutions with their activations and the concatenation."""
+    t = _fire_conv(as_map(x), fire.squeeze, fire.squeeze_activation)
+    return concat_channels([_fire_conv(t, fire.expand1x1, fire.expand1x1_activation),
+                            _fire_conv(t, fire.expand3x3, fire.expand3x3_activation)])
+
+
+def _fire_plain(fire) -> bool:
+    """The module the fused kernel computes: 1x1 and 3x3 (pad 1) dense stride-1 convolutions on one input, ReLU after each."""
+    from .nn import Conv2d, Lambda, act_name
+    e1, e3 = fire.expand1x1, fire.expand3x3
+    if not (type(fire.squeeze) is Conv2d and type(e1) is Conv2d and type(e3) is Conv2d):
+        return False
+    if not all(isinstance(a, Lambda) and act_name(a.fn) == "relu"
+               for a in (fire.squeeze_activation, fire.expand1x1_activation, fire.expand3x3_activation)):
+        return False
+    one = (1, 1)
+    return (e1.kernel_size == one and e1.padding == (0, 0) and e3.kernel_size == (3, 3) and e3.padding == one
+            and all(c.stride == one and c.dilation == one and c.groups == 1 for c in (e1, e3))
+            and e1.in_channels == e3.in_channels == fire.squeeze.out_channels)
+
+
+def fire(x: Act, mod) -> Act:
+    """One Fire module.  bf16 inference where mv_fire_expand_fwd has the shape: the squeeze as the ordinary fused convolution, then
+    both expand convolutions, their ReLUs and the concatenation in one launch (2 launches).  Otherwise (fp32 mode, the switches
+    "no_fire_expand" / "force_generic", other shapes or activations): the literal composition."""
+    x = as_map(x)
+    B, H, W, _ = x.t.shape
+    if not (compute_dtype() == "bf16" and x.t.dtype == torch.bfloat16 and _fire_plain(mod)):
+        return fire_literal(x, mod)
+    S, E1, E3 = mod.squeeze.out_channels, mod.expand1x1.out_channels, mod.expand3x3.out_channels
+    if not _lib.load().mv_fire_expand_supported(S, E1, E3, H, W, _lib.BF16, _lib.BF16):
+        return fire_literal(x, mod)
+    if S == 64 and B * H * W >= FIRE_S64_LITERAL_PIXELS and not _lib.get_flag("fire_expand_always"):
+        # measured (DESIGN.md 3.6): 64 -> 256 + 256 on 27 x 27 maps at 256 images is the one Fire of both networks where the
+        # composition beats the fused launch (by 5 - 8 %); it stays on the composition
+        return fire_literal(x, mod)
+    cache = mod._cache()
+    ops_ = cache.get("fire_expand")
+    if ops_ is None:
+        def bias(conv):
+            return None if conv.bias is None else _dev(np.asarray(conv.bias, np.float32).reshape(-1), torch.float32)
+        ops_ = (_dev(fire_fragments(np.asarray(mod.expand1x1.weight, np.float32)), torch.bfloat16), bias(mod.expand1x1),
+                _dev(fire_fragments(np.asarray(mod.expand3x3.weight, np.float32)), torch.bfloat16), bias(mod.expand3x3))
+        cache["fire_expand"] = ops_
+    t = conv2d(x, mod.squeeze, None, "relu")
+    y = empty((B, H, W, E1 + E3), torch.bfloat16)
+    _lib.call("mv_fire_expand_fwd", _ptr(t.t), _ptr(ops_[0]), _ptr(ops_[1]), _ptr(ops_[2]), _ptr(ops_[3]), _ptr(y), B, H, W, S, E1, E3,
+              _lib.BF16, _lib.BF16, stream_ptr())
+    return Act(y, "map", x.batched)
 
 
 # ------------------------------------------------------------------ element-wise (unfused call sites)

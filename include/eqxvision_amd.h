@@ -379,6 +379,25 @@ int mv_shuffle_dwpw_fwd(const void* x, const void* w_dw, const float* dw_scale, 
                         const void* src, int src_pitch, int P_src, int n_pass, int pass_off, int pass_pad, int B, int H, int W, int Cx,
                         int stride, int in_dtype, int out_dtype, mv_stream_t stream);
 
+/* SqueezeNet Fire module, expand half (squeezenet.py:45-53): both expand convolutions, their ReLUs and the concatenation in one
+ * launch; each half lands in its channel slice of the one output tensor:
+ *   y[m, n]      = relu( b1[n] + sum_{c<S}        W1[n][c]       t[m, c] )                         for n < E1
+ *   y[m, E1 + n] = relu( b3[n] + sum_{r,s<3, c<S} W3[n][c][r][s] t[b, h + r - 1, w + s - 1, c] )   for n < E3   (zero padding)
+ * m = b*H*W + h*W + w.  t NHWC [B][H][W][S] bf16 (the squeeze output), y NHWC [B][H][W][E1 + E3] bf16, dense, not in place; b1 / b3
+ * fp32 [E1] / [E3] or NULL; fp32 accumulation.  The tile of t and its one-pixel halo are staged in LDS once per workgroup (the padding
+ * is zeros written to LDS) and every output-channel tile is computed from that copy.
+ * w1_frag / w3_frag: the weights in the A-fragment order of v_mfma_f32_32x32x16_bf16 (eqxvision_amd/ops.py: fire_fragments), with
+ * the reduction index k = (3 r + s) * S + c (k = c for the 1x1) and the rows of a 32-channel tile permuted so that a lane's 16
+ * accumulator registers are 16 consecutive output channels:
+ *   w_frag[tile 0..E/32-1][step 0..K/16-1][lane 0..63][e 0..7] = Wk[32*tile + chan(lane%32)][16*step + 8*(lane/32) + e]
+ *   chan(p) = 16*((p/4)%2) + 4*(p/8) + p%4
+ * S in {16, 32, 48, 64}; E1 == E3 in {64, 128, 192, 256}; any H, W >= 1 (up to 4096) whose tile and halo rows fit LDS
+ * ((131 + 2 W) * (2 S + 16) <= 160 KiB); bf16 only.  Flags "no_fire_expand" / "force_generic": _supported returns 0 (the caller
+ * composes mv_conv2d_nhwc_fwd twice + mv_copy_rows); "fire_expand_m256": the 256-pixel tile whatever the pixel count. */
+int mv_fire_expand_supported(int S, int E1, int E3, int H, int W, int x_dtype, int y_dtype);
+int mv_fire_expand_fwd(const void* t, const void* w1_frag, const float* b1, const void* w3_frag, const float* b3, void* y, int B,
+                       int H, int W, int S, int E1, int E3, int x_dtype, int y_dtype, mv_stream_t stream);
+
 /* y[r, j] = x[r, idx[j]] over the channel axis of rows x C_in -> rows x C_out (the literal channel shuffle / split of ShuffleNetV2,
  * shufflenetv2.py:16-23, where the folded layout is not used).  idx: C_out device int32 (an index outside 0 .. C_in-1 gives 0);
  * MV_F32 or MV_BF16, any channel counts, not in place.  A bit copy. */
@@ -429,6 +448,13 @@ int mv_copy_rows(const void* src, void* dst, int64_t rows, int64_t row_bytes, in
 /* eqx.nn.MaxPool2d (resnet.py:254, alexnet.py:46,49,56): -inf padding, floor output size. */
 int mv_maxpool2d_nhwc_fwd(const void* x, void* y, int N, int H, int W, int C,
                           int kh, int kw, int sh, int sw, int ph, int pw, int dtype, mv_stream_t stream);
+
+/* eqx.nn.MaxPool2d(use_ceil=True) (squeezenet.py:88-112): the same pooling with the output size Ho x Wo given by the caller.  Per
+ * axis it must be the floor size or the ceil size (floor + 1 where (size + 2 pad - kernel) % stride != 0: equinox grows the right /
+ * bottom padding by `stride`), and the last window must still hold a tap of the map: MV_E_INVALID otherwise.  Taps outside the map
+ * are skipped.  MV_F32 or MV_BF16. */
+int mv_maxpool2d_out_nhwc_fwd(const void* x, void* y, int N, int H, int W, int C, int kh, int kw, int sh, int sw, int ph, int pw,
+                              int Ho, int Wo, int dtype, mv_stream_t stream);
 
 /* eqx.nn.AdaptiveAvgPool2d (resnet.py:283, alexnet.py:59, swin.py:757), equinox chunking rule. */
 int mv_adaptive_avgpool2d_nhwc_fwd(const void* x, void* y, int N, int H, int W, int C, int oh, int ow,
