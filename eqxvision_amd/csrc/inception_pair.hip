@@ -1,0 +1,217 @@
+// GoogLeNet Inception module, the two 3x3 convolutions of branches 2 and 3 (reference googlenet.py:206-220, 229-237) in ONE launch:
+// 3x3, padding 1, stride 1, folded BatchNorm + ReLU each; each reads its channel slice of the reduce map t and writes its channel slice
+// of the module's output y, so nothing is concatenated afterwards.  NHWC bf16, fp32 accumulation on the matrix cores, gfx950.
+//
+//   y[m, cy_i + n] = relu( scale_i[n] * sum_{r,s<3, c<S_i} W_i[n][c][r][s] t[b, h + r - 1, w + s - 1, ct_i + c] + shift_i[n] )   n < N_i
+//
+// for i = 0, 1; rows of t are ldt apart, rows of y ldy.  m is the FLATTENED pixel index b * H * W + h * W + w.  A 256-thread workgroup
+// owns 128 consecutive pixels whatever image they belong to and ONE pair of 32-channel output tiles of ONE of the two convolutions
+// (blockIdx.y): 7 x 7 and 14 x 14 maps at batch size are few pixel tiles, the output channels fill the machine.  It stages, once,
+// the flat pixel range m0 - W - 1 .. m0 + 128 + W of its convolution's slice of t in LDS: the tile and its one-pixel halo are all
+// inside it (neighbour (dh, dw) of pixel m is flat pixel m + dh W + dw).  Range entries outside 0 .. M-1 are written as zeros, and
+// one more all-zero slot follows the range: a tap that falls outside its IMAGE's map (or belongs to a pixel past M) reads that slot,
+// so the padding is zeros in LDS and is never read from memory.  A slot is S_i bf16 + 16 bytes of padding.
+//
+// The product runs on v_mfma_f32_32x32x16_bf16 with the weights as the A operand (rows = output channels) and the pixels as the B
+// operand; the k-step is 16 channels of ONE tap (S_i is a multiple of 16).  A wave owns 32 pixels and both tiles of the pair.  The
+// weights are streamed from L2 in fragment order (packed once on the host, ops.inception_fragments: output rows padded with zeros to
+// a multiple of 32, the rows of a tile permuted so that a lane ends up with 16 CONSECUTIVE output channels of its pixel in the
+// accumulator): scale, shift, ReLU and two 16-byte stores.  N_i is a multiple of 16: the upper half of the last tile may not exist
+// (it is computed on the zero rows and not stored), and an odd tile count leaves the last workgroup column a single tile.
+#include "mfma_common.h"
+
+namespace mv {
+
+namespace {
+
+constexpr int IP_THREADS = 256;
+constexpr int IP_TM = 128;
+constexpr int IP_LDS_MAX = 160 * 1024;
+
+struct PairP {
+    const bf16_t* t;
+    bf16_t* y;
+    long long ldt, ldy, M;
+    const uint4* wf0; const float* scale0; const float* shift0;      // [ceil(N0 / 32)][9 S0 / 16][64] fragments
+    const uint4* wf1; const float* scale1; const float* shift1;
+    int H, W;
+    int ct0, S0, cy0, N0;
+    int ct1, S1, cy1, N1;
+    int jobs0;             // blockIdx.y < jobs0: convolution 0, tile pair blockIdx.y; else convolution 1, pair blockIdx.y - jobs0
+    int n_slots;           // 128 + 2 W + 2 staged pixels; slot n_slots is the zero pixel
+};
+
+// NJ 32-channel tiles x 32 pixels over the nine taps
+template <int NJ>
+__device__ __forceinline__ void pair_taps(const uint4* __restrict__ wf, const char* lds, const int (&off)[9], f32x16 (&acc)[2], const int KC,
+                                          const int lane) {
+    // the k-steps of a tile are consecutive in the packed array whatever the tap: the fragments of step ks + 2 are requested while
+    // step ks runs (the index is clamped to the last step, so nothing past the tile is read)
+    const int KS = 9 * KC;
+    const uint4* wl = wf + lane;
+    const uint4* wh = wl + (NJ == 2 ? KS * 64 : 0);
+    uint4 n0a = wl[0], n0b = wh[0], n1a = wl[64], n1b = wh[64];
+    int ks = 0;
+#pragma unroll
+    for (int tap = 0; tap < 9; ++tap) {
+        const char* bp = lds + off[tap];
+        for (int kc = 0; kc < KC; ++kc, ++ks) {
+            const bf16x8 a0 = __builtin_bit_cast(bf16x8, n0a), a1 = __builtin_bit_cast(bf16x8, n0b);
+            n0a = n1a;
+            n0b = n1b;
+            const int nx = (ks + 2 < KS ? ks + 2 : KS - 1) * 64;
+            n1a = wl[nx];
+            if (NJ == 2) n1b = wh[nx];
+            const bf16x8 b = __builtin_bit_cast(bf16x8, *(const uint4*)(bp + kc * 32));
+            acc[0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a0, b, acc[0], 0, 0, 0);
+            if (NJ == 2) acc[1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1, b, acc[1], 0, 0, 0);
+        }
+    }
+}
+
+// scale, shift, ReLU, store: the lane holds channels 0 .. 15 from `dst` on (accumulator registers 0 .. 15 in that order)
+__device__ __forceinline__ void pair_store(const f32x16& a, const float* scale, const float* shift, bf16_t* dst) {
+    float sc[16], sh[16];
+#pragma unroll
+    for (int g = 0; g < 4; ++g) {
+        const float4 s = *(const float4*)(scale + 4 * g), h = *(const float4*)(shift + 4 * g);
+        sc[4 * g] = s.x; sc[4 * g + 1] = s.y; sc[4 * g + 2] = s.z; sc[4 * g + 3] = s.w;
+        sh[4 * g] = h.x; sh[4 * g + 1] = h.y; sh[4 * g + 2] = h.z; sh[4 * g + 3] = h.w;
+    }
+    uint32_t o[8];
+#pragma unroll
+    for (int e = 0; e < 8; ++e)
+        o[e] = pack_bf2(fmaxf(fmaf(a[2 * e], sc[2 * e], sh[2 * e]), 0.f), fmaxf(fmaf(a[2 * e + 1], sc[2 * e + 1], sh[2 * e + 1]), 0.f));
+    uint4* d = (uint4*)dst;
+    d[0] = make_uint4(o[0], o[1], o[2], o[3]);
+    d[1] = make_uint4(o[4], o[5], o[6], o[7]);
+}
+
+__global__ __launch_bounds__(IP_THREADS) void conv3x3_pair_kernel(const PairP p) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const long long m0 = (long long)blockIdx.x * IP_TM;
+    const int W = p.W;
+    const bool second = (int)blockIdx.y >= p.jobs0;
+    const int S = second ? p.S1 : p.S0, N = second ? p.N1 : p.N0;
+    const int ct = second ? p.ct1 : p.ct0, cy = second ? p.cy1 : p.cy0;
+    const uint4* wf = second ? p.wf1 : p.wf0;
+    const float* scale = second ? p.scale1 : p.scale0;
+    const float* shift = second ? p.shift1 : p.shift0;
+    const int tile0 = 2 * ((int)blockIdx.y - (second ? p.jobs0 : 0));
+    const int KC = S >> 4, row_b = 2 * S + 16;
+
+    // ---- 1. the flat pixel range m0 - W - 1 .. m0 + 128 + W of this convolution's slice of t, and the zero pixel, to LDS
+    {
+        const int C8 = 2 * KC;                                       // 16-byte chunks per pixel
+        const int total = (p.n_slots + 1) * C8;
+        const long long f0 = m0 - W - 1;
+        for (int i = tid; i < total; i += IP_THREADS) {
+            const int slot = i / C8, c8 = i - slot * C8;
+            const long long f = f0 + slot;
+            uint4 v = make_uint4(0, 0, 0, 0);
+            if (slot < p.n_slots && f >= 0 && f < p.M) v = *(const uint4*)(p.t + f * p.ldt + ct + c8 * 8);
+            *(uint4*)(smem + slot * row_b + c8 * 16) = v;
+        }
+    }
+
+    // ---- 2. the LDS byte offsets of the nine taps of this lane's pixel (B operand: pixel = lane % 32, channels 8 (lane / 32) ..)
+    int off[9];
+    const int hh = lane >> 5;
+    const int local = wave * 32 + (lane & 31);
+    const long long m = m0 + local;
+    {
+        const int HW = p.H * W;
+        const bool live = m < p.M;
+        const int rem = live ? (int)(m % HW) : 0;
+        const int h = rem / W, w = rem - h * W;
+#pragma unroll
+        for (int r = 0; r < 3; ++r)
+#pragma unroll
+            for (int s = 0; s < 3; ++s) {
+                const bool ok = live && (unsigned)(h + r - 1) < (unsigned)p.H && (unsigned)(w + s - 1) < (unsigned)W;
+                const int slot = ok ? local + r * W + s : p.n_slots;
+                off[r * 3 + s] = slot * row_b + hh * 16;
+            }
+    }
+    __syncthreads();
+
+    // ---- 3. the pair of tiles (one tile where the count is odd)
+    f32x16 acc[2];
+#pragma unroll
+    for (int j = 0; j < 2; ++j)
+#pragma unroll
+        for (int e = 0; e < 16; ++e) acc[j][e] = 0.f;
+    const int tiles = (N + 31) >> 5;
+    const bool two = tile0 + 1 < tiles;
+    const uint4* wt = wf + (long long)tile0 * (9 * KC) * 64;
+    if (two) pair_taps<2>(wt, smem, off, acc, KC, lane);
+    else pair_taps<1>(wt, smem, off, acc, KC, lane);
+    if (m >= p.M) return;
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+        const int n = (tile0 + j) * 32 + 16 * hh;                   // first of the lane's 16 channels inside its convolution
+        if (n + 16 <= N) pair_store(acc[j], scale + n, shift + n, p.y + m * p.ldy + cy + n);
+    }
+}
+
+size_t pair_lds(int W, int S) { return (size_t)(IP_TM + 2 * W + 3) * (2 * S + 16); }
+
+}  // namespace
+
+}  // namespace mv
+
+extern "C" {
+
+int mv_conv3x3_pair_supported(int S0, int S1, int N0, int N1, int H, int W, int x_dtype, int y_dtype) {
+    if (mv::get_flag("no_inception_fused") || mv::get_flag("force_generic")) return 0;
+    if (x_dtype != MV_BF16 || y_dtype != MV_BF16) return 0;
+    if (S0 < 16 || S1 < 16 || S0 > 512 || S1 > 512 || N0 < 16 || N1 < 16 || N0 > 4096 || N1 > 4096) return 0;
+    if ((S0 | S1 | N0 | N1) & 15) return 0;
+    if (H < 1 || W < 1 || H > 4096 || W > 4096) return 0;
+    return mv::pair_lds(W, S0 > S1 ? S0 : S1) <= (size_t)mv::IP_LDS_MAX;      // the tile and its halo rows have to fit LDS
+}
+
+int mv_conv3x3_pair_fwd(const void* t, int ldt, int ct0, int S0, int ct1, int S1, const void* w0_frag, const float* scale0,
+                        const float* shift0, const void* w1_frag, const float* scale1, const float* shift1, void* y, int ldy, int cy0,
+                        int N0, int cy1, int N1, int B, int H, int W, int x_dtype, int y_dtype, mv_stream_t stream_) {
+    using namespace mv;
+    MV_CHECK_ARG(t && w0_frag && scale0 && shift0 && w1_frag && scale1 && shift1 && y, "mv_conv3x3_pair_fwd: NULL argument");
+    MV_CHECK_ARG(t != y, "mv_conv3x3_pair_fwd: not in place");
+    MV_CHECK_ARG(B >= 1, "mv_conv3x3_pair_fwd: B=%d", B);
+    if (!mv_conv3x3_pair_supported(S0, S1, N0, N1, H, W, x_dtype, y_dtype)) {
+        set_error("mv_conv3x3_pair_fwd: unsupported S0=%d S1=%d N0=%d N1=%d H=%d W=%d x_dtype=%d y_dtype=%d (ask "
+                  "mv_conv3x3_pair_supported first)", S0, S1, N0, N1, H, W, x_dtype, y_dtype);
+        return MV_E_UNSUPPORTED;
+    }
+    MV_CHECK_ARG(!((ldt | ct0 | ct1 | ldy | cy0 | cy1) & 15) && ct0 >= 0 && ct1 >= 0 && cy0 >= 0 && cy1 >= 0,
+                 "mv_conv3x3_pair_fwd: strides and offsets are non-negative multiples of 16 (ldt=%d ct0=%d ct1=%d ldy=%d cy0=%d cy1=%d)",
+                 ldt, ct0, ct1, ldy, cy0, cy1);
+    MV_CHECK_ARG(ct0 + S0 <= ldt && ct1 + S1 <= ldt, "mv_conv3x3_pair_fwd: slices [%d, +%d) / [%d, +%d) of rows of %d", ct0, S0, ct1, S1,
+                 ldt);
+    MV_CHECK_ARG(cy0 + N0 <= ldy && cy1 + N1 <= ldy && (cy0 + N0 <= cy1 || cy1 + N1 <= cy0),
+                 "mv_conv3x3_pair_fwd: output slices [%d, +%d) / [%d, +%d) of rows of %d", cy0, N0, cy1, N1, ldy);
+    PairP p;
+    p.t = (const bf16_t*)t; p.y = (bf16_t*)y; p.ldt = ldt; p.ldy = ldy;
+    p.M = (long long)B * H * W;
+    MV_CHECK_ARG(p.M < (1ll << 31) - 8192, "mv_conv3x3_pair_fwd: %lld pixels", p.M);
+    p.wf0 = (const uint4*)w0_frag; p.scale0 = scale0; p.shift0 = shift0;
+    p.wf1 = (const uint4*)w1_frag; p.scale1 = scale1; p.shift1 = shift1;
+    p.H = H; p.W = W;
+    p.ct0 = ct0; p.S0 = S0; p.cy0 = cy0; p.N0 = N0;
+    p.ct1 = ct1; p.S1 = S1; p.cy1 = cy1; p.N1 = N1;
+    const int tiles0 = (N0 + 31) / 32, tiles1 = (N1 + 31) / 32;
+    p.jobs0 = (tiles0 + 1) / 2;
+    const int jobs = p.jobs0 + (tiles1 + 1) / 2;
+    p.n_slots = IP_TM + 2 * W + 2;
+    const size_t smem = pair_lds(W, S0 > S1 ? S0 : S1);
+    static LdsAttrSite site;
+    MV_HIP(site.ensure((const void*)conv3x3_pair_kernel, smem));
+    const dim3 grid((unsigned)((p.M + IP_TM - 1) / IP_TM), (unsigned)jobs);
+    set_kernel_name("conv3x3_pair");
+    hipLaunchKernelGGL(conv3x3_pair_kernel, grid, dim3(IP_THREADS), smem, (hipStream_t)stream_, p);
+    MV_LAUNCH_CHECK();
+    return MV_OK;
+}
+
+}  // extern "C"

@@ -55,6 +55,7 @@ from .classification.shufflenetv2 import (
     shufflenet_v2_x2_0,
 )
 from .classification.squeezenet import SqueezeNet, squeezenet1_0, squeezenet1_1
+from .classification.googlenet import BasicConv2d, GoogLeNet, InceptionAux, _Inception, googlenet
 from .segmentation.deeplabv3 import ASPP, DeepLabHead, DeepLabV3, deeplabv3
 from .segmentation.fcn import FCN, FCNHead, fcn
 from .segmentation.lraspp import LRASPP, LRASPPHead, lraspp_mobilenet_v3_large

@@ -2181,6 +2181,131 @@ def fire(x: Act, mod) -> Act:
     return Act(y, "map", x.batched)
 
 
+# ------------------------------------------------------------------ GoogLeNet Inception module (conv1x1_split.hip, inception_pair.hip)
+def inception_fragments(w: np.ndarray, s_pad: Optional[int] = None) -> np.ndarray:
+    """An [N][S][3][3] filter in the A-fragment order of mv_conv3x3_pair_fwd (header): `fire_fragments` of the filter with its input
+    channels padded by zero columns to `s_pad` (the reduce map's slice is 16-channel aligned) and its output rows padded by zero rows
+    to a multiple of 32 (N is a multiple of 16: the upper half of the last tile may not exist)."""
+    N, S, kh, kw = w.shape
+    Sp = S if s_pad is None else int(s_pad)
+    if N % 16 or Sp % 16 or Sp < S:
+        raise ValueError(f"inception_fragments: N={N} (multiple of 16), S={S} padded to {Sp} (multiple of 16)")
+    wp = np.zeros(((N + 31) // 32 * 32, Sp, kh, kw), np.float32)
+    wp[:N, :S] = np.asarray(w, np.float32)
+    return fire_fragments(wp)
+
+
+def inception_stack(parts):
+    """The merged pointwise convolution: `parts` = [(w [n][C][1][1], scale [n], shift [n])] -> (W [N][C], scale [N], shift [N], the
+    parts' first rows), every part padded to a multiple of 16 rows with zero filters, zero scale and zero shift (a padded column
+    computes relu(0 * acc + 0) = 0)."""
+    C = parts[0][0].shape[1]
+    rows, sc, sh, starts = [], [], [], []
+    n = 0
+    for w, s, h in parts:
+        k = w.shape[0]
+        kp = (k + 15) // 16 * 16
+        wp, sp, hp = np.zeros((kp, C), np.float32), np.zeros((kp,), np.float32), np.zeros((kp,), np.float32)
+        wp[:k], sp[:k], hp[:k] = np.asarray(w, np.float32).reshape(k, C), s, h
+        rows.append(wp), sc.append(sp), sh.append(hp), starts.append(n)
+        n += kp
+    return np.concatenate(rows), np.concatenate(sc), np.concatenate(sh), starts
+
+
+def _inception_units(mod):
+    """(branch1, 3x3 reduce, 3x3, "5x5" reduce, "5x5", pool projection) when `mod` is the reference's module built from BasicConv2d
+    units (1x1 / 3x3 pad 1, stride 1, dense) with the 3x3 stride-1 pad-1 max pool in branch 4, else None."""
+    from .nn import Conv2d, BatchNorm, MaxPool2d, Sequential
+    from .models.classification.googlenet import BasicConv2d
+    b2, b3, b4 = mod.branch2, mod.branch3, mod.branch4
+    if not all(isinstance(b, Sequential) and len(b.layers) == 2 for b in (b2, b3, b4)):
+        return None
+    pool = b4.layers[0]
+    units = (mod.branch1, b2.layers[0], b2.layers[1], b3.layers[0], b3.layers[1], b4.layers[1])
+    if not (type(pool) is MaxPool2d and pool.kernel_size == (3, 3) and pool.stride == (1, 1) and pool.padding == (1, 1)):
+        return None
+    one = (1, 1)
+    for u, k in zip(units, (1, 1, 3, 1, 3, 1)):
+        if not (type(u) is BasicConv2d and type(u.conv) is Conv2d and type(u.bn) is BatchNorm):
+            return None
+        c = u.conv
+        if not (c.kernel_size == (k, k) and c.padding == (k // 2, k // 2) and c.stride == one and c.dilation == one and c.groups == 1
+                and c.bias is None):
+            return None
+    C = units[0].conv.in_channels
+    if not (units[1].conv.in_channels == units[3].conv.in_channels == units[5].conv.in_channels == C
+            and units[2].conv.in_channels == units[1].conv.out_channels and units[4].conv.in_channels == units[3].conv.out_channels):
+        return None
+    return units
+
+
+def _inception_pool(x: Act, pool) -> Act:
+    from .nn import MaxPool2d
+    if type(pool) is MaxPool2d and pool.stride == (1, 1):
+        return maxpool2d(x, pool.kernel_size, pool.stride, pool.padding)    # at stride 1 ceil mode never grows the output
+    return pool(x)
+
+
+def inception_literal(x: Act, mod) -> Act:
+    """The reference's module (googlenet.py:229-237): four branches and the concatenation.  BatchNorm ignores its key."""
+    x = as_map(x)
+    b4 = mod.branch4
+    from .nn import Sequential
+    p4 = b4.layers[1](_inception_pool(x, b4.layers[0])) if isinstance(b4, Sequential) and len(b4.layers) == 2 else b4(x)
+    return concat_channels([mod.branch1(x), mod.branch2(x), mod.branch3(x), p4])
+
+
+# (C_in, H) of module shapes kept on the composition because the 4-launch path measured slower there (DESIGN.md 3.7); the switch
+# "inception_always" overrides it for measurements
+INCEPTION_LITERAL_SHAPES = frozenset()
+
+
+def inception(x: Act, mod) -> Act:
+    """One Inception module.  bf16 inference where the two kernels have the shapes: 4 launches and no concatenation -- the merged
+    1x1 (branch 1 into its slice of the output, the two reduce maps into the scratch map t), the stride-1 max pool, the pool
+    projection into its slice, both 3x3 convolutions into theirs.  Otherwise (fp32 mode, training-mode BatchNorm, the switches
+    "no_inception_fused" / "force_generic", other module structures or shapes): the literal composition."""
+    x = as_map(x)
+    B, H, W, C = x.t.shape
+    units = _inception_units(mod) if compute_dtype() == "bf16" and x.t.dtype == torch.bfloat16 else None
+    if units is None or any(_bn_training(u.bn) for u in units) or C != units[0].conv.in_channels:
+        return inception_literal(x, mod)
+    c1, c3r, c3, c5r, c5, cp = (u.conv.out_channels for u in units)
+    c5p = (c5r + 15) // 16 * 16
+    lt, Ct = c3r + c5p, c1 + c3 + c5 + cp
+    lib, BF = _lib.load(), _lib.BF16
+    if not (lib.mv_conv1x1_split_supported(C, c1 + lt, c1, Ct, 0, lt, 0, BF, BF)
+            and lib.mv_conv1x1_split_supported(C, cp, cp, Ct, c1 + c3 + c5, 0, 0, BF, BF)
+            and lib.mv_conv3x3_pair_supported(c3r, c5p, c3, c5, H, W, BF, BF)):
+        return inception_literal(x, mod)
+    if (C, H) in INCEPTION_LITERAL_SHAPES and H == W and not _lib.get_flag("inception_always"):
+        return inception_literal(x, mod)
+    cache = mod._cache()
+    key = ("inception", tuple(_bn_id(u.bn) for u in units))
+    hit = cache.get(key)
+    if hit is None:
+        f = [(np.asarray(u.conv.weight, np.float32),) + bn_fold(u.bn) for u in units]
+        wm, sm, hm, _ = inception_stack([f[0], f[1], f[3]])
+        d32 = lambda a: _dev(a, torch.float32)
+        hit = dict(merged=(_dev(wm, torch.bfloat16), d32(sm), d32(hm)),
+                   proj=(_dev(f[5][0].reshape(cp, C), torch.bfloat16), d32(f[5][1]), d32(f[5][2])),
+                   w3=(_dev(inception_fragments(f[2][0]), torch.bfloat16), d32(f[2][1]), d32(f[2][2])),
+                   w5=(_dev(inception_fragments(f[4][0], c5p), torch.bfloat16), d32(f[4][1]), d32(f[4][2])))
+        cache[key] = hit
+    M, st = B * H * W, stream_ptr()
+    y = empty((B, H, W, Ct), torch.bfloat16)
+    t = empty((B, H, W, lt), torch.bfloat16)
+    w, s, h = hit["merged"]
+    _lib.call("mv_conv1x1_split_fwd", _ptr(x.t), _ptr(w), _ptr(s), _ptr(h), _ptr(y), Ct, 0, _ptr(t), lt, 0, M, C, c1 + lt, c1, BF, BF, st)
+    p = maxpool2d(x, 3, 1, 1)
+    w, s, h = hit["proj"]
+    _lib.call("mv_conv1x1_split_fwd", _ptr(p.t), _ptr(w), _ptr(s), _ptr(h), _ptr(y), Ct, c1 + c3 + c5, None, 0, 0, M, C, cp, cp, BF, BF, st)
+    (w3, s3, h3), (w5, s5, h5) = hit["w3"], hit["w5"]
+    _lib.call("mv_conv3x3_pair_fwd", _ptr(t), lt, 0, c3r, c3r, c5p, _ptr(w3), _ptr(s3), _ptr(h3), _ptr(w5), _ptr(s5), _ptr(h5), _ptr(y), Ct,
+              c1, c3, c1 + c3, c5, B, H, W, BF, BF, st)
+    return Act(y, "map", x.batched)
+
+
 # ------------------------------------------------------------------ element-wise (unfused call sites)
 def _canon(x: Act) -> Act:
     return as_map(x) if x.kind == "img" else (x if x.kind == "map" else as_rows(x))

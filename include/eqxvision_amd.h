@@ -398,6 +398,35 @@ int mv_fire_expand_supported(int S, int E1, int E3, int H, int W, int x_dtype, i
 int mv_fire_expand_fwd(const void* t, const void* w1_frag, const float* b1, const void* w3_frag, const float* b3, void* y, int B,
                        int H, int W, int S, int E1, int E3, int x_dtype, int y_dtype, mv_stream_t stream);
 
+/* GoogLeNet Inception module (googlenet.py:229-237), the pointwise convolutions: folded BatchNorm + ReLU, the output columns split
+ * over one or two strided destinations so that a branch lands in its channel slice of the module's output:
+ *   v[m, n] = relu( scale[n] * sum_{c<C} w[n][c] x[m][c] + shift[n] )        m < M, n < N
+ *   n <  n0:  dst0[m * ld0 + c0 + n]        = v[m, n]
+ *   n >= n0:  dst1[m * ld1 + c1 + (n - n0)] = v[m, n]
+ * x bf16 [M][C] dense rows, w bf16 [N][C] (the stacked filters of the merged convolutions), scale / shift fp32 [N]; fp32 accumulation.
+ * n0 == N with dst1 == NULL is the one-destination form.  C, N, n0, the offsets and the strides (in elements) are multiples of 16:
+ * every row is written in 16-byte pieces; nothing outside the two slices is touched.  bf16 only, not in place.  Flags
+ * "no_inception_fused" / "force_generic": _supported returns 0 (the caller composes mv_conv2d_nhwc_fwd + mv_copy_rows). */
+int mv_conv1x1_split_supported(int C, int N, int n0, int ld0, int c0, int ld1, int c1, int x_dtype, int y_dtype);
+int mv_conv1x1_split_fwd(const void* x, const void* w, const float* scale, const float* shift, void* dst0, int ld0, int c0, void* dst1,
+                         int ld1, int c1, int64_t M, int C, int N, int n0, int x_dtype, int y_dtype, mv_stream_t stream);
+
+/* GoogLeNet Inception module, the 3x3 convolutions of branches 2 and 3 (googlenet.py:206-220) in one launch: padding 1, stride 1, folded
+ * BatchNorm + ReLU; convolution i reads channels [ct_i, ct_i + S_i) of t and writes channels [cy_i, cy_i + N_i) of y:
+ *   y[m, cy_i + n] = relu( scale_i[n] * sum_{r,s<3, c<S_i} W_i[n][c][r][s] t[b, h + r - 1, w + s - 1, ct_i + c] + shift_i[n] )
+ * m = b*H*W + h*W + w; t NHWC bf16 with rows of ldt elements, y NHWC bf16 with rows of ldy; the output slices do not overlap; not in
+ * place; fp32 accumulation.  A workgroup stages 128 pixels of one slice with their halo in LDS (the padding is zeros written to LDS) and
+ * computes one pair of 32-channel tiles of one convolution, so small maps still fill the machine with output-channel tiles.
+ * w_i_frag: the A-fragment order of mv_fire_expand_fwd with the rows padded by zeros to a multiple of 32
+ * (eqxvision_amd/ops.py: inception_fragments):
+ *   w_frag[tile 0..ceil(N/32)-1][step 0..9 S/16-1][lane 0..63][e 0..7] = Wk[32*tile + chan(lane%32)][16*step + 8*(lane/32) + e]
+ *   k = (3 r + s) * S + c,  chan(p) = 16*((p/4)%2) + 4*(p/8) + p%4
+ * S_i, N_i, offsets and strides are multiples of 16; (131 + 2 W) * (2 max(S_0, S_1) + 16) <= 160 KiB; bf16 only.  Flags as above. */
+int mv_conv3x3_pair_supported(int S0, int S1, int N0, int N1, int H, int W, int x_dtype, int y_dtype);
+int mv_conv3x3_pair_fwd(const void* t, int ldt, int ct0, int S0, int ct1, int S1, const void* w0_frag, const float* scale0,
+                        const float* shift0, const void* w1_frag, const float* scale1, const float* shift1, void* y, int ldy, int cy0,
+                        int N0, int cy1, int N1, int B, int H, int W, int x_dtype, int y_dtype, mv_stream_t stream);
+
 /* y[r, j] = x[r, idx[j]] over the channel axis of rows x C_in -> rows x C_out (the literal channel shuffle / split of ShuffleNetV2,
  * shufflenetv2.py:16-23, where the folded layout is not used).  idx: C_out device int32 (an index outside 0 .. C_in-1 gives 0);
  * MV_F32 or MV_BF16, any channel counts, not in place.  A bit copy. */
