@@ -11,11 +11,11 @@
 // operand (rows = output channels) and the pixels as the B operand.  The reduction runs in chunks of 64 channels: both operands of a
 // chunk are staged in LDS (rows of 128 + 16 bytes: the 16-byte reads of 32 consecutive rows fall on different bank quads), double
 // buffered, with the next chunk's global loads in flight in registers while the matrix cores work on the current one -- one barrier
-// per chunk.  The lane reads weight row chan(lane % 32) = 16 ((p / 4) % 2) + 4 (p / 8) + p % 4 of its 32-row tile, so its 16
-// accumulator registers are 16 CONSECUTIVE output channels of one pixel: scale, shift, ReLU and two 16-byte stores, to whichever
-// destination the 16-channel group belongs (n0 is a multiple of 16).  Rows past M, columns past N and channels past C are zeros in
+// per chunk.  The lane reads weight row mfma32_tile_row(lane % 32) of its 32-row tile, so its 16 accumulator registers are 16
+// CONSECUTIVE output channels of one pixel (flat3x3.h): scale, shift, ReLU and two 16-byte stores, to whichever destination the
+// 16-channel group belongs (n0 is a multiple of 16).  Rows past M, columns past N and channels past C are zeros in
 // LDS and are never read from memory.
-#include "mfma_common.h"
+#include "flat3x3.h"
 
 namespace mv {
 
@@ -38,23 +38,6 @@ struct SplitP {
     int C, N, n0, c0, c1;
 };
 
-__device__ __forceinline__ void split_store(const f32x16& a, const float* scale, const float* shift, bf16_t* dst) {
-    float sc[16], sh[16];
-#pragma unroll
-    for (int g = 0; g < 4; ++g) {
-        const float4 s = *(const float4*)(scale + 4 * g), h = *(const float4*)(shift + 4 * g);
-        sc[4 * g] = s.x; sc[4 * g + 1] = s.y; sc[4 * g + 2] = s.z; sc[4 * g + 3] = s.w;
-        sh[4 * g] = h.x; sh[4 * g + 1] = h.y; sh[4 * g + 2] = h.z; sh[4 * g + 3] = h.w;
-    }
-    uint32_t o[8];
-#pragma unroll
-    for (int e = 0; e < 8; ++e)
-        o[e] = pack_bf2(fmaxf(fmaf(a[2 * e], sc[2 * e], sh[2 * e]), 0.f), fmaxf(fmaf(a[2 * e + 1], sc[2 * e + 1], sh[2 * e + 1]), 0.f));
-    uint4* d = (uint4*)dst;
-    d[0] = make_uint4(o[0], o[1], o[2], o[3]);
-    d[1] = make_uint4(o[4], o[5], o[6], o[7]);
-}
-
 __global__ __launch_bounds__(CS_THREADS) void conv1x1_split_kernel(const SplitP p) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -62,7 +45,7 @@ __global__ __launch_bounds__(CS_THREADS) void conv1x1_split_kernel(const SplitP 
     const int nb0 = blockIdx.y * CS_TN;
     const int wm = wave & 1, wn = wave >> 1;
     const int hh = lane >> 5, pl = lane & 31;
-    const int chan = 16 * ((pl >> 2) & 1) + 4 * (pl >> 3) + (pl & 3);
+    const int chan = mfma32_tile_row(pl);
 
     // staging: the thread moves 16-byte piece tid % 8 of rows tid / 8 + 32 j of both operands
     const int sr = tid >> 3, sc8 = tid & 7;
@@ -135,7 +118,7 @@ __global__ __launch_bounds__(CS_THREADS) void conv1x1_split_kernel(const SplitP 
             const long long m = m0 + wm * 64 + q * 32 + pl;
             if (m >= p.M) continue;
             bf16_t* dst = n < p.n0 ? p.dst0 + m * p.ld0 + p.c0 + n : p.dst1 + m * p.ld1 + p.c1 + (n - p.n0);
-            split_store(acc[j][q], p.scale + n, p.shift + n, dst);
+            store16_relu(acc[j][q], p.scale + n, p.shift + n, dst);
         }
     }
 }

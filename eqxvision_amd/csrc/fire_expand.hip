@@ -4,22 +4,12 @@
 //   y[m, n]      = relu( b1[n] + sum_{c<S}          W1[n][c]       t[m, c] )                       n < E1
 //   y[m, E1 + n] = relu( b3[n] + sum_{r,s<3, c<S}   W3[n][c][r][s] t[b, h + r - 1, w + s - 1, c] ) n < E3     (zero padding)
 //
-// m is the FLATTENED pixel index b * H * W + h * W + w.  A 256-thread workgroup owns TM = 128 PT consecutive pixels whatever image
-// they belong to (13 x 13 maps fill the machine at batch size) and stages, once, the flat pixel range m0 - W - 1 .. m0 + TM + W of t
-// in LDS: the tile and its one-pixel halo are all inside it (neighbour (dh, dw) of pixel m is flat pixel m + dh W + dw).  Range
-// entries outside 0 .. M-1 are written as zeros, and one more all-zero slot follows the range: a tap that falls outside the MAP
-// (or belongs to a pixel past M) reads that slot, so the padding is zeros in LDS and is never read from HBM.  A slot is S bf16 + 16
-// bytes of padding (row strides 48 / 80 / 112 / 144 bytes: the 16-byte reads of 16 consecutive pixels fall on 16 different bank
-// quads).
-//
-// The product runs on v_mfma_f32_32x32x16_bf16 with the weights as the A operand (rows = output channels) and the pixels as the B
-// operand: the k-step is 16 channels of ONE tap, which divides every S in {16, 32, 48, 64}, so no step ever reads past a pixel's S
-// channels and nothing is padded.  A wave owns 32 PT pixels and walks every 64-channel pair of output tiles from the one LDS copy:
-// the expand1x1 tiles reduce over the centre tap only (S / 16 steps), the expand3x3 tiles over the nine taps (9 S / 16 steps); every
-// B fragment read from LDS feeds two MFMAs and every A fragment PT.  The weights are streamed from L2 in fragment order (packed once
-// on the host, ops.fire_fragments); the rows of a 32-channel tile are permuted in the packed array so that a lane ends up with 16
-// CONSECUTIVE output channels of its pixel in the accumulator: bias, ReLU and two 16-byte stores into the tensor's channel slice.
-#include "mfma_common.h"
+// A 256-thread workgroup owns TM = 128 PT consecutive flattened pixels (13 x 13 maps fill the machine at batch size) and stages their
+// flat range of t in LDS once (flat3x3.h: the range, the zero slot, the fragment order).  The k-step of 16 channels divides every S
+// in {16, 32, 48, 64}, so nothing is padded.  A wave owns 32 PT pixels and walks every 64-channel pair of output tiles from the one
+// LDS copy: the expand1x1 tiles reduce over the centre tap only (S / 16 steps), the expand3x3 tiles over the nine taps (9 S / 16
+// steps), fully unrolled; every B fragment read from LDS feeds two MFMAs and every A fragment PT.
+#include "flat3x3.h"
 
 namespace mv {
 
@@ -91,40 +81,14 @@ __global__ __launch_bounds__(FE_THREADS) void fire_expand_kernel(const FireP p) 
     const long long m0 = (long long)blockIdx.x * TM;
     const int W = p.W, S = p.S;
 
-    // ---- 1. the flat pixel range m0 - W - 1 .. m0 + TM + W of t, and the zero pixel, to LDS
-    {
-        constexpr int C8 = 2 * KC;                                   // 16-byte chunks per pixel
-        const int total = (p.n_slots + 1) * C8;
-        const long long f0 = m0 - W - 1;
-        for (int i = tid; i < total; i += FE_THREADS) {
-            const int slot = i / C8, c8 = i - slot * C8;
-            const long long f = f0 + slot;
-            uint4 v = make_uint4(0, 0, 0, 0);
-            if (slot < p.n_slots && f >= 0 && f < p.M) v = *(const uint4*)(p.t + f * S + c8 * 8);
-            *(uint4*)(smem + slot * p.row_b + c8 * 16) = v;
-        }
-    }
+    // ---- 1. the flat pixel range of t and the zero pixel to LDS; 2 KC 16-byte chunks per pixel
+    flat_stage<FE_THREADS>(smem, p.t, S, 0, 2 * KC, m0, W, p.M, p.n_slots, p.row_b, tid);
 
-    // ---- 2. the LDS byte offsets of the nine taps of this lane's pixels (B operand: pixel = lane % 32, channels 8 (lane / 32) ..)
+    // ---- 2. the LDS byte offsets of the nine taps of this lane's pixels
     int off[PT][9];
     const int hh = lane >> 5;
-    const int HW = p.H * W;
 #pragma unroll
-    for (int q = 0; q < PT; ++q) {
-        const int local = (wave * PT + q) * 32 + (lane & 31);
-        const long long m = m0 + local;
-        const bool live = m < p.M;
-        const int rem = live ? (int)(m % HW) : 0;
-        const int h = rem / W, w = rem - h * W;
-#pragma unroll
-        for (int r = 0; r < 3; ++r)
-#pragma unroll
-            for (int s = 0; s < 3; ++s) {
-                const bool ok = live && (unsigned)(h + r - 1) < (unsigned)p.H && (unsigned)(w + s - 1) < (unsigned)W;
-                const int slot = ok ? local + r * W + s : p.n_slots;
-                off[q][r * 3 + s] = slot * p.row_b + hh * 16;
-            }
-    }
+    for (int q = 0; q < PT; ++q) flat_tap_offsets(off[q], (wave * PT + q) * 32 + (lane & 31), m0, p.M, p.H, W, p.n_slots, p.row_b, hh);
     __syncthreads();
 
     // ---- 3. every 64-channel pair of output tiles from the one copy: expand1x1 (centre tap), then expand3x3 (nine taps)
@@ -154,14 +118,12 @@ __global__ __launch_bounds__(FE_THREADS) void fire_expand_kernel(const FireP p) 
     }
 }
 
-size_t fire_lds(int PT, int W, int S) { return (size_t)(128 * PT + 2 * W + 3) * (2 * S + 16); }
-
 template <int PT, int KC>
 int fire_go(FireP p, hipStream_t st) {
     static LdsAttrSite site;
     auto kern = fire_expand_kernel<PT, KC>;
     p.n_slots = 128 * PT + 2 * p.W + 2;
-    const size_t smem = fire_lds(PT, p.W, p.S);
+    const size_t smem = flat_lds_bytes(128 * PT, p.W, p.S);
     MV_HIP(site.ensure((const void*)kern, smem));
     const long long blocks = (p.M + 128 * PT - 1) / (128 * PT);
     hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(FE_THREADS), smem, st, p);
@@ -191,7 +153,7 @@ int mv_fire_expand_supported(int S, int E1, int E3, int H, int W, int x_dtype, i
     if (S != 16 && S != 32 && S != 48 && S != 64) return 0;
     if (E1 != E3 || (E1 != 64 && E1 != 128 && E1 != 192 && E1 != 256)) return 0;
     if (H < 1 || W < 1 || H > 4096 || W > 4096) return 0;
-    return mv::fire_lds(1, W, S) <= (size_t)mv::FE_LDS_MAX;           // the tile and its halo rows have to fit LDS
+    return mv::flat_lds_bytes(128, W, S) <= (size_t)mv::FE_LDS_MAX;           // the tile and its halo rows have to fit LDS
 }
 
 int mv_fire_expand_fwd(const void* t, const void* w1_frag, const float* b1, const void* w3_frag, const float* b3, void* y, int B,
@@ -213,7 +175,7 @@ int mv_fire_expand_fwd(const void* t, const void* w1_frag, const float* b1, cons
     hipStream_t st = (hipStream_t)stream_;
     // 256 pixels per workgroup (every weight fragment feeds two pixel tiles per wave) while that leaves two workgroups per CU
     // busy and resident; flag "fire_expand_m256": at any size (the parity tests run both tiles on small maps)
-    const bool wide = (p.M >= 256ll * 512 || get_flag("fire_expand_m256")) && fire_lds(2, W, S) <= (size_t)FE_LDS_TWO;
+    const bool wide = (p.M >= 256ll * 512 || get_flag("fire_expand_m256")) && flat_lds_bytes(256, W, S) <= (size_t)FE_LDS_TWO;
     if (wide) {
         set_kernel_name("fire_expand_m256");
         return fire_go_kc<2>(p, st);

@@ -4,21 +4,13 @@
 //
 //   y[m, cy_i + n] = relu( scale_i[n] * sum_{r,s<3, c<S_i} W_i[n][c][r][s] t[b, h + r - 1, w + s - 1, ct_i + c] + shift_i[n] )   n < N_i
 //
-// for i = 0, 1; rows of t are ldt apart, rows of y ldy.  m is the FLATTENED pixel index b * H * W + h * W + w.  A 256-thread workgroup
-// owns 128 consecutive pixels whatever image they belong to and ONE pair of 32-channel output tiles of ONE of the two convolutions
-// (blockIdx.y): 7 x 7 and 14 x 14 maps at batch size are few pixel tiles, the output channels fill the machine.  It stages, once,
-// the flat pixel range m0 - W - 1 .. m0 + 128 + W of its convolution's slice of t in LDS: the tile and its one-pixel halo are all
-// inside it (neighbour (dh, dw) of pixel m is flat pixel m + dh W + dw).  Range entries outside 0 .. M-1 are written as zeros, and
-// one more all-zero slot follows the range: a tap that falls outside its IMAGE's map (or belongs to a pixel past M) reads that slot,
-// so the padding is zeros in LDS and is never read from memory.  A slot is S_i bf16 + 16 bytes of padding.
-//
-// The product runs on v_mfma_f32_32x32x16_bf16 with the weights as the A operand (rows = output channels) and the pixels as the B
-// operand; the k-step is 16 channels of ONE tap (S_i is a multiple of 16).  A wave owns 32 pixels and both tiles of the pair.  The
-// weights are streamed from L2 in fragment order (packed once on the host, ops.inception_fragments: output rows padded with zeros to
-// a multiple of 32, the rows of a tile permuted so that a lane ends up with 16 CONSECUTIVE output channels of its pixel in the
-// accumulator): scale, shift, ReLU and two 16-byte stores.  N_i is a multiple of 16: the upper half of the last tile may not exist
-// (it is computed on the zero rows and not stored), and an odd tile count leaves the last workgroup column a single tile.
-#include "mfma_common.h"
+// for i = 0, 1; rows of t are ldt apart, rows of y ldy.  A 256-thread workgroup owns 128 consecutive flattened pixels and ONE pair of
+// 32-channel output tiles of ONE of the two convolutions (blockIdx.y): 7 x 7 and 14 x 14 maps at batch size are few pixel tiles, the
+// output channels fill the machine.  It stages the flat range of its convolution's slice of t (S_i channels per slot) in LDS once
+// (flat3x3.h: the range, the zero slot, the fragment order; host: ops.inception_fragments pads the output rows with zeros to a
+// multiple of 32).  A wave owns 32 pixels and both tiles of the pair.  N_i is a multiple of 16: the upper half of the last tile may
+// not exist (it is computed on the zero rows and not stored), and an odd tile count leaves the last workgroup column a single tile.
+#include "flat3x3.h"
 
 namespace mv {
 
@@ -69,24 +61,6 @@ __device__ __forceinline__ void pair_taps(const uint4* __restrict__ wf, const ch
     }
 }
 
-// scale, shift, ReLU, store: the lane holds channels 0 .. 15 from `dst` on (accumulator registers 0 .. 15 in that order)
-__device__ __forceinline__ void pair_store(const f32x16& a, const float* scale, const float* shift, bf16_t* dst) {
-    float sc[16], sh[16];
-#pragma unroll
-    for (int g = 0; g < 4; ++g) {
-        const float4 s = *(const float4*)(scale + 4 * g), h = *(const float4*)(shift + 4 * g);
-        sc[4 * g] = s.x; sc[4 * g + 1] = s.y; sc[4 * g + 2] = s.z; sc[4 * g + 3] = s.w;
-        sh[4 * g] = h.x; sh[4 * g + 1] = h.y; sh[4 * g + 2] = h.z; sh[4 * g + 3] = h.w;
-    }
-    uint32_t o[8];
-#pragma unroll
-    for (int e = 0; e < 8; ++e)
-        o[e] = pack_bf2(fmaxf(fmaf(a[2 * e], sc[2 * e], sh[2 * e]), 0.f), fmaxf(fmaf(a[2 * e + 1], sc[2 * e + 1], sh[2 * e + 1]), 0.f));
-    uint4* d = (uint4*)dst;
-    d[0] = make_uint4(o[0], o[1], o[2], o[3]);
-    d[1] = make_uint4(o[4], o[5], o[6], o[7]);
-}
-
 __global__ __launch_bounds__(IP_THREADS) void conv3x3_pair_kernel(const PairP p) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -101,39 +75,15 @@ __global__ __launch_bounds__(IP_THREADS) void conv3x3_pair_kernel(const PairP p)
     const int tile0 = 2 * ((int)blockIdx.y - (second ? p.jobs0 : 0));
     const int KC = S >> 4, row_b = 2 * S + 16;
 
-    // ---- 1. the flat pixel range m0 - W - 1 .. m0 + 128 + W of this convolution's slice of t, and the zero pixel, to LDS
-    {
-        const int C8 = 2 * KC;                                       // 16-byte chunks per pixel
-        const int total = (p.n_slots + 1) * C8;
-        const long long f0 = m0 - W - 1;
-        for (int i = tid; i < total; i += IP_THREADS) {
-            const int slot = i / C8, c8 = i - slot * C8;
-            const long long f = f0 + slot;
-            uint4 v = make_uint4(0, 0, 0, 0);
-            if (slot < p.n_slots && f >= 0 && f < p.M) v = *(const uint4*)(p.t + f * p.ldt + ct + c8 * 8);
-            *(uint4*)(smem + slot * row_b + c8 * 16) = v;
-        }
-    }
+    // ---- 1. the flat pixel range of this convolution's slice of t and the zero pixel to LDS
+    flat_stage<IP_THREADS>(smem, p.t, p.ldt, ct, 2 * KC, m0, W, p.M, p.n_slots, row_b, tid);
 
-    // ---- 2. the LDS byte offsets of the nine taps of this lane's pixel (B operand: pixel = lane % 32, channels 8 (lane / 32) ..)
+    // ---- 2. the LDS byte offsets of the nine taps of this lane's pixel
     int off[9];
     const int hh = lane >> 5;
     const int local = wave * 32 + (lane & 31);
     const long long m = m0 + local;
-    {
-        const int HW = p.H * W;
-        const bool live = m < p.M;
-        const int rem = live ? (int)(m % HW) : 0;
-        const int h = rem / W, w = rem - h * W;
-#pragma unroll
-        for (int r = 0; r < 3; ++r)
-#pragma unroll
-            for (int s = 0; s < 3; ++s) {
-                const bool ok = live && (unsigned)(h + r - 1) < (unsigned)p.H && (unsigned)(w + s - 1) < (unsigned)W;
-                const int slot = ok ? local + r * W + s : p.n_slots;
-                off[r * 3 + s] = slot * row_b + hh * 16;
-            }
-    }
+    flat_tap_offsets(off, local, m0, p.M, p.H, W, p.n_slots, row_b, hh);
     __syncthreads();
 
     // ---- 3. the pair of tiles (one tile where the count is odd)
@@ -151,11 +101,9 @@ __global__ __launch_bounds__(IP_THREADS) void conv3x3_pair_kernel(const PairP p)
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
         const int n = (tile0 + j) * 32 + 16 * hh;                   // first of the lane's 16 channels inside its convolution
-        if (n + 16 <= N) pair_store(acc[j], scale + n, shift + n, p.y + m * p.ldy + cy + n);
+        if (n + 16 <= N) store16_relu(acc[j], scale + n, shift + n, p.y + m * p.ldy + cy + n);
     }
 }
-
-size_t pair_lds(int W, int S) { return (size_t)(IP_TM + 2 * W + 3) * (2 * S + 16); }
 
 }  // namespace
 
@@ -169,7 +117,7 @@ int mv_conv3x3_pair_supported(int S0, int S1, int N0, int N1, int H, int W, int 
     if (S0 < 16 || S1 < 16 || S0 > 512 || S1 > 512 || N0 < 16 || N1 < 16 || N0 > 4096 || N1 > 4096) return 0;
     if ((S0 | S1 | N0 | N1) & 15) return 0;
     if (H < 1 || W < 1 || H > 4096 || W > 4096) return 0;
-    return mv::pair_lds(W, S0 > S1 ? S0 : S1) <= (size_t)mv::IP_LDS_MAX;      // the tile and its halo rows have to fit LDS
+    return mv::flat_lds_bytes(mv::IP_TM, W, S0 > S1 ? S0 : S1) <= (size_t)mv::IP_LDS_MAX;      // the tile and its halo rows have to fit LDS
 }
 
 int mv_conv3x3_pair_fwd(const void* t, int ldt, int ct0, int S0, int ct1, int S1, const void* w0_frag, const float* scale0,
@@ -204,7 +152,7 @@ int mv_conv3x3_pair_fwd(const void* t, int ldt, int ct0, int S0, int ct1, int S1
     p.jobs0 = (tiles0 + 1) / 2;
     const int jobs = p.jobs0 + (tiles1 + 1) / 2;
     p.n_slots = IP_TM + 2 * W + 2;
-    const size_t smem = pair_lds(W, S0 > S1 ? S0 : S1);
+    const size_t smem = flat_lds_bytes(IP_TM, W, S0 > S1 ? S0 : S1);
     static LdsAttrSite site;
     MV_HIP(site.ensure((const void*)conv3x3_pair_kernel, smem));
     const dim3 grid((unsigned)((p.M + IP_TM - 1) / IP_TM), (unsigned)jobs);

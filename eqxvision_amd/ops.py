@@ -2107,14 +2107,13 @@ def shuffle_head(x: Act, conv, bn, layout_in) -> Act:
 
 # ------------------------------------------------------------------ SqueezeNet Fire module (fire_expand.hip)
 FIRE_S64_LITERAL_PIXELS = 256 * 512      # the pixel count from which mv_fire_expand_fwd uses its 256-pixel tile
-FIRE_TILE_ROW =16 * ((np.arange(32) >> 2) & 1) + 4 * (np.arange(32) >> 3) + (np.arange(32) & 3)     # header: chan(p)
+FIRE_TILE_ROW = 16 * ((np.arange(32) >> 2) & 1) + 4 * (np.arange(32) >> 3) + (np.arange(32) & 3)     # csrc/flat3x3.h: mfma32_tile_row
 
 
 def fire_fragments(w: np.ndarray) -> np.ndarray:
-    """An [E][S][kh][kw] expand weight (1x1 or 3x3) in the A-fragment order of mv_fire_expand_fwd (header): with Wk[n][k],
+    """An [E][S][kh][kw] expand weight (1x1 or 3x3) in the A-fragment order of mv_fire_expand_fwd: with Wk[n][k],
     k = (3 r + s) * S + c, the array [E / 32][K / 16][lane 64][8] holds Wk[32 tile + chan(lane % 32)][16 step + 8 (lane / 32) + e],
-    chan = FIRE_TILE_ROW: row p of a tile is accumulator register (p % 4) + 4 (p / 8) of lane half (p / 4) % 2, so a lane's 16
-    registers are 16 consecutive output channels.  E % 32 == 0 and S % 16 == 0: nothing is padded."""
+    chan = FIRE_TILE_ROW (why: csrc/flat3x3.h).  E % 32 == 0 and S % 16 == 0: nothing is padded."""
     E, S, kh, kw = w.shape
     K = kh * kw * S
     if E % 32 or S % 16:
@@ -2183,7 +2182,7 @@ def fire(x: Act, mod) -> Act:
 
 # ------------------------------------------------------------------ GoogLeNet Inception module (conv1x1_split.hip, inception_pair.hip)
 def inception_fragments(w: np.ndarray, s_pad: Optional[int] = None) -> np.ndarray:
-    """An [N][S][3][3] filter in the A-fragment order of mv_conv3x3_pair_fwd (header): `fire_fragments` of the filter with its input
+    """An [N][S][3][3] filter in the A-fragment order of mv_conv3x3_pair_fwd (csrc/flat3x3.h): `fire_fragments` of the filter with its input
     channels padded by zero columns to `s_pad` (the reduce map's slice is 16-channel aligned) and its output rows padded by zero rows
     to a multiple of 32 (N is a multiple of 16: the upper half of the last tile may not exist)."""
     N, S, kh, kw = w.shape

@@ -51,7 +51,7 @@ def _launch_fire(t, w1, b1, w3, b3, wide):
     f3 = torch.from_numpy(ops.fire_fragments(w3.float().numpy())).to(torch.bfloat16).cuda()
     n = B * H * W * (E1 + E3)
     buf = torch.full((n + GUARD,), SENTINEL, dtype=torch.bfloat16, device="cuda")
-    td, b1d, b3d = t.cuda(), b1.cuda(), b3.cuda()
+    td, b1d, b3d = t.cuda(), None if b1 is None else b1.cuda(), None if b3 is None else b3.cuda()
     if wide:
         _lib.set_flag("fire_expand_m256", 1)
     try:
@@ -89,6 +89,29 @@ def test_fire_expand(S_):
             assert kern == ("fire_expand_m256" if wide else "fire_expand_m128")
             err = (y.double() - ref).abs()
             tag = dict(S=S_, E=E, hw=(H, W), B=B, kernel=kern)
+            print({**tag, "err_1x1": float(err[..., :E].max()), "err_3x3": float(err[..., E:].max()), "bound": 2.0 ** -8 * scale})
+            assert bool((guard == SENTINEL).all()), tag
+            assert float(err.max()) <= 2.0 ** -8 * scale, (tag, float(err.max()), scale)
+
+
+def test_fire_expand_no_bias():
+    """A convolution without a bias reaches the kernel as a null pointer (`ops.fire`): it stands for zeros, in either half and with the
+    other half's bias applied.  S = 16, E1 = E3 = 64 on the 5 x 7 map (B = 3), both pixel tiles, the bound of `test_fire_expand`."""
+    S_, E, (H, W, B) = 16, 64, MAPS[1]
+    g = torch.Generator().manual_seed(160057)
+    t = torch.randn(B, H, W, S_, generator=g).to(torch.bfloat16)
+    w1 = (torch.randn(E, S_, 1, 1, generator=g) / np.sqrt(S_)).to(torch.bfloat16)
+    w3 = (torch.randn(E, S_, 3, 3, generator=g) / np.sqrt(9 * S_)).to(torch.bfloat16)
+    b1, b3 = torch.randn(E, generator=g) * 0.1, torch.randn(E, generator=g) * 0.1
+    zeros = torch.zeros(E)
+    for c1, c3 in ((None, b3), (b1, None)):
+        ref = _fire_ref(t, w1, zeros if c1 is None else c1, w3, zeros if c3 is None else c3)
+        scale = float(ref.abs().max())
+        for wide in (False, True):
+            y, guard, kern = _launch_fire(t, w1, c1, w3, c3, wide)
+            assert kern == ("fire_expand_m256" if wide else "fire_expand_m128")
+            err = (y.double() - ref).abs()
+            tag = dict(b1=c1 is not None, b3=c3 is not None, kernel=kern)
             print({**tag, "err_1x1": float(err[..., :E].max()), "err_3x3": float(err[..., E:].max()), "bound": 2.0 ** -8 * scale})
             assert bool((guard == SENTINEL).all()), tag
             assert float(err.max()) <= 2.0 ** -8 * scale, (tag, float(err.max()), scale)
