@@ -93,6 +93,11 @@ PROTOTYPES = {
     "mv_conv1x1_split_fwd": [_vp] * 5 + [_i, _i, _vp, _i, _i, _i64] + [_i] * 5 + [_vp],
     "mv_conv3x3_pair_supported": [_i] * 8,
     "mv_conv3x3_pair_fwd": [_vp] + [_i] * 5 + [_vp] * 7 + [_i] * 10 + [_vp],
+    "mv_preact_conv1x1_supported": [_i] * 8,
+    "mv_preact_conv1x1_fwd": [_vp, _i, _vp, _vp, _vp, _vp, _vp, _vp] + [_i] * 10 + [_vp],
+    "mv_conv3x3_slice_supported": [_i] * 6,
+    "mv_conv3x3_slice_fwd": [_vp, _i, _i, _vp, _vp] + [_i] * 8 + [_vp],
+    "mv_avgpool2d_nhwc_fwd": [_vp, _vp] + [_i] * 8 + [_i, _vp],
     "mv_maxpool2d_out_nhwc_fwd": [_vp, _vp] + [_i] * 12 + [_i, _vp],
     "mv_conv2d_nchw_split_fwd": [_vp, _vp, _vp, _vp, _vp, _vp] + [_i] * 11 + [_i, _i, _i, _vp],
     "mv_resize_bilinear_nhwc_fwd": [_vp, _vp] + [_i] * 6 + [_i, _i, _i, _vp],

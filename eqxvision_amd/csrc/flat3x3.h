@@ -1,5 +1,6 @@
-// Pieces shared by the concat-free 3x3 kernels (fire_expand.hip, inception_pair.hip) and, for the epilogue and the tile-row
-// permutation, conv1x1_split.hip.  What a kernel keeps for itself is the formula it computes, its grid and its k-loop.
+// Pieces shared by the concat-free 3x3 kernels (fire_expand.hip, inception_pair.hip, conv3x3_slice.hip) and, for the epilogue and the
+// tile-row permutation, conv1x1_split.hip and preact1x1.hip.  What a kernel keeps for itself is the formula it computes and its grid;
+// the two kernels that give a workgroup ONE pair of output tiles (inception_pair.hip, conv3x3_slice.hip) share their k-loop too.
 //
 // The flat range.  m is the FLATTENED pixel index b * H * W + h * W + w of an NHWC bf16 tensor; a workgroup owns TM consecutive pixels
 // from m0 on, whatever image they belong to (small maps at batch size still fill the machine).  It stages, once, slots
@@ -61,6 +62,34 @@ __device__ __forceinline__ void flat_tap_offsets(int (&off)[9], const int local,
         }
 }
 
+// NJ 32-channel tiles x 32 pixels over the nine taps
+template <int NJ>
+__device__ __forceinline__ void flat_taps9(const uint4* __restrict__ wf, const char* lds, const int (&off)[9], f32x16 (&acc)[2], const int KC,
+                                          const int lane) {
+    // the k-steps of a tile are consecutive in the packed array whatever the tap: the fragments of step ks + 2 are requested while
+    // step ks runs (the index is clamped to the last step, so nothing past the tile is read)
+    const int KS = 9 * KC;
+    const uint4* wl = wf + lane;
+    const uint4* wh = wl + (NJ == 2 ? KS * 64 : 0);
+    uint4 n0a = wl[0], n0b = wh[0], n1a = wl[64], n1b = wh[64];
+    int ks = 0;
+#pragma unroll
+    for (int tap = 0; tap < 9; ++tap) {
+        const char* bp = lds + off[tap];
+        for (int kc = 0; kc < KC; ++kc, ++ks) {
+            const bf16x8 a0 = __builtin_bit_cast(bf16x8, n0a), a1 = __builtin_bit_cast(bf16x8, n0b);
+            n0a = n1a;
+            n0b = n1b;
+            const int nx = (ks + 2 < KS ? ks + 2 : KS - 1) * 64;
+            n1a = wl[nx];
+            if (NJ == 2) n1b = wh[nx];
+            const bf16x8 b = __builtin_bit_cast(bf16x8, *(const uint4*)(bp + kc * 32));
+            acc[0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a0, b, acc[0], 0, 0, 0);
+            if (NJ == 2) acc[1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1, b, acc[1], 0, 0, 0);
+        }
+    }
+}
+
 // relu(a * scale + shift), the lane holding channels 0 .. 15 from `dst` on (accumulator registers 0 .. 15 in that order); the
 // bounds checks are the caller's.  fire_expand.hip keeps its own epilogue (a + bias, a null bias, its check): routed through this
 // function, as a template on the arithmetic, with the check in front of the call or in a wrapper, its four 256-pixel instantiations
@@ -73,6 +102,16 @@ __device__ __forceinline__ void store16_relu(const f32x16& a, const float* scale
         o[2 * g] = pack_bf2(fmaxf(fmaf(a[4 * g], s.x, h.x), 0.f), fmaxf(fmaf(a[4 * g + 1], s.y, h.y), 0.f));
         o[2 * g + 1] = pack_bf2(fmaxf(fmaf(a[4 * g + 2], s.z, h.z), 0.f), fmaxf(fmaf(a[4 * g + 3], s.w, h.w), 0.f));
     }
+    uint4* d = (uint4*)dst;
+    d[0] = make_uint4(o[0], o[1], o[2], o[3]);
+    d[1] = make_uint4(o[4], o[5], o[6], o[7]);
+}
+
+// the identity form: the 16 values rounded to bf16 and stored as they are (a convolution with nothing behind it: negatives survive)
+__device__ __forceinline__ void store16_plain(const f32x16& a, bf16_t* dst) {
+    uint32_t o[8];
+#pragma unroll
+    for (int e = 0; e < 8; ++e) o[e] = pack_bf2(a[2 * e], a[2 * e + 1]);
     uint4* d = (uint4*)dst;
     d[0] = make_uint4(o[0], o[1], o[2], o[3]);
     d[1] = make_uint4(o[4], o[5], o[6], o[7]);

@@ -33,34 +33,6 @@ struct PairP {
     int n_slots;           // 128 + 2 W + 2 staged pixels; slot n_slots is the zero pixel
 };
 
-// NJ 32-channel tiles x 32 pixels over the nine taps
-template <int NJ>
-__device__ __forceinline__ void pair_taps(const uint4* __restrict__ wf, const char* lds, const int (&off)[9], f32x16 (&acc)[2], const int KC,
-                                          const int lane) {
-    // the k-steps of a tile are consecutive in the packed array whatever the tap: the fragments of step ks + 2 are requested while
-    // step ks runs (the index is clamped to the last step, so nothing past the tile is read)
-    const int KS = 9 * KC;
-    const uint4* wl = wf + lane;
-    const uint4* wh = wl + (NJ == 2 ? KS * 64 : 0);
-    uint4 n0a = wl[0], n0b = wh[0], n1a = wl[64], n1b = wh[64];
-    int ks = 0;
-#pragma unroll
-    for (int tap = 0; tap < 9; ++tap) {
-        const char* bp = lds + off[tap];
-        for (int kc = 0; kc < KC; ++kc, ++ks) {
-            const bf16x8 a0 = __builtin_bit_cast(bf16x8, n0a), a1 = __builtin_bit_cast(bf16x8, n0b);
-            n0a = n1a;
-            n0b = n1b;
-            const int nx = (ks + 2 < KS ? ks + 2 : KS - 1) * 64;
-            n1a = wl[nx];
-            if (NJ == 2) n1b = wh[nx];
-            const bf16x8 b = __builtin_bit_cast(bf16x8, *(const uint4*)(bp + kc * 32));
-            acc[0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a0, b, acc[0], 0, 0, 0);
-            if (NJ == 2) acc[1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1, b, acc[1], 0, 0, 0);
-        }
-    }
-}
-
 __global__ __launch_bounds__(IP_THREADS) void conv3x3_pair_kernel(const PairP p) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -95,8 +67,8 @@ __global__ __launch_bounds__(IP_THREADS) void conv3x3_pair_kernel(const PairP p)
     const int tiles = (N + 31) >> 5;
     const bool two = tile0 + 1 < tiles;
     const uint4* wt = wf + (long long)tile0 * (9 * KC) * 64;
-    if (two) pair_taps<2>(wt, smem, off, acc, KC, lane);
-    else pair_taps<1>(wt, smem, off, acc, KC, lane);
+    if (two) flat_taps9<2>(wt, smem, off, acc, KC, lane);
+    else flat_taps9<1>(wt, smem, off, acc, KC, lane);
     if (m >= p.M) return;
 #pragma unroll
     for (int j = 0; j < 2; ++j) {

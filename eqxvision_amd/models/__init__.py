@@ -56,6 +56,16 @@ from .classification.shufflenetv2 import (
 )
 from .classification.squeezenet import SqueezeNet, squeezenet1_0, squeezenet1_1
 from .classification.googlenet import BasicConv2d, GoogLeNet, InceptionAux, _Inception, googlenet
+from .classification.densenet import (
+    DenseNet,
+    _DenseBlock,
+    _DenseLayer,
+    _Transition,
+    densenet121,
+    densenet161,
+    densenet169,
+    densenet201,
+)
 from .segmentation.deeplabv3 import ASPP, DeepLabHead, DeepLabV3, deeplabv3
 from .segmentation.fcn import FCN, FCNHead, fcn
 from .segmentation.lraspp import LRASPP, LRASPPHead, lraspp_mobilenet_v3_large

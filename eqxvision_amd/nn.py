@@ -292,6 +292,26 @@ class MaxPool2d(Module):
         return ops.maxpool2d(x, self.kernel_size, self.stride, self.padding)
 
 
+class AvgPool2d(Module):
+    """eqx.nn.AvgPool2d(kernel_size, stride): floor-mode output size, no padding (densenet.py:128)."""
+
+    kernel_size: Tuple[int, int]
+    stride: Tuple[int, int]
+
+    def __init__(self, kernel_size, stride=1, padding=0, use_ceil=False, **kwargs):
+        if _pair(padding) != (0, 0) or use_ceil:
+            raise NotImplementedError("AvgPool2d with padding or use_ceil (the reference never builds one)")
+        self.kernel_size = _pair(kernel_size)
+        self.stride = _pair(stride)
+
+    def output_size(self, H: int, W: int) -> Tuple[int, int]:
+        return tuple((size - k) // s + 1 for size, k, s in zip((H, W), self.kernel_size, self.stride))
+
+    @boundary
+    def __call__(self, x, *, key=None):
+        return ops.avgpool2d(x, self.kernel_size, self.stride)
+
+
 class AdaptiveAvgPool2d(Module):
     target_shape: Tuple[int, int]
 

@@ -1310,6 +1310,19 @@ def maxpool2d_ceil(x: Act, pool) -> Act:
     return Act(y, "map", x.batched)
 
 
+def avgpool2d(x: Act, kernel_size, stride) -> Act:
+    """nn.AvgPool2d: floor-mode output size, no padding (mv_avgpool2d_nhwc_fwd)."""
+    x = as_map(x)
+    B, H, W, C = x.t.shape
+    kh, kw = _pair(kernel_size)
+    sh, sw = _pair(stride)
+    if H < kh or W < kw:
+        raise ValueError(f"avgpool2d: a {kh} x {kw} window on a {H} x {W} map")
+    y = empty((B, (H - kh) // sh + 1, (W - kw) // sw + 1, C), x.t.dtype)
+    _lib.call("mv_avgpool2d_nhwc_fwd", _ptr(x.t), _ptr(y), B, H, W, C, kh, kw, sh, sw, x.dt, stream_ptr())
+    return Act(y, "map", x.batched)
+
+
 def adaptive_avgpool2d(x: Act, target, out_fp32: bool = False) -> Act:
     x = as_map(x)
     B, H, W, C = x.t.shape
@@ -2302,6 +2315,186 @@ def inception(x: Act, mod) -> Act:
     (w3, s3, h3), (w5, s5, h5) = hit["w3"], hit["w5"]
     _lib.call("mv_conv3x3_pair_fwd", _ptr(t), lt, 0, c3r, c3r, c5p, _ptr(w3), _ptr(s3), _ptr(h3), _ptr(w5), _ptr(s5), _ptr(h5), _ptr(y), Ct,
               c1, c3, c1 + c3, c5, B, H, W, BF, BF, st)
+    return Act(y, "map", x.batched)
+
+
+# ------------------------------------------------------------------ DenseNet dense blocks and transitions (preact1x1.hip, conv3x3_slice.hip)
+def _bn_act(x: Act, bn, lam) -> Act:
+    from .nn import act_name
+    a = act_name(getattr(lam, "fn", None))
+    return batchnorm(x, bn, a) if a is not None else lam(batchnorm(x, bn))
+
+
+def dense_layer_literal(feats, layer, key=None) -> Act:
+    """The reference's dense layer (densenet.py:55-67) on the list of earlier features: concatenate, BatchNorm + ReLU, 1x1, BatchNorm
+    + ReLU (folded behind the 1x1 in inference: the ordinary fused convolution), 3x3, Dropout."""
+    from .nn import act_name, dropout_live
+    cat = as_map(feats[0]) if len(feats) == 1 else concat_channels(feats)
+    a = _bn_act(cat, layer.norm1, layer.relu)
+    if act_name(getattr(layer.relu, "fn", None)) == "relu":
+        t = conv2d(a, layer.conv1, layer.norm2, "relu")
+    else:
+        t = layer.relu(conv2d(a, layer.conv1, layer.norm2))
+    new = conv2d(t, layer.conv2)
+    if dropout_live(layer.dropout):
+        if key is None:
+            raise RuntimeError("Dropout requires a key when running in non-deterministic mode.")
+        new = layer.dropout(new, key=key)
+    return new
+
+
+def dense_block_literal(x: Act, block, key=None) -> Act:
+    """The reference's block (densenet.py:97-103): every layer sees the concatenation of everything before it; the block's key is
+    split over its layers and a layer's Dropout draws from its key as given."""
+    from .nn import dropout_live
+    from . import random as jr
+    feats = [as_map(x)]
+    n = len(block.layers)
+    live = any(dropout_live(getattr(l, "dropout", None)) for l in block.layers)
+    keys = jr.split(_batched_keys(key, feats[0].t.shape[0]), n) if live and key is not None else [None] * n
+    for i, layer in enumerate(block.layers):
+        feats.append(dense_layer_literal(feats, layer, keys[i]))
+    return concat_channels(feats)
+
+
+def _transition_parts(trans):
+    """(BatchNorm, relu Lambda, 1x1 convolution, pool) of the reference's transition, else None."""
+    from .nn import AvgPool2d, BatchNorm, Conv2d, Lambda, Sequential
+    seq = getattr(trans, "layers", None)
+    if not (isinstance(seq, Sequential) and len(seq.layers) == 4):
+        return None
+    bn, lam, conv, pool = seq.layers
+    if not (type(bn) is BatchNorm and isinstance(lam, Lambda) and type(conv) is Conv2d and type(pool) is AvgPool2d):
+        return None
+    return bn, lam, conv, pool
+
+
+def dense_transition_literal(x: Act, trans, key=None) -> Act:
+    """The reference's transition (densenet.py:116-133): BatchNorm + ReLU, the 1x1 convolution, the 2 x 2 average."""
+    parts = _transition_parts(trans)
+    if parts is None:
+        return trans.layers(as_map(x), key=key)
+    bn, lam, conv, pool = parts
+    return pool(conv2d(_bn_act(as_map(x), bn, lam), conv))
+
+
+def _plain_conv(c, k: int) -> bool:
+    one = (1, 1)
+    return (c.kernel_size == (k, k) and c.padding == (k // 2, k // 2) and c.stride == one and c.dilation == one and c.groups == 1
+            and c.bias is None)
+
+
+# (C0, layers, growth, H) of blocks kept on the composition because the two-launch layers measured slower there (DESIGN.md 3.8); the
+# switch "dense_always" overrides it for measurements
+DENSE_LITERAL_SHAPES = frozenset()
+
+
+def dense_block_plan(block, C0: int, H: int, W: int):
+    """(mid, growth, total channels) when `block` is the reference's structure on C0 input channels, in bf16 inference, and both
+    kernels have every layer's shape -- the block then runs as two launches per layer in one buffer; else None (the composition)."""
+    from .nn import BatchNorm, Conv2d, Lambda, act_name, dropout_live
+    layers = getattr(block, "layers", None)
+    if compute_dtype() != "bf16" or not isinstance(layers, (list, tuple)) or not layers:
+        return None
+    mid, g = layers[0].conv1.out_channels if hasattr(layers[0], "conv1") else 0, 0
+    for i, l in enumerate(layers):
+        if not all(hasattr(l, f) for f in ("norm1", "relu", "conv1", "norm2", "conv2", "dropout")):
+            return None
+        if not (type(l.norm1) is BatchNorm and type(l.norm2) is BatchNorm and type(l.conv1) is Conv2d and type(l.conv2) is Conv2d
+                and isinstance(l.relu, Lambda) and act_name(l.relu.fn) == "relu"):
+            return None
+        if _bn_training(l.norm1) or _bn_training(l.norm2) or dropout_live(l.dropout):
+            return None
+        g = g or l.conv2.out_channels
+        if not (_plain_conv(l.conv1, 1) and _plain_conv(l.conv2, 3) and l.conv1.in_channels == C0 + i * g == l.norm1.input_size
+                and l.conv1.out_channels == mid == l.conv2.in_channels == l.norm2.input_size and l.conv2.out_channels == g):
+            return None
+    Ct = C0 + len(layers) * g
+    lib, BF = _lib.load(), _lib.BF16
+    if not lib.mv_conv3x3_slice_supported(mid, g, H, W, BF, BF):
+        return None
+    if not all(lib.mv_preact_conv1x1_supported(C0 + i * g, mid, Ct, mid, 0, 1, BF, BF) for i in range(len(layers))):
+        return None
+    if (C0, len(layers), g, H) in DENSE_LITERAL_SHAPES and H == W and not _lib.get_flag("dense_always"):
+        return None
+    return mid, g, Ct
+
+
+def _dense_layer_operands(layer):
+    cache = layer._cache()
+    key = ("dense_layer", _bn_id(layer.norm1), _bn_id(layer.norm2))
+    hit = cache.get(key)
+    if hit is None:
+        s1, h1 = bn_fold(layer.norm1)
+        s2, h2 = bn_fold(layer.norm2)
+        w1 = np.asarray(layer.conv1.weight, np.float32)
+        d32 = lambda a: _dev(a, torch.float32)
+        hit = (d32(s1), d32(h1), _dev(w1.reshape(w1.shape[0], w1.shape[1]), torch.bfloat16), d32(s2), d32(h2),
+               _dev(inception_fragments(np.asarray(layer.conv2.weight, np.float32)), torch.bfloat16))
+        cache[key] = hit
+    return hit
+
+
+def dense_block(x: Act, block, filled: Optional[int] = None, key=None) -> Act:
+    """One dense block.  bf16 inference where the two kernels have the shapes: ONE [B, H, W, C0 + L * growth] buffer with the input in
+    channels [0, C0); per layer mv_preact_conv1x1_fwd (BatchNorm 1 + ReLU on the way into LDS, the 1x1, BatchNorm 2 + ReLU; buffer
+    channels [0, C_i) -> the scratch map t, reused by every layer) and mv_conv3x3_slice_fwd (t -> buffer channels [C_i, C_i + growth)):
+    two launches per layer, nothing is concatenated.  `filled` = C0 says that `x` already IS that buffer with its first C0 channels
+    written (ops.dense_transition with `next_ld`), so there is nothing to place; otherwise one mv_copy_rows places the input.
+    Everything else (fp32 mode, training-mode BatchNorm, live Dropout, the switches "no_dense_fused" / "force_generic", other
+    structures or shapes): the literal composition."""
+    x = as_map(x)
+    B, H, W, Cx = x.t.shape
+    C0 = Cx if filled is None else int(filled)
+    plan = dense_block_plan(block, C0, H, W) if x.t.dtype == torch.bfloat16 else None
+    if plan is None or (filled is not None and plan[2] != Cx):
+        return dense_block_literal(x if filled is None else _channel_slice(x, 0, C0), block, key)
+    mid, g, Ct = plan
+    BF, st, es = _lib.BF16, stream_ptr(), 2
+    if filled is None:
+        buf = empty((B, H, W, Ct), torch.bfloat16)
+        _lib.call("mv_copy_rows", _ptr(x.t), _ptr(buf), B * H * W, C0 * es, C0 * es, Ct * es, st)
+    else:
+        buf = x.t
+    t = empty((B, H, W, mid), torch.bfloat16)
+    for i, layer in enumerate(block.layers):
+        s1, h1, w1, s2, h2, wf = _dense_layer_operands(layer)
+        Ci = C0 + i * g
+        _lib.call("mv_preact_conv1x1_fwd", _ptr(buf), Ct, _ptr(s1), _ptr(h1), _ptr(w1), _ptr(s2), _ptr(h2), _ptr(t), mid, 0, B, H, W, Ci,
+                  mid, 1, BF, BF, st)
+        _lib.call("mv_conv3x3_slice_fwd", _ptr(t), mid, mid, _ptr(wf), _ptr(buf), Ct, Ci, g, B, H, W, BF, BF, st)
+    return Act(buf, "map", x.batched)
+
+
+def dense_transition(x: Act, trans, next_ld: int = 0, key=None) -> Act:
+    """One transition.  bf16 inference: ONE mv_preact_conv1x1_fwd with the 2 x 2 average in front of the product (exact: both are
+    linear).  With `next_ld` > 0 the result is a [B, H/2, W/2, next_ld] map whose channels [0, C/2) are written -- the next block's
+    buffer, handed to ops.dense_block with `filled` = C/2; the caller tells the two results apart by the channel count.  Otherwise,
+    and wherever the kernel does not serve, the dense [.., C/2] map (the literal composition where the kernel does not serve)."""
+    from .nn import act_name
+    x = as_map(x)
+    B, H, W, C = x.t.shape
+    parts = _transition_parts(trans)
+    ok = parts is not None and compute_dtype() == "bf16" and x.t.dtype == torch.bfloat16
+    if ok:
+        bn, lam, conv, pool = parts
+        N = conv.out_channels
+        ld = int(next_ld) if next_ld else N
+        ok = (act_name(lam.fn) == "relu" and not _bn_training(bn) and _plain_conv(conv, 1) and conv.in_channels == C == bn.input_size
+              and pool.kernel_size == (2, 2) and pool.stride == (2, 2) and H >= 2 and W >= 2 and ld >= N
+              and bool(_lib.load().mv_preact_conv1x1_supported(C, N, C, ld, 0, 2, _lib.BF16, _lib.BF16)))
+    if not ok:
+        return dense_transition_literal(x, trans, key)
+    cache = trans._cache()
+    ck = ("dense_transition", _bn_id(bn))
+    hit = cache.get(ck)
+    if hit is None:
+        s1, h1 = bn_fold(bn)
+        hit = (_dev(s1, torch.float32), _dev(h1, torch.float32), _dev(np.asarray(conv.weight, np.float32).reshape(N, C), torch.bfloat16))
+        cache[ck] = hit
+    y = empty((B, H // 2, W // 2, ld), torch.bfloat16)
+    _lib.call("mv_preact_conv1x1_fwd", _ptr(x.t), C, _ptr(hit[0]), _ptr(hit[1]), _ptr(hit[2]), None, None, _ptr(y), ld, 0, B, H, W, C, N, 2,
+              _lib.BF16, _lib.BF16, stream_ptr())
     return Act(y, "map", x.batched)
 
 

@@ -49,6 +49,8 @@ _STEMS = {
     "shufflenetv2_x0.5": "shufflenetv2_x0.5-f707e7126e", "shufflenetv2_x1.0": "shufflenetv2_x1-5666bf0f80",
     "squeezenet1_0": "squeezenet1_0-b66bff10", "squeezenet1_1": "squeezenet1_1-b8a52dc0",
     "googlenet": "googlenet-1378be20",
+    "densenet121": "densenet121-a639ec97", "densenet169": "densenet169-b2777c0a", "densenet201": "densenet201-c1103571",
+    "densenet161": "densenet161-8d451a50",
     "swin_t": "swin_t-704ceda3", "swin_s": "swin_s-5e29d889", "sim_b": "swin_b-68c6b09e",
 }
 SEGMENTATION_URLS = {      # reference utils.py:20-24

@@ -427,6 +427,42 @@ int mv_conv3x3_pair_fwd(const void* t, int ldt, int ct0, int S0, int ct1, int S1
                         const float* shift0, const void* w1_frag, const float* scale1, const float* shift1, void* y, int ldy, int cy0,
                         int N0, int cy1, int N1, int B, int H, int W, int x_dtype, int y_dtype, mv_stream_t stream);
 
+/* DenseNet (densenet.py:55-67, 106-133): the pre-activated pointwise convolution -- BatchNorm + ReLU IN FRONT of a 1x1 convolution, which
+ * no producer can fold because every consumer of a feature has its own statistics -- with an optional 2 x 2 average in front of the
+ * product and a strided source and destination:
+ *   a[mo, c] = bf16( mean over the pool x pool window of  relu(s1[c] * x[pix * ldx + c] + h1[c]) )      c < C, pool in {1, 2}
+ *   v[mo, n] = sum_c w[n][c] * a[mo, c]                                                                  fp32 accumulation
+ *   y[mo * ldy + cy + n] = relu(s2[n] * v + h2[n]),  or v when s2 == h2 == NULL
+ * x NHWC bf16 [B][H][W] with rows of ldx >= C elements; ONLY channels [0, C) of a row are read (the rest of a dense block's buffer
+ * is not written yet).  pool = 2: the output map is floor(H/2) x floor(W/2) (AvgPool2d(2, 2); an odd last row / column is dropped), the
+ * mean is taken in fp32 after affine + ReLU and before the rounding to bf16; averaging in front of the convolution instead of behind
+ * it is exact algebra (both are linear) and divides the product by four.  H < pool or W < pool: MV_E_INVALID.  w bf16 [N][C], s1 / h1
+ * fp32 [C], s2 / h2 fp32 [N] or both NULL.  C, N, ldx, ldy and cy are multiples of 16; bf16 only; not in place.  The dense-layer
+ * bottleneck is pool = 1 with BatchNorm 2 folded into s2 / h2 and a dense y; a transition is pool = 2 with the identity, y = channels
+ * [0, N) of the next block's buffer.  Flags "no_dense_fused" / "force_generic": _supported returns 0 (the caller composes
+ * mv_channel_affine_fwd, mv_conv2d_nhwc_fwd, mv_copy_rows, mv_avgpool2d_nhwc_fwd). */
+int mv_preact_conv1x1_supported(int C, int N, int ldx, int ldy, int cy, int pool, int x_dtype, int y_dtype);
+int mv_preact_conv1x1_fwd(const void* x, int ldx, const float* s1, const float* h1, const void* w, const float* s2, const float* h2,
+                          void* y, int ldy, int cy, int B, int H, int W, int C, int N, int pool, int x_dtype, int y_dtype,
+                          mv_stream_t stream);
+
+/* DenseNet dense layer, conv2 (densenet.py:44-52): a plain 3x3 convolution, padding 1, stride 1, into a channel slice -- no affine
+ * step, no ReLU, negative values survive:
+ *   y[m * ldy + cy + n] = sum_{r,s<3, c<S} W[n][c][r][s] t[b, h + r - 1, w + s - 1, c]       n < N, m = b*H*W + h*W + w
+ * t NHWC bf16 with rows of ldt >= S elements, y NHWC bf16 with rows of ldy; not in place; fp32 accumulation.  w_frag: the A-fragment
+ * order of mv_conv3x3_pair_fwd (eqxvision_amd/ops.py: inception_fragments; N = 48 pads to 64 rows and the upper half tile is never
+ * stored).  S, N, the strides and cy are multiples of 16; (131 + 2 W) * (2 S + 16) <= 160 KiB; bf16 only.  A workgroup owns 128 pixels,
+ * or 64 below 131072 pixels (flags "dense3x3_m64" / "dense3x3_m128": that tile whatever the count).  Flags "no_dense_fused" /
+ * "force_generic": _supported returns 0. */
+int mv_conv3x3_slice_supported(int S, int N, int H, int W, int x_dtype, int y_dtype);
+int mv_conv3x3_slice_fwd(const void* t, int ldt, int S, const void* w_frag, void* y, int ldy, int cy, int N, int B, int H, int W,
+                         int x_dtype, int y_dtype, mv_stream_t stream);
+
+/* eqx.nn.AvgPool2d(kernel_size, stride) (densenet.py:128): floor-mode output size ((H - kh) / sh + 1), no padding, every window
+ * full; NHWC, MV_F32 or MV_BF16, fp32 sums; not in place.  H < kh or W < kw: MV_E_INVALID. */
+int mv_avgpool2d_nhwc_fwd(const void* x, void* y, int N, int H, int W, int C, int kh, int kw, int sh, int sw, int dtype,
+                          mv_stream_t stream);
+
 /* y[r, j] = x[r, idx[j]] over the channel axis of rows x C_in -> rows x C_out (the literal channel shuffle / split of ShuffleNetV2,
  * shufflenetv2.py:16-23, where the folded layout is not used).  idx: C_out device int32 (an index outside 0 .. C_in-1 gives 0);
  * MV_F32 or MV_BF16, any channel counts, not in place.  A bit copy. */
