@@ -1,6 +1,10 @@
 // Pieces shared by the concat-free 3x3 kernels (fire_expand.hip, inception_pair.hip, conv3x3_slice.hip) and, for the epilogue and the
-// tile-row permutation, conv1x1_split.hip and preact1x1.hip.  What a kernel keeps for itself is the formula it computes and its grid;
-// the two kernels that give a workgroup ONE pair of output tiles (inception_pair.hip, conv3x3_slice.hip) share their k-loop too.
+// tile-row permutation, the 128 x 128 pointwise tile of pw128.h (conv1x1_split.hip, preact1x1.hip).  What a kernel keeps for itself is
+// the formula it computes and its grid; the two kernels that give a workgroup ONE pair of output tiles (inception_pair.hip,
+// conv3x3_slice.hip) share their k-loop too.  The few lines that string stage / offsets / k-loop / store together stay in each of
+// the two: moved into one function template here (thread count as the parameter, a store functor; also with the store called
+// directly, with tid and m0 passed in, with the functor by value or always_inline), conv3x3_pair_kernel took 74 VGPRs for 72 every
+// time, while conv3x3_slice_kernel<2> / <4> kept their 54 and the parent's text against the same header its 72.
 //
 // The flat range.  m is the FLATTENED pixel index b * H * W + h * W + w of an NHWC bf16 tensor; a workgroup owns TM consecutive pixels
 // from m0 on, whatever image they belong to (small maps at batch size still fill the machine).  It stages, once, slots

@@ -13,25 +13,16 @@
 // pixels.  The mean is taken in fp32 after affine + ReLU and before the one rounding to bf16.
 //
 // Rows of x are ldx >= C elements apart and only channels [0, C) of a row are ever read: the rest of a dense block's buffer is memory
-// that a later layer has not written yet.  The tile is conv1x1_split.hip's: a 256-thread workgroup owns 128 output pixels x 128 output
-// channels, four waves as a 2 x 2 grid of 64 x 64 sub-tiles on v_mfma_f32_32x32x16_bf16, weights as the A operand, 64-channel chunks
-// of both operands in LDS (rows of 128 + 16 bytes), double buffered, the next chunk's global loads in flight in registers while the
-// matrix cores work -- the affine step, the ReLU, the mean and the rounding happen when those registers are written to LDS, behind
-// the chunk's MFMAs.  Reduction channels past C and rows past M must be ZERO AFTER the pre-activation, and relu(0 * s + h) is not
-// zero: they are masked behind the affine step (zeros are written to LDS) and are never loaded.  The lane reads weight row
-// mfma32_tile_row(lane % 32), so its 16 accumulator registers are 16 consecutive output channels (flat3x3.h: store16_relu /
-// store16_plain).
-#include "flat3x3.h"
+// that a later layer has not written yet.  The tile, the chunk loop and the epilogue walk are pw128.h's; a B-operand row is made of
+// P x P source pixels held in registers while the matrix cores work, and the affine step, the ReLU, the mean and the rounding happen
+// when those registers are written to LDS, behind the chunk's MFMAs.  Reduction channels past C and rows past M must be ZERO AFTER
+// the pre-activation, and relu(0 * s + h) is not zero: they are masked behind the affine step (zeros are written to LDS) and are
+// never loaded.
+#include "pw128.h"
 
 namespace mv {
 
 namespace {
-
-constexpr int PA_THREADS = 256;
-constexpr int PA_TM = 128, PA_TN = 128, PA_KC = 64;
-constexpr int PA_ROW_B = 2 * PA_KC + 16;
-constexpr int PA_BUF_B = (PA_TM + PA_TN) * PA_ROW_B;
-constexpr int PA_LDS = 2 * PA_BUF_B;
 
 struct PreactP {
     const bf16_t* x;       // [B][H][W] rows of ldx
@@ -54,40 +45,35 @@ __device__ __forceinline__ void preact_acc8(float (&a)[8], const uint4 v, const 
     }
 }
 
+// the B operand: a pixel row is made of the P x P source pixels src[j] + {0, 1} + {0, W}, pre-activated on their way into LDS
 template <int P>
-__global__ __launch_bounds__(PA_THREADS) void preact1x1_kernel(const PreactP p) {
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const long long m0 = (long long)blockIdx.x * PA_TM;
-    const int nb0 = blockIdx.y * PA_TN;
-    const int wm = wave & 1, wn = wave >> 1;
-    const int hh = lane >> 5, pl = lane & 31;
-    const int chan = mfma32_tile_row(pl);
-
-    // staging: the thread moves 16-byte piece tid % 8 of rows tid / 8 + 32 j of both operands; a pixel row of the B operand is made
-    // of the P x P source pixels src[j] + {0, 1} + {0, W}
-    const int sr = tid >> 3, sc8 = tid & 7;
+struct PreactRows {
+    const PreactP& p;
+    const PwStageMap map;
     long long src[4];
     bool row_ok[4];
+    uint4 xr[4][P * P];
+    float sv[8], hv[8];
+    bool kok;
+    __device__ __forceinline__ void init() {
+        kok = false;
 #pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        const long long m = m0 + sr + 32 * j;
-        row_ok[j] = m < p.M;
-        if (P == 1) {
-            src[j] = m;
-        } else {
-            const long long per = (long long)p.Ho * p.Wo;
-            const long long b = m / per;
-            const int rem = (int)(m - b * per);
-            const int ho = rem / p.Wo, wo = rem - ho * p.Wo;
-            src[j] = (b * p.H + 2 * ho) * p.W + 2 * wo;
+        for (int j = 0; j < 4; ++j) {
+            const long long m = pw128_m0() + map.sr + 32 * j;
+            row_ok[j] = m < p.M;
+            if (P == 1) {
+                src[j] = m;
+            } else {
+                const long long per = (long long)p.Ho * p.Wo;
+                const long long b = m / per;
+                const int rem = (int)(m - b * per);
+                const int ho = rem / p.Wo, wo = rem - ho * p.Wo;
+                src[j] = (b * p.H + 2 * ho) * p.W + 2 * wo;
+            }
         }
     }
-    uint4 xr[4][P * P], wr[4];
-    float sv[8], hv[8];
-    bool kok = false;
-    auto fetch = [&](const int k0) {
-        const int k = k0 + sc8 * 8;
+    __device__ __forceinline__ void fetch(const int k0) {
+        const int k = k0 + map.sc8 * 8;
         kok = k < p.C;
         if (kok) {
             const float4 a = *(const float4*)(p.s1 + k), b = *(const float4*)(p.s1 + k + 4);
@@ -97,17 +83,14 @@ __global__ __launch_bounds__(PA_THREADS) void preact1x1_kernel(const PreactP p) 
         }
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
-            const int n = nb0 + sr + 32 * j;
-            wr[j] = make_uint4(0, 0, 0, 0);
-            if (kok && n < p.N) wr[j] = *(const uint4*)(p.w + (long long)n * p.C + k);
             if (kok && row_ok[j]) {
 #pragma unroll
                 for (int e = 0; e < P * P; ++e)
                     xr[j][e] = *(const uint4*)(p.x + (src[j] + (e >> 1) * p.W + (e & 1)) * p.ldx + k);
             }
         }
-    };
-    auto stash = [&](char* buf) {
+    }
+    __device__ __forceinline__ void stash(char* buf) const {
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
             uint4 o = make_uint4(0, 0, 0, 0);                       // past C / past M: zero AFTER the pre-activation
@@ -123,62 +106,23 @@ __global__ __launch_bounds__(PA_THREADS) void preact1x1_kernel(const PreactP p) 
                 }
                 o = make_uint4(pack_bf2(a[0], a[1]), pack_bf2(a[2], a[3]), pack_bf2(a[4], a[5]), pack_bf2(a[6], a[7]));
             }
-            *(uint4*)(buf + (sr + 32 * j) * PA_ROW_B + sc8 * 16) = o;
-            *(uint4*)(buf + (PA_TM + sr + 32 * j) * PA_ROW_B + sc8 * 16) = wr[j];
-        }
-    };
-
-    f32x16 acc[2][2];                                               // [channel tile j][pixel tile q]
-#pragma unroll
-    for (int j = 0; j < 2; ++j)
-#pragma unroll
-        for (int q = 0; q < 2; ++q)
-#pragma unroll
-            for (int e = 0; e < 16; ++e) acc[j][q][e] = 0.f;
-
-    const bool wave_live = nb0 + wn * 64 < p.N;                     // a wave whose 64 columns are all past N only stages
-    const int a_off = (PA_TM + wn * 64 + chan) * PA_ROW_B + hh * 16;
-    const int b_off = (wm * 64 + pl) * PA_ROW_B + hh * 16;
-    const int nchunks = (p.C + PA_KC - 1) / PA_KC;
-    fetch(0);
-    stash(smem);
-    __syncthreads();
-    for (int ch = 0; ch < nchunks; ++ch) {
-        const char* cur = smem + (ch & 1) * PA_BUF_B;
-        const bool more = ch + 1 < nchunks;
-        if (more) fetch((ch + 1) * PA_KC);
-        if (wave_live) {
-            const int left = (p.C - ch * PA_KC) >> 4;
-            const int nks = left < 4 ? left : 4;
-            for (int ks = 0; ks < nks; ++ks) {
-                const bf16x8 a0 = __builtin_bit_cast(bf16x8, *(const uint4*)(cur + a_off + ks * 32));
-                const bf16x8 a1 = __builtin_bit_cast(bf16x8, *(const uint4*)(cur + a_off + 32 * PA_ROW_B + ks * 32));
-                const bf16x8 b0 = __builtin_bit_cast(bf16x8, *(const uint4*)(cur + b_off + ks * 32));
-                const bf16x8 b1 = __builtin_bit_cast(bf16x8, *(const uint4*)(cur + b_off + 32 * PA_ROW_B + ks * 32));
-                acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a0, b0, acc[0][0], 0, 0, 0);
-                acc[1][0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1, b0, acc[1][0], 0, 0, 0);
-                acc[0][1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a0, b1, acc[0][1], 0, 0, 0);
-                acc[1][1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1, b1, acc[1][1], 0, 0, 0);
-            }
-        }
-        if (more) stash(smem + ((ch + 1) & 1) * PA_BUF_B);          // the other buffer: every wave left it before the last barrier
-        __syncthreads();
-    }
-
-    if (!wave_live) return;
-#pragma unroll
-    for (int j = 0; j < 2; ++j) {
-        const int n = nb0 + wn * 64 + j * 32 + 16 * hh;             // first of the lane's 16 columns
-        if (n >= p.N) continue;
-#pragma unroll
-        for (int q = 0; q < 2; ++q) {
-            const long long m = m0 + wm * 64 + q * 32 + pl;
-            if (m >= p.M) continue;
-            bf16_t* dst = p.y + m * p.ldy + p.cy + n;
-            if (p.s2) store16_relu(acc[j][q], p.s2 + n, p.h2 + n, dst);
-            else store16_plain(acc[j][q], dst);
+            map.put(buf, 0, j, o);
         }
     }
+};
+
+template <int P>
+__global__ __launch_bounds__(PW_THREADS) void preact1x1_kernel(const PreactP p) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    f32x16 acc[2][2];
+    PreactRows<P> rows{p};
+    rows.init();
+    pw128_product(acc, smem, rows, p.w, p.C, p.N);
+    pw128_epilogue(acc, p.M, p.N, [&](const f32x16& a, const long long m, const int n) {
+        bf16_t* dst = p.y + m * p.ldy + p.cy + n;
+        if (p.s2) store16_relu(a, p.s2 + n, p.h2 + n, dst);
+        else store16_plain(a, dst);
+    });
 }
 
 }  // namespace
@@ -218,18 +162,18 @@ int mv_preact_conv1x1_fwd(const void* x, int ldx, const float* s1, const float* 
     p.ldx = ldx; p.ldy = ldy; p.C = C; p.N = N; p.cy = cy; p.H = H; p.W = W; p.Ho = H / pool; p.Wo = W / pool;
     p.M = (long long)B * p.Ho * p.Wo;
     MV_CHECK_ARG((long long)B * H * W < (1ll << 31) - 8192, "mv_preact_conv1x1_fwd: %lld pixels", (long long)B * H * W);
-    const dim3 grid((unsigned)((p.M + PA_TM - 1) / PA_TM), (unsigned)((N + PA_TN - 1) / PA_TN));
+    const dim3 grid((unsigned)((p.M + PW_TM - 1) / PW_TM), (unsigned)((N + PW_TN - 1) / PW_TN));
     hipStream_t st = (hipStream_t)stream_;
     if (pool == 1) {
         static LdsAttrSite site;
-        MV_HIP(site.ensure((const void*)preact1x1_kernel<1>, PA_LDS));
+        MV_HIP(site.ensure((const void*)preact1x1_kernel<1>, PW_LDS));
         set_kernel_name(s2 ? "preact1x1_relu" : "preact1x1");
-        hipLaunchKernelGGL(preact1x1_kernel<1>, grid, dim3(PA_THREADS), PA_LDS, st, p);
+        hipLaunchKernelGGL(preact1x1_kernel<1>, grid, dim3(PW_THREADS), PW_LDS, st, p);
     } else {
         static LdsAttrSite site;
-        MV_HIP(site.ensure((const void*)preact1x1_kernel<2>, PA_LDS));
+        MV_HIP(site.ensure((const void*)preact1x1_kernel<2>, PW_LDS));
         set_kernel_name(s2 ? "preact1x1_pool2_relu" : "preact1x1_pool2");
-        hipLaunchKernelGGL(preact1x1_kernel<2>, grid, dim3(PA_THREADS), PA_LDS, st, p);
+        hipLaunchKernelGGL(preact1x1_kernel<2>, grid, dim3(PW_THREADS), PW_LDS, st, p);
     }
     MV_LAUNCH_CHECK();
     return MV_OK;

@@ -15,12 +15,11 @@ import torch.nn.functional as Fn
 import eqxvision_amd as eqv
 from oracle import state as S
 from tests import _densenet_ref as R
+from tests._slices import _check_slice, _dest, _p, _read, _stream
 
 pytestmark = pytest.mark.gpu
 
 BF16_TOL, FP32_TOL = 1e-2, 1e-3
-SENTINEL = -7.0
-GUARD = 64
 MAPS_1X1 = ((1, 1, 2), (5, 7, 3), (14, 14, 1), (7, 7, 5))              # (H, W, B): one pixel; not a tile multiple; more than one tile
 MAPS_POOL = ((4, 4, 3), (5, 7, 2), (2, 2, 1), (15, 14, 2))              # 5 x 7 -> 2 x 3 and 15 x 14 -> 7 x 7: an odd row / column is dropped
 MAPS_3X3 = ((1, 1, 2), (5, 7, 3), (7, 7, 4), (14, 14, 1), (28, 28, 1))  # tests/test_googlenet_gpu.py
@@ -34,40 +33,6 @@ def _need_gpu():
     _lib.check_device_status()
     yield
     _lib.check_device_status()
-
-
-def _p(t):
-    return None if t is None else t.data_ptr()
-
-
-def _stream():
-    return torch.cuda.current_stream().cuda_stream
-
-
-def _dest(M, ld):
-    """A sentinel-filled destination of M rows of ld bf16 with a guard behind it."""
-    return torch.full((M * ld + GUARD,), SENTINEL, dtype=torch.bfloat16, device="cuda")
-
-
-def _read(buf, M, ld):
-    host = buf.float().cpu()
-    return host[:M * ld].reshape(M, ld), host[M * ld:]
-
-
-def _check_slice(y, guard, c, ref, bound, tag, exact=False):
-    """Inside [c, c + n) the reference to `bound` (or bit-equal); outside the sentinel; the guard intact; no NaN anywhere."""
-    n = ref.shape[1]
-    assert not bool(torch.isnan(y).any()) and not bool(torch.isnan(guard).any()), (tag, "NaN")
-    assert bool((guard == SENTINEL).all()), tag
-    outside = torch.cat([y[:, :c], y[:, c + n:]], 1)
-    assert bool((outside == SENTINEL).all()), (tag, "written outside the slice")
-    if exact:
-        wrong = y[:, c:c + n].double() != ref
-        assert not bool(wrong.any()), (tag, int(wrong.sum()), torch.nonzero(wrong)[:8].tolist())
-        return 0.0
-    err = float((y[:, c:c + n].double() - ref).abs().max())
-    assert err <= bound, (tag, err, bound)
-    return err
 
 
 # ------------------------------------------------------------------------------------------------ op level: mv_preact_conv1x1_fwd

@@ -14,12 +14,11 @@ import torch.nn.functional as Fn
 import eqxvision_amd as eqv
 from oracle import state as S
 from tests import _googlenet_ref as R
+from tests._slices import SENTINEL, _check_slice, _dest, _p, _read, _stream
 
 pytestmark = pytest.mark.gpu
 
 BF16_TOL, FP32_TOL = 1e-2, 1e-3
-SENTINEL = -7.0
-GUARD = 64
 MAPS_1X1 = ((1, 1, 2), (5, 7, 3), (14, 14, 1), (7, 7, 5))              # (H, W, B): one pixel; not a tile multiple; more than one tile
 MAPS_3X3 = ((1, 1, 2), (5, 7, 3), (7, 7, 4), (14, 14, 1), (28, 28, 1))  # tiles that cross image borders; a map wider than a tile's halo
 
@@ -32,24 +31,6 @@ def _need_gpu():
     _lib.check_device_status()
     yield
     _lib.check_device_status()
-
-
-def _p(t):
-    return None if t is None else t.data_ptr()
-
-
-def _stream():
-    return torch.cuda.current_stream().cuda_stream
-
-
-def _dest(M, ld):
-    """A sentinel-filled destination of M rows of ld bf16 with a guard behind it."""
-    return torch.full((M * ld + GUARD,), SENTINEL, dtype=torch.bfloat16, device="cuda")
-
-
-def _read(buf, M, ld):
-    host = buf.float().cpu()
-    return host[:M * ld].reshape(M, ld), host[M * ld:]
 
 
 # ------------------------------------------------------------------------------------------------ op level: mv_conv1x1_split_fwd
@@ -76,21 +57,6 @@ def _split_ref(x, w, scale, shift):
     return torch.relu(x.double() @ w.double().T * scale.double() + shift.double())
 
 
-def _check_slices(y, guard, c, ref, bound, tag, exact=False):
-    """Inside [c, c + n) the reference to `bound` (or bit-equal); outside the sentinel; the guard intact."""
-    n = ref.shape[1]
-    assert bool((guard == SENTINEL).all()), tag
-    outside = torch.cat([y[:, :c], y[:, c + n:]], 1)
-    assert bool((outside == SENTINEL).all()), (tag, "written outside the slice")
-    if exact:
-        wrong = y[:, c:c + n].double() != ref
-        assert not bool(wrong.any()), (tag, int(wrong.sum()), torch.nonzero(wrong)[:8].tolist())
-        return 0.0
-    err = float((y[:, c:c + n].double() - ref).abs().max())
-    assert err <= bound, (tag, err, bound)
-    return err
-
-
 @pytest.mark.parametrize("form", ["two", "one"])
 def test_conv1x1_split(form):
     C, N, n0, ld0, c0, ld1, c1 = (48, 48, 16, 64, 16, 48, 0) if form == "two" else (832, 128, 128, 160, 16, 0, 0)
@@ -105,8 +71,8 @@ def test_conv1x1_split(form):
         y0, g0, y1, g1, kern = _launch_split(x, w, scale, shift, n0, ld0, c0, ld1, c1)
         tag = dict(form=form, hw=(H, W), B=B, kernel=kern)
         assert kern == ("conv1x1_split2" if form == "two" else "conv1x1_split1")
-        e0 = _check_slices(y0, g0, c0, ref[:, :n0], bound, tag)
-        e1 = _check_slices(y1, g1, c1, ref[:, n0:], bound, tag) if form == "two" else 0.0
+        e0 = _check_slice(y0, g0, c0, ref[:, :n0], bound, tag)
+        e1 = _check_slice(y1, g1, c1, ref[:, n0:], bound, tag) if form == "two" else 0.0
         print({**tag, "err0": e0, "err1": e1, "bound": bound})
 
 
@@ -123,8 +89,8 @@ def test_conv1x1_split_exact_integers():
     ref = _split_ref(x, w, torch.ones(N), shift)
     assert float(ref.max()) <= 256.0 and bool((ref == ref.round()).all()) and bool((ref == 0).any()) and bool((ref > 0).any())
     y0, g0, y1, g1, kern = _launch_split(x.to(torch.bfloat16), w.to(torch.bfloat16), torch.ones(N), shift, n0, 64, 16, 144, 16)
-    _check_slices(y0, g0, 16, ref[:, :n0], 0.0, kern, exact=True)
-    _check_slices(y1, g1, 16, ref[:, n0:], 0.0, kern, exact=True)
+    _check_slice(y0, g0, 16, ref[:, :n0], 0.0, kern, exact=True)
+    _check_slice(y1, g1, 16, ref[:, n0:], 0.0, kern, exact=True)
 
 
 # ------------------------------------------------------------------------------------------------ op level: mv_conv3x3_pair_fwd

@@ -13,12 +13,11 @@ import torch.nn.functional as Fn
 import eqxvision_amd as eqv
 from oracle import state as S
 from tests import _squeezenet_ref as R
+from tests._slices import GUARD, SENTINEL, _p, _stream
 
 pytestmark = pytest.mark.gpu
 
 BF16_TOL, FP32_TOL = 1e-2, 1e-3
-SENTINEL = -7.0
-GUARD = 64
 MAPS = ((13, 13, 2), (5, 7, 3), (27, 27, 1), (1, 1, 2))     # (H, W, B): a few tiles; every pixel on a border; not a tile multiple; 1 pixel
 
 
@@ -30,14 +29,6 @@ def _need_gpu():
     _lib.check_device_status()
     yield
     _lib.check_device_status()
-
-
-def _p(t):
-    return None if t is None else t.data_ptr()
-
-
-def _stream():
-    return torch.cuda.current_stream().cuda_stream
 
 
 # ------------------------------------------------------------------------------------------------ op level: mv_fire_expand_fwd
