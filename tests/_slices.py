@@ -14,9 +14,9 @@ def _stream():
     return torch.cuda.current_stream().cuda_stream
 
 
-def _dest(M, ld):
-    """A sentinel-filled destination of M rows of ld bf16 with a guard behind it."""
-    return torch.full((M * ld + GUARD,), SENTINEL, dtype=torch.bfloat16, device="cuda")
+def _dest(M, ld, dtype=torch.bfloat16):
+    """A sentinel-filled destination of M rows of ld bf16 (or `dtype`) with a guard behind it."""
+    return torch.full((M * ld + GUARD,), SENTINEL, dtype=dtype, device="cuda")
 
 
 def _read(buf, M, ld):

@@ -29,54 +29,11 @@ import torch
 
 from eqxvision_amd import _lib, ops
 from tests import _strict as S
+from tests._strict_gpu import DT, _dev, _Flags, _host, _need_gpu, _out, _p, _stream  # noqa: F401  (_need_gpu: the module fixture)
 
 pytestmark = pytest.mark.gpu
 
 BF, F32 = _lib.BF16, _lib.F32
-DT = {"bf16": BF, "fp32": F32}
-
-
-@pytest.fixture(scope="module", autouse=True)
-def _need_gpu():
-    assert torch.cuda.is_available(), "gpu tests need an MI355X"
-    _lib.load()
-    _lib.check_device_status()
-    yield
-    _lib.check_device_status()
-
-
-def _stream():
-    return torch.cuda.current_stream().cuda_stream
-
-
-def _p(t):
-    return None if t is None else t.data_ptr()
-
-
-def _dev(a, dtype="bf16"):
-    t = torch.from_numpy(np.ascontiguousarray(a))
-    return (t.to(torch.bfloat16) if dtype == "bf16" else t).cuda()
-
-
-def _host(t):
-    return t.float().cpu().numpy().astype(np.float64)
-
-
-def _out(shape, dtype="bf16", fill=-7.0):
-    return torch.full(shape, fill, dtype=torch.bfloat16 if dtype == "bf16" else torch.float32, device="cuda")
-
-
-class _Flags:
-    def __init__(self, flags):
-        self.flags = [(f.split("=")[0], int(f.split("=")[1]) if "=" in f else 1) for f in flags]
-
-    def __enter__(self):
-        for k, v in self.flags:
-            _lib.set_flag(k, v)
-
-    def __exit__(self, *a):
-        for k, _ in self.flags:
-            _lib.set_flag(k, 0)
 
 
 # ------------------------------------------------------------------------------------------------ operands
