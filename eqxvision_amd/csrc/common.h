@@ -7,6 +7,7 @@
 #include <string.h>
 
 #include "../../include/eqxvision_amd.h"
+#include "route.h"
 
 namespace mv {
 
@@ -85,8 +86,7 @@ void append_kernel_name(const char* suffix);
 int get_flag(const char* name);
 // the scratch the host handed over with mv_set_scratch for the next launch on `stream`: returned (and forgotten) if it holds
 // at least `need` bytes, else nullptr
-constexpr size_t SCRATCH_SYNC_BYTES = 4096;      // head of every scratch offer: split-K arrival words, zero between launches
-void* take_scratch(hipStream_t stream, size_t need);
+void* take_scratch(hipStream_t stream, size_t need);            // (SCRATCH_SYNC_BYTES, the head of every offer: route.h)
 void* peek_scratch(hipStream_t stream, size_t* bytes);
 size_t splitk_scratch_bytes(long long M, long long N, long long kred);       // igemm8.hip
 const void* zero_page(hipStream_t stream);  // >= 4 KiB of device zeros for the current device
@@ -142,24 +142,43 @@ struct LdsAttrSite {
         }                                                                            \
     } while (0)
 
-// dispatch helpers implemented in the kernel translation units
-int igemm_supported(int C, int K, int R, int S, int groups, int in_dtype, int out_dtype);
-int igemm_launch(const void* x, const void* w, const float* scale, const float* shift, const void* residual,
-                 void* y, int N, int H, int W, int C, int K, int R, int S, int sh, int sw, int ph, int pw,
-                 int dh, int dw, int act, int in_dtype, int out_dtype, hipStream_t stream);
+// The convolution geometry of the igemm parameter structs (IgemmP, Igemm2P): Ho, Wo, M, strides, pads, dilations, the zero page
+// that out-of-image taps read, and the 31-bit range checks (pixel_index32: the kernel indexes INPUT pixels with 32 bits too).
+template <class P> int fill_geometry(P& p, const ConvShape& s, const char* who, bool pixel_index32, hipStream_t st) {
+    p.zero = (const bf16_t*)zero_page(st);
+    if (!p.zero) {
+        set_error("%s: zero page allocation failed", who);
+        return MV_E_OOM;
+    }
+    if (pixel_index32 && (long long)s.N * s.H * s.W >= (1LL << 31) - (1LL << 20)) {
+        set_error("%s: %lld input pixels do not fit the 32-bit pixel index", who, (long long)s.N * s.H * s.W);
+        return MV_E_UNSUPPORTED;
+    }
+    p.N = s.N; p.H = s.H; p.W = s.W; p.C = s.C; p.K = s.K; p.R = s.R; p.S = s.S;
+    p.Ho = s.Ho(); p.Wo = s.Wo();
+    p.sh = s.sh; p.sw = s.sw; p.ph = s.ph; p.pw = s.pw; p.dh = s.dh; p.dw = s.dw;
+    const long long M = s.M();
+    if (M >= (1LL << 31) - 256) {
+        set_error("%s: M=%lld too large", who, M);
+        return MV_E_UNSUPPORTED;
+    }
+    p.M = (int)M;
+    p.act = s.act;
+    return MV_OK;
+}
+
+// The launchers that execute a route (route.h holds the rule, its predicates and the kernels' names), implemented in the kernel
+// translation units.  igemm_launch: every route of route_conv but Kern::generic.
+int igemm_launch(const void* x, const void* w, const float* scale, const float* shift, const void* residual, void* y,
+                 const ConvShape& s, Route r, hipStream_t stream);
 int igemm_grouped64_supported(int C, int K, int R, int S, int groups, int in_dtype, int out_dtype);
 int igemm_grouped64_window(int C, int groups);
 int igemm_grouped64_launch(const void* x, const void* w64, const float* scale, const float* shift, const void* residual, void* y,
                            int N, int H, int W, int C, int K, int R, int S, int sh, int sw, int ph, int pw, int dh, int dw, int groups,
                            int act, int out_dtype, hipStream_t stream);
-int igemm_oddc_supported(int C, int K, int groups, int in_dtype, int out_dtype);
-int igemm_oddc_launch(const void* x, const void* w, const float* scale, const float* shift, const void* residual, void* y, int N,
-                      int H, int W, int C, int K, int R, int S, int sh, int sw, int ph, int pw, int dh, int dw, int act,
-                      int out_dtype, hipStream_t stream);
 int dwconv_supported(int C, int K, int groups, int R, int S, int in_dtype, int out_dtype);
 int dwconv_launch(const void* x, const void* w, const float* scale, const float* shift, void* y, int N, int H, int W, int C, int R,
                   int S, int sh, int sw, int ph, int pw, int dh, int dw, int act, hipStream_t stream);
-int stream1x1_supported(int C, int K, int in_dtype, int out_dtype, long long M);
 int stream1x1_launch(const void* x, const void* w, const float* scale, const float* shift, const void* residual,
                      void* y, long long M, int C, int K, int act, int out_dtype, hipStream_t stream);
 int ln_mlp_supported(long long M, int C, int hidden, int x_dtype);
@@ -170,18 +189,11 @@ int ln_mlp_res_launch(const void* x, const float* res, const void* w1, const flo
 int stream1x1_ln_supported(long long M, int C, int K, int x_dtype, int out_dtype);
 int stream1x1_ln_launch(const void* x, const void* w, const float* shift, void* y, long long M, int C, int K, float eps, int act,
                         int x_dtype, hipStream_t st);
-int conv3x3c64_supported(int C, int K, int R, int S, int sh, int sw, int ph, int pw, int dh, int dw, int in_dtype,
-                         int out_dtype, const void* residual, long long M);
-int igemm2_wanted(long long M, int C, int K, int R, int S);
-int igemm2_launch(const void* x, const void* w, const float* scale, const float* shift, const void* residual,
-                  void* y, int N, int H, int W, int C, int K, int R, int S, int sh, int sw, int ph, int pw,
-                  int dh, int dw, int act, int out_dtype, int m_end, int tok, hipStream_t stream);
+int igemm2_launch(const void* x, const void* w, const float* scale, const float* shift, const void* residual, void* y,
+                  const ConvShape& s, int tile, int tok, hipStream_t stream);   // tile: 1 = 256x64, 2 = 256x128, 3 = 256x256, 0 = its own rule
 int igemm2_tile_shape(long long M, int K, int* bm, int* bn);
-int igemm2_dual_supported(long long M, int C1, int C2, int K, int dtype);
 int igemm2_dual_launch(const void* x, const void* x2, const void* w, const float* scale, const float* shift, void* y, int N,
-                       int Ho, int Wo, int C1, int H2, int W2, int C2, int s2, int K, int act, hipStream_t st);
-void igemm2_force_tile(int tile);
-int tile_override(const char* kind, long long M, int a, int b, int R, int S, int sh);
+                       int Ho, int Wo, int C1, int H2, int W2, int C2, int s2, int K, int act, int tile, hipStream_t st);   // tile: 2 = 256x128, 3 = 256x256
 int chain1x1_supported(long long M, int C, int K, int N2, int dtype);
 int chain1x1_dual_supported(long long M, int C1, int C2, int K, int N2, int dtype);
 int chain1x1_dual_launch(const void* x, const void* x2, const void* wcat, const float* scale3, const float* shift3, void* y,
@@ -207,12 +219,9 @@ int chain_l2_dual_launch(const void* t2, const void* x, const void* wfrag, const
 int chain_stream_supported(long long M, int C, int K, int N2, int dtype);
 int chain_stream_launch(const void* x, const void* w3, const float* scale3, const float* shift3, const void* residual, void* y,
                         const void* w1, const float* scale1, const float* shift1, void* t1, long long M, hipStream_t st);
-int igemm8_supported(long long M, int C, int K, int R, int S, long long x_bytes, long long w_bytes);
 int device_status(int clear, unsigned* out);              // igemm8.hip: the status word of mv_device_status
-int igemm8_wanted(long long M, int C, int K, int R, int S);
 int igemm8_launch(const void* x, const void* w, const float* scale, const float* shift, const void* residual, void* y,
-                  int N, int H, int W, int C, int K, int R, int S, int sh, int sw, int ph, int pw, int dh, int dw,
-                  int act, int out_dtype, int tok, int tile, hipStream_t st);   // tile: 1 = 256x256, 2 = 128x256, 3 = 256x128
+                  const ConvShape& s, int tok, int tile, hipStream_t st);       // tile: 1 = 256x256, 2 = 128x256, 3 = 256x128
 bool igemm8_ln_supported(long long M, int N, int K);
 int igemm8_lnout_launch(const void* x, const void* w, const float* shift, const void* res, const void* res_lo, void* y, void* y_lo,
                         float* stats, long long M, int N, int K, hipStream_t st);
@@ -227,7 +236,6 @@ int stem_launch(const void* x, const void* w, const float* scale, const float* s
                 int H, int W, int K, int R, int S, int sh, int sw, int ph, int pw, int act, int x_dtype,
                 int out_dtype, int tok_stride, int tok_offset, const float* pos, hipStream_t stream,
                 const void* w_lo = nullptr);   // w_lo: low halves of split-precision weights (generic kernel only)
-int skinny_f32_supported(long long M, int C, int K, int in_dtype, int out_dtype, const void* residual);
 int skinny_f32_launch(const void* x, const void* w, const float* scale, const float* shift, void* y, long long M, int C, int K,
                       int act, hipStream_t stream);
 int swin_mfma_supported(int C, int heads, int ws_h, int ws_w, int dtype);
@@ -235,7 +243,6 @@ int swin_mfma_launch(const void* qkv, const float* bias, void* out, int B, int H
                      int ws_w, int shift_h, int shift_w, const uint32_t* drop_keys, float keep, hipStream_t st);
 int conv3x3c64_v2_launch(const void* x, const void* w, const float* scale, const float* shift, void* y, int N, int H,
                          int W, int act, hipStream_t stream);
-int skinny_supported(long long M, int C, int K, int in_dtype, const void* residual);
 int skinny_launch(const void* x, const void* w, const float* scale, const float* shift, void* y, long long M, int C, int K,
                   int act, int out_dtype, hipStream_t stream);
 int stem_pool_supported(int C, int K, int R, int S, int sh, int sw, int ph, int pw, int pk, int ps, int pp, int act,

@@ -266,12 +266,13 @@ __global__ __launch_bounds__(512) void conv_f32_lds_kernel(const float* __restri
 static int conv_generic_dispatch(const void* x, const void* w, const float* scale, const float* shift,
                                  const void* residual, void* y, const float* pos, const ConvP& p, int x_dtype,
                                  int w_dtype, int y_dtype, hipStream_t st) {
-    if (x_dtype == MV_F32 && w_dtype == MV_F32 && y_dtype == MV_F32 && p.groups == 1 && p.sxc == 1 && p.swc == 1 && p.K >= 32 && p.C >= 64 &&
-        (p.C & 3) == 0 && (p.sxn & 3) == 0 && (p.sxh & 3) == 0 && (p.sxw & 3) == 0 && (p.swk & 3) == 0 && (p.swr & 3) == 0 &&
-        (p.sws & 3) == 0 && (long long)p.N * p.Ho * p.Wo >= 1024 && !get_flag("no_f32_mfma") && !get_flag("force_generic") && !get_flag("no_f32_lds")) {
-        const long long M = (long long)p.N * p.Ho * p.Wo;
+    const long long M = (long long)p.N * p.Ho * p.Wo;
+    const bool aligned4 = p.sxc == 1 && p.swc == 1 && (p.C & 3) == 0 && (p.sxn & 3) == 0 && (p.sxh & 3) == 0 && (p.sxw & 3) == 0 &&
+                          (p.swk & 3) == 0 && (p.swr & 3) == 0 && (p.sws & 3) == 0;
+    const int variant = generic_variant(x_dtype == MV_F32 && w_dtype == MV_F32 && y_dtype == MV_F32, p.groups, p.C, p.K, aligned4, M, get_flag);
+    set_kernel_name(generic_kernel_name(variant));
+    if (variant == 2) {
         constexpr int SMEM = 2 * (64 + 256) * 36 * 4;
-        set_kernel_name("conv_f32_lds_mfma");
         static LdsAttrSite attr;
         MV_HIP(attr.ensure((const void*)conv_f32_lds_kernel, SMEM));
         hipLaunchKernelGGL(conv_f32_lds_kernel, dim3((unsigned)((M + 255) / 256), (unsigned)((p.K + 63) / 64)), dim3(512), SMEM, st,
@@ -279,15 +280,12 @@ static int conv_generic_dispatch(const void* x, const void* w, const float* scal
         MV_LAUNCH_CHECK();
         return MV_OK;
     }
-    if (x_dtype == MV_F32 && w_dtype == MV_F32 && y_dtype == MV_F32 && p.groups == 1 && p.K >= 8 && !get_flag("no_f32_mfma") && !get_flag("force_generic")) {
-        const long long M = (long long)p.N * p.Ho * p.Wo;
-        set_kernel_name("conv_f32_mfma");
+    if (variant == 1) {
         hipLaunchKernelGGL(conv_f32_mfma_kernel, dim3((unsigned)((M + 127) / 128), (unsigned)((p.K + 31) / 32)), dim3(256), 0, st,
                            (const float*)x, (const float*)w, scale, shift, (const float*)residual, (float*)y, pos, p);
         MV_LAUNCH_CHECK();
         return MV_OK;
     }
-    set_kernel_name("conv_generic");
 #define GO(TX, TW, TY) return conv_generic_launch<TX, TW, TY>(x, w, scale, shift, residual, y, pos, p, st)
     if (x_dtype == MV_F32 && w_dtype == MV_F32 && y_dtype == MV_F32) GO(float, float, float);
     if (x_dtype == MV_BF16 && w_dtype == MV_BF16 && y_dtype == MV_BF16) GO(bf16_t, bf16_t, bf16_t);
@@ -1200,6 +1198,24 @@ static inline int grid_for(long long n, int block = 256) {
     return (int)g;
 }
 
+// Executes a route of route_conv / route_linear (route.h): the matrix-core launchers, or this file's generic kernels.
+static int conv_route_launch(const void* x, const void* w, const float* scale, const float* shift, const void* residual, void* y,
+                             const ConvShape& s, Route r, hipStream_t st) {
+    if (r.kern == Kern::skinny && r.tile == 1) {              // fp32 classifier heads (exact-fp32 MFMA)
+        set_kernel_name(kernel_name(r, true, s, false, false, get_flag));
+        return skinny_f32_launch(x, w, scale, shift, y, s.M(), s.C, s.K, s.act, st);
+    }
+    if (r.kern != Kern::generic) return igemm_launch(x, w, scale, shift, residual, y, s, r, st);
+    ConvP p;
+    p.N = s.N; p.H = s.H; p.W = s.W; p.C = s.C; p.K = s.K; p.R = s.R; p.S = s.S; p.Ho = s.Ho(); p.Wo = s.Wo();
+    p.sh = s.sh; p.sw = s.sw; p.ph = s.ph; p.pw = s.pw; p.dh = s.dh; p.dw = s.dw; p.groups = s.groups;
+    p.sxn = (long long)s.H * s.W * s.C; p.sxh = (long long)s.W * s.C; p.sxw = s.C; p.sxc = 1;
+    const int Cg = s.C / s.groups;
+    p.swk = (long long)s.R * s.S * Cg; p.swr = (long long)s.S * Cg; p.sws = Cg; p.swc = 1;
+    p.act = s.act; p.tok_stride = 0; p.tok_offset = 0;
+    return conv_generic_dispatch(x, w, scale, shift, residual, y, nullptr, p, s.in_dtype, s.in_dtype, s.out_dtype, st);
+}
+
 }  // namespace mv
 
 using namespace mv;
@@ -1215,31 +1231,9 @@ int mv_conv2d_nhwc_fwd(const void* x, const void* w, const float* scale, const f
     MV_CHECK_ARG(sh > 0 && sw > 0 && dh > 0 && dw > 0 && ph >= 0 && pw >= 0, "conv2d_nhwc: bad stride/dilation/pad");
     MV_CHECK_ARG(groups > 0 && C % groups == 0 && K % groups == 0, "conv2d_nhwc: C=%d K=%d not divisible by groups=%d",
                  C, K, groups);
-    const int Ho = (H + 2 * ph - dh * (R - 1) - 1) / sh + 1;
-    const int Wo = (W + 2 * pw - dw * (S - 1) - 1) / sw + 1;
-    MV_CHECK_ARG(Ho > 0 && Wo > 0, "conv2d_nhwc: empty output (%d x %d)", Ho, Wo);
-    hipStream_t st = (hipStream_t)stream;
-    {   // pointwise layers whose reduction is not a multiple of 64 (Swin C = 96) still fit the streaming kernel
-        const long long M = (long long)N * Ho * Wo;
-        const bool dense1x1 = R == 1 && S == 1 && sh == 1 && sw == 1 && ph == 0 && pw == 0 && groups == 1;
-        if (!get_flag("force_generic") && !get_flag("no_stream") && !get_flag("igemm_tile") && dense1x1 && C % 64 != 0 &&
-            stream1x1_supported(C, K, in_dtype, out_dtype, M))
-            return stream1x1_launch(x, w, scale, shift, residual, y, M, C, K, act, out_dtype, st);
-    }
-    if (!get_flag("force_generic") && igemm_supported(C, K, R, S, groups, in_dtype, out_dtype))
-        return igemm_launch(x, w, scale, shift, residual, y, N, H, W, C, K, R, S, sh, sw, ph, pw, dh, dw, act, in_dtype,
-                            out_dtype, st);
-    if (!get_flag("force_generic") && !get_flag("no_oddc") && igemm_oddc_supported(C, K, groups, in_dtype, out_dtype) &&
-        (long long)N * Ho * Wo < (1LL << 31) - 256)                // widths like 24 / 96 / 144 / 160: zero-filled last k-tile
-        return igemm_oddc_launch(x, w, scale, shift, residual, y, N, H, W, C, K, R, S, sh, sw, ph, pw, dh, dw, act, out_dtype, st);
-    ConvP p;
-    p.N = N; p.H = H; p.W = W; p.C = C; p.K = K; p.R = R; p.S = S; p.Ho = Ho; p.Wo = Wo;
-    p.sh = sh; p.sw = sw; p.ph = ph; p.pw = pw; p.dh = dh; p.dw = dw; p.groups = groups;
-    p.sxn = (long long)H * W * C; p.sxh = (long long)W * C; p.sxw = C; p.sxc = 1;
-    const int Cg = C / groups;
-    p.swk = (long long)R * S * Cg; p.swr = (long long)S * Cg; p.sws = Cg; p.swc = 1;
-    p.act = act; p.tok_stride = 0; p.tok_offset = 0;
-    return conv_generic_dispatch(x, w, scale, shift, residual, y, nullptr, p, in_dtype, in_dtype, out_dtype, st);
+    const ConvShape s = {N, H, W, C, K, R, S, sh, sw, ph, pw, dh, dw, groups, act, in_dtype, out_dtype, residual != nullptr, scale != nullptr};
+    MV_CHECK_ARG(s.Ho() > 0 && s.Wo() > 0, "conv2d_nhwc: empty output (%d x %d)", s.Ho(), s.Wo());
+    return conv_route_launch(x, w, scale, shift, residual, y, s, route_conv(s, get_flag), (hipStream_t)stream);
 }
 
 int mv_conv2d_nchw_fwd(const void* x, const void* w, const float* scale, const float* shift, void* y, int N, int C,
@@ -1411,7 +1405,7 @@ int mv_conv1x1_chain_rc0_fwd(const void* t2, const void* x0, const void* wfrag, 
 }
 
 int mv_conv1x1_dual_supported(int64_t M, int C1, int C2, int K, int dtype) {
-    return !get_flag("force_generic") && !get_flag("no_igemm2") && igemm2_dual_supported(M, C1, C2, K, dtype);
+    return conv1x1_dual_supported(M, C1, C2, K, dtype, get_flag);
 }
 
 int mv_conv1x1_dual_fwd(const void* x, const void* x2, const void* wcat, const float* scale, const float* shift, void* y,
@@ -1422,22 +1416,18 @@ int mv_conv1x1_dual_fwd(const void* x, const void* x2, const void* wcat, const f
     MV_CHECK_ARG(N > 0 && Ho > 0 && Wo > 0 && stride2 >= 1 && (Ho - 1) * stride2 < H2 && (Wo - 1) * stride2 < W2,
                  "conv1x1_dual: the strided source does not cover the output map");
     const int64_t M = (int64_t)N * Ho * Wo;
-    if (!mv_conv1x1_dual_supported(M, C1, C2, K, dtype)) {
+    const Route r = route_conv1x1_dual(M, C1, C2, K, stride2, dtype, get_flag);
+    if (r.tile == 0) {
         set_error("conv1x1_dual: unsupported shape M=%lld C1=%d C2=%d K=%d (ask mv_conv1x1_dual_supported first)", (long long)M,
                   C1, C2, K);
         return MV_E_UNSUPPORTED;
     }
-    const int ovd = tile_override("ovd", M, C1, C2, K, stride2, 1);          // 10 / 11 / 12 = igemm8 tiles, 3 = igemm2, 0 = the rule
-    {
-        int t8 = 0;
-        if (get_flag("igemm8") >= 2) t8 = get_flag("igemm8") - 1;
-        else if (ovd >= 10 && ovd <= 12) t8 = ovd - 9;
-        else if (ovd == 0 && (C1 + C2) / 64 >= 8) t8 = igemm8_wanted(M, C1 + C2, K, 1, 1);   // shorter: igemm2 (tuner, ResNet layer2 entry)
-        if (t8)
-            return igemm8_dual_launch(x, x2, wcat, scale, shift, nullptr, y, N, Ho, Wo, C1, H2, W2, C2, stride2, K, act, MV_BF16, t8,
-                                      (hipStream_t)stream);
-    }
-    return igemm2_dual_launch(x, x2, wcat, scale, shift, y, N, Ho, Wo, C1, H2, W2, C2, stride2, K, act, (hipStream_t)stream);
+    ConvShape s = linear_shape(M, K, C1, act, MV_BF16, MV_BF16, false, scale != nullptr);
+    set_kernel_name(kernel_name(r, true, s, true, false, get_flag));
+    if (r.kern == Kern::igemm8)
+        return igemm8_dual_launch(x, x2, wcat, scale, shift, nullptr, y, N, Ho, Wo, C1, H2, W2, C2, stride2, K, act, MV_BF16, r.tile,
+                                  (hipStream_t)stream);
+    return igemm2_dual_launch(x, x2, wcat, scale, shift, y, N, Ho, Wo, C1, H2, W2, C2, stride2, K, act, r.tile, (hipStream_t)stream);
 }
 
 int mv_conv1x1_dual_chain_supported(int64_t M, int C1, int C2, int K, int N2, int dtype) {
@@ -1461,11 +1451,8 @@ int mv_linear_fwd(const void* x, const void* w, const float* scale, const float*
     MV_CHECK_FUSED_ACT(act, "linear");
     MV_CHECK_ARG(x && w && y, "linear: NULL pointer");
     MV_CHECK_ARG(M > 0 && N > 0 && K > 0 && M < (1LL << 31), "linear: bad dims M=%lld N=%d K=%d", (long long)M, N, K);
-    if (skinny_f32_supported(M, K, N, in_dtype, out_dtype, residual))       // fp32 classifier heads (exact-fp32 MFMA)
-        return skinny_f32_launch(x, w, scale, shift, y, M, K, N, act, (hipStream_t)stream);
-    // a Linear over M rows is a 1x1 convolution over an M x 1 image
-    return mv_conv2d_nhwc_fwd(x, w, scale, shift, residual, y, 1, (int)M, 1, K, N, 1, 1, 1, 1, 0, 0, 1, 1, 1, act,
-                              in_dtype, out_dtype, stream);
+    const ConvShape s = linear_shape(M, N, K, act, in_dtype, out_dtype, residual != nullptr, scale != nullptr);
+    return conv_route_launch(x, w, scale, shift, residual, y, s, route_linear(s, get_flag), (hipStream_t)stream);
 }
 
 int mv_linear_split_supported(int64_t M, int N, int K, int dtype) {
@@ -1481,10 +1468,10 @@ int mv_linear_split_fwd(const void* x, const void* w_hi_lo, const float* scale, 
         set_error("linear_split: unsupported shape M=%lld N=%d K=%d (ask mv_linear_split_supported first)", (long long)M, N, K);
         return MV_E_UNSUPPORTED;
     }
-    int tile = igemm8_wanted(M, 2 * K, N, 1, 1);
-    if (tile == 0) tile = N <= 128 ? 3 : 2;
+    const Route r = route_linear_split(M, N, K, get_flag);
+    set_kernel_name(kernel_name(r, true, linear_shape(M, N, K, act, in_dtype, out_dtype, residual != nullptr, scale != nullptr), true, false, get_flag));
     // the second reduction source IS x: [x | x] . [w_hi | w_lo]^T = x . (w_hi + w_lo)^T, accumulated in fp32
-    return igemm8_dual_launch(x, x, w_hi_lo, scale, shift, residual, y, 1, (int)M, 1, K, (int)M, 1, K, 1, N, act, out_dtype, tile,
+    return igemm8_dual_launch(x, x, w_hi_lo, scale, shift, residual, y, 1, (int)M, 1, K, (int)M, 1, K, 1, N, act, out_dtype, r.tile,
                               (hipStream_t)stream);
 }
 
@@ -1777,25 +1764,11 @@ int mv_linear_heads_fwd(const void* x, const void* w, const float* scale, const 
                   (long long)M, N, K, tokens, dh);
         return MV_E_UNSUPPORTED;
     }
-    const int ov8 = !get_flag("igemm2_tile") ? tile_override("ovh", M, N, K, 1, 1, 1) : -1;
-    {
-        int t8 = 0;
-        if (get_flag("igemm8") >= 2) t8 = get_flag("igemm8") - 1;
-        else if (ov8 >= 10 && ov8 <= 12) t8 = ov8 - 9;
-        else if (ov8 == 0) t8 = igemm8_wanted(M, K, N, 1, 1);
-        if (t8 && igemm8_supported(M, K, N, 1, 1, 2LL * M * K, 2LL * N * K))
-            return igemm8_launch(x, w, scale, shift, nullptr, y, 1, (int)M, 1, K, N, 1, 1, 1, 1, 0, 0, 1, 1, MV_ACT_NONE, MV_BF16, tokens,
-                                 t8, (hipStream_t)stream);
-    }
-    if (ov8 == 2 || ov8 == 3) {
-        igemm2_force_tile(ov8);
-        const int rc = igemm2_launch(x, w, scale, shift, nullptr, y, 1, (int)M, 1, K, N, 1, 1, 1, 1, 0, 0, 1, 1, MV_ACT_NONE,
-                                     MV_BF16, 0, tokens, (hipStream_t)stream);
-        igemm2_force_tile(0);
-        return rc;
-    }
-    return igemm2_launch(x, w, scale, shift, nullptr, y, 1, (int)M, 1, K, N, 1, 1, 1, 1, 0, 0, 1, 1, MV_ACT_NONE, MV_BF16, 0,
-                         tokens, (hipStream_t)stream);
+    const Route r = route_linear_heads(M, N, K, get_flag);
+    const ConvShape s = linear_shape(M, N, K, MV_ACT_NONE, MV_BF16, MV_BF16, false, scale != nullptr);
+    set_kernel_name(kernel_name(r, true, s, false, false, get_flag));
+    if (r.kern == Kern::igemm8) return igemm8_launch(x, w, scale, shift, nullptr, y, s, tokens, r.tile, (hipStream_t)stream);
+    return igemm2_launch(x, w, scale, shift, nullptr, y, s, r.tile, tokens, (hipStream_t)stream);
 }
 
 // ---- the LayerNorm between two Linears folded into their epilogues (ViT: norm1 -> qkv, norm2 -> fc1) ----
@@ -1803,7 +1776,7 @@ int mv_linear_heads_fwd(const void* x, const void* w, const float* scale, const 
 // caller's business: ask _supported for each Linear of the pair).
 int mv_linear_lnout_supported(int64_t M, int N, int K, int dtype) {
     return dtype == MV_BF16 && !get_flag("force_generic") && !get_flag("no_igemm8") && !get_flag("no_ln_fold") && igemm8_ln_supported(M, N, K) &&
-           igemm8_wanted(M, K, N, 1, 1) == 1;
+           igemm8_wanted(M, K, N, 1, 1, get_flag) == 1;
 }
 
 int mv_linear_lnout_fwd(const void* x, const void* w, const float* shift, const void* res, const void* res_lo, void* y, void* y_lo,
@@ -1822,7 +1795,7 @@ int mv_linear_lnout_fwd(const void* x, const void* w, const float* shift, const 
 int mv_linear_lnin_supported(int64_t M, int N, int K, int tokens, int dh, int dtype) {
     if (tokens > 0 && !(dh == 64 && M % tokens == 0 && mha_mfma_supported(tokens, dh, dtype))) return 0;
     return dtype == MV_BF16 && !get_flag("force_generic") && !get_flag("no_igemm8") && !get_flag("no_ln_fold") && K <= 768 &&
-           igemm8_ln_supported(M, N, K) && igemm8_wanted(M, K, N, 1, 1) == 1;
+           igemm8_ln_supported(M, N, K) && igemm8_wanted(M, K, N, 1, 1, get_flag) == 1;
 }
 
 int mv_linear_lnin_fwd(const void* x, const float* stats, const void* w_folded, const float* colsum, const float* shift, void* y,

@@ -281,12 +281,6 @@ __global__ __launch_bounds__(256) void igemm_bf16_kernel(const IgemmP p) {
 }
 
 // ------------------------------------------------------------------------------------------------
-int igemm_supported(int C, int K, int R, int S, int groups, int in_dtype, int out_dtype) {
-    (void)R; (void)S;
-    return in_dtype == MV_BF16 && (out_dtype == MV_BF16 || out_dtype == MV_F32) && groups == 1 && C % 64 == 0 &&
-           K % 8 == 0;
-}
-
 template <int BM, int BN, int WM, int WN>
 static int launch_tile(IgemmP& p, bool dense, bool out_f32, hipStream_t st) {
     p.tiles_m = (p.M - p.m_off + BM - 1) / BM;
@@ -303,131 +297,47 @@ static int launch_tile(IgemmP& p, bool dense, bool out_f32, hipStream_t st) {
     return MV_OK;
 }
 
-// Per-shape kernel choice: "ov:<M>:<C>:<K>:<R>:<S>:<stride>" flags (tools/tune_tiles.py sets them while it searches:
-// greedy, one shape at a time, judged on whole-model ms/step in one process) and the short table of shapes where the
-// search beat the rules below by more than its 0.4% threshold.  Choices: 1/2/3 = igemm2 256x64 / 256x128 / 256x256,
-// 7 / 8 = 128x128 / 128x64 (this file), 9 = stream1x1, 10 / 11 / 12 = igemm8 256x256 / 128x256 / 256x128;
-// 0 = the rules.  Kinds: "ov" conv / linear, "ovh" head-major qkv projection, "ovd" dual-source pointwise (3 = igemm2, 10 = igemm8).
-// Round 1 (profiles/r01/*_tile_search.txt): resnet50 B=256 and swin_t B=128 -- nothing above the drift (+0.4% / -0.4%
-// in total), rules kept; vit_base B=256, two lanes -- three shapes, +3.5% together:
-struct TunedTile { const char* kind; int M, a, b, R, S, sh, choice; };
-// Round 2: the three ViT-B rows of round 1 are gone -- igemm8 (choice 10, now the rule for those shapes) beats all of them.
-// Round 3 (gpurun_out/r3d/tune_resnet50.log; after bneck_tail changed the mix): resnet50 B=256, two lanes -- two shapes, +2.2% and +1.6%
-// (three more "wins" of that log are the rule's own kernel re-measured: drift)
-// (inside the laned graph the other lane fills the idle CUs, so the per-FLOP cheaper 256-row tile wins although it leaves
-// fewer tiles than CUs); swin_t B=128: nothing above the drift.
-static const TunedTile kTuned[] = {
-    {"ov", 25088, 1024, 256, 1, 1, 1, 10},    // layer-3 conv1 1x1 1024 -> 256 at 128 images: igemm8 256x256 (98 tiles) over 128x256 (196)
-    {"ov", 6272, 512, 512, 3, 3, 1, 12},      // layer-4 conv2 3x3 at 128 images: igemm8 256x128
-    {"ov", 21632, 192, 384, 3, 3, 1, 12},     // alexnet conv3 (13 x 13, 192 -> 384) at 128 images: igemm8 256x128 (+0.9%, gpurun_out/r3l/tune_alexnet.log)
-};
-int tile_override(const char* kind, long long M, int a, int b, int R, int S, int sh) {
-    char key[96];
-    snprintf(key, sizeof(key), "%s:%lld:%d:%d:%d:%d:%d", kind, M, a, b, R, S, sh);
-    const int f = get_flag(key);
-    if (f) return f > 0 ? f : 0;                          // a negative flag = "the rules", whatever the table says
-    if (get_flag("no_tuned")) return 0;
-    for (const TunedTile& t : kTuned)
-        if (!strcmp(t.kind, kind) && t.M == M && t.a == a && t.b == b && t.R == R && t.S == S && t.sh == sh) return t.choice;
-    return 0;
+// this file's 128-row tile: route.tile = BN (64 for K <= 64, else 128); the odd-C form is the same kernel (zero-filled last k-tile)
+static int launch128(IgemmP& p, Route r, bool dense, bool out_f32, hipStream_t st) {
+    p.m_off = 0;
+    if (r.tile == 64) return launch_tile<128, 64, 4, 1>(p, dense, out_f32, st);
+    return launch_tile<128, 128, 4, 1>(p, dense, out_f32, st);
 }
 
+// Executes a route of route_conv (route.h) other than Kern::generic.
 int igemm_launch(const void* x, const void* w, const float* scale, const float* shift, const void* residual, void* y,
-                 int N, int H, int W, int C, int K, int R, int S, int sh, int sw, int ph, int pw, int dh, int dw,
-                 int act, int in_dtype, int out_dtype, hipStream_t st) {
-    (void)in_dtype;
-    IgemmP p;
-    p.x = (const bf16_t*)x; p.w = (const bf16_t*)w; p.scale = scale; p.shift = shift; p.residual = residual; p.y = y;
-    p.zero = (const bf16_t*)zero_page(st);
-    if (!p.zero) {
-        set_error("igemm: zero page allocation failed");
-        return MV_E_OOM;
-    }
-    p.N = N; p.H = H; p.W = W; p.C = C; p.K = K; p.R = R; p.S = S;
-    p.xpitch = C; p.grouped = 0;
-    p.Ho = (H + 2 * ph - dh * (R - 1) - 1) / sh + 1;
-    p.Wo = (W + 2 * pw - dw * (S - 1) - 1) / sw + 1;
-    p.sh = sh; p.sw = sw; p.ph = ph; p.pw = pw; p.dh = dh; p.dw = dw;
-    const long long M = (long long)N * p.Ho * p.Wo;
-    if (M >= (1LL << 31) - 256) {
+                 const ConvShape& s, Route r, hipStream_t st) {
+    const bool dense = s.dense();
+    const long long M = s.M();
+    if (M >= (1LL << 31) - 256) {                      // every kernel below indexes output rows with 32 bits
         set_error("igemm: M=%lld too large", M);
         return MV_E_UNSUPPORTED;
     }
-    p.M = (int)M;
-    p.m_off = 0;
-    p.act = act;
-    const bool dense = (R == 1 && S == 1 && sh == 1 && sw == 1 && ph == 0 && pw == 0);
-    const bool out_f32 = out_dtype == MV_F32;
-    if (act > MV_ACT_GELU_TANH && dense && !get_flag("no_stream") && !get_flag("igemm_tile") && !get_flag("igemm2_tile") &&
-        stream1x1_supported(C, K, in_dtype, out_dtype, M))             // the streaming kernel's epilogue has every activation
-        return stream1x1_launch(x, w, scale, shift, residual, y, M, C, K, act, out_dtype, st);
-    if (act > MV_ACT_GELU_TANH) {
-        // jax.nn.hard_swish / hard_sigmoid / sigmoid / silu (MobileNetV3, EfficientNet): only this file's epilogue implements them;
-        // fused here they save the element-wise pass over the layer's output that a faster main loop would not buy back
-        if (K <= 64) {
-            set_kernel_name(dense ? "igemm_bf16_128x64_dense_act" : "igemm_bf16_128x64_conv_act");
-            return launch_tile<128, 64, 4, 1>(p, dense, out_f32, st);
-        }
-        set_kernel_name(dense ? "igemm_bf16_128x128_dense_act" : "igemm_bf16_128x128_conv_act");
-        return launch_tile<128, 128, 4, 1>(p, dense, out_f32, st);
+    set_kernel_name(kernel_name(r, dense, s, false, false, get_flag));
+    switch (r.kern) {
+    case Kern::stream1x1:
+        return stream1x1_launch(x, w, scale, shift, residual, y, M, s.C, s.K, s.act, s.out_dtype, st);
+    case Kern::skinny:
+        return skinny_launch(x, w, scale, shift, y, M, s.C, s.K, s.act, s.out_dtype, st);
+    case Kern::conv3x3c64_v2:
+        return conv3x3c64_v2_launch(x, w, scale, shift, y, s.N, s.H, s.W, s.act, st);
+    case Kern::igemm8:
+        return igemm8_launch(x, w, scale, shift, residual, y, s, 0, r.tile, st);
+    case Kern::igemm2:
+        return igemm2_launch(x, w, scale, shift, residual, y, s, r.tile, 0, st);
+    case Kern::igemm128:
+    case Kern::igemm128_oddc: {
+        IgemmP p;
+        p.x = (const bf16_t*)x; p.w = (const bf16_t*)w; p.scale = scale; p.shift = shift; p.residual = residual; p.y = y;
+        p.xpitch = s.C; p.grouped = 0;
+        const int rc = fill_geometry(p, s, r.kern == Kern::igemm128 ? "igemm" : "igemm_oddc", false, st);
+        return rc != MV_OK ? rc : launch128(p, r, dense, s.out_dtype == MV_F32, st);
     }
-    const bool forced_old = get_flag("igemm_tile") || get_flag("igemm2_tile") || get_flag("no_igemm2");
-    if (dense && !get_flag("no_skinny") && !forced_old && get_flag("igemm8") < 2 &&
-        skinny_supported(M, C, K, in_dtype, residual))                   // classifier heads: one wave per 32 x 32 tile
-        return skinny_launch(x, w, scale, shift, y, M, C, K, act, out_dtype, st);
-    const bool ok8 = igemm8_supported(M, C, K, R, S, 2LL * N * H * W * C, 2LL * K * R * S * C);
-    if (get_flag("igemm8") >= 2 && get_flag("igemm8") <= 4 && ok8)                                   // forced (tests): 2 = 256x256, 3 = 128x256, 4 = 256x128
-        return igemm8_launch(x, w, scale, shift, residual, y, N, H, W, C, K, R, S, sh, sw, ph, pw, dh, dw, act, out_dtype, 0,
-                             get_flag("igemm8") - 1, st);
-    const bool plain = !forced_old && !get_flag("no_stream");
-    const int ov = plain && sh == sw ? tile_override("ov", M, C, K, R, S, sh) : 0;
-    if (ov >= 1 && ov <= 3 && C % 64 == 0 && (long long)R * S * (C / 64) >= 1 && R * S <= 64) {
-        igemm2_force_tile(ov);
-        const int rc = igemm2_launch(x, w, scale, shift, residual, y, N, H, W, C, K, R, S, sh, sw, ph, pw, dh, dw, act,
-                                     out_dtype, 0, 0, st);
-        igemm2_force_tile(0);
-        return rc;
+    case Kern::generic:
+        break;
     }
-    if (ov >= 10 && ov <= 12 && ok8)
-        return igemm8_launch(x, w, scale, shift, residual, y, N, H, W, C, K, R, S, sh, sw, ph, pw, dh, dw, act, out_dtype, 0,
-                             ov - 9, st);
-    if (ov == 9 && dense && stream1x1_supported(C, K, in_dtype, out_dtype, M))
-        return stream1x1_launch(x, w, scale, shift, residual, y, M, C, K, act, out_dtype, st);
-    if (ov == 7 || ov == 8) {
-        p.m_off = 0;
-        if (ov == 8) {
-            set_kernel_name(dense ? "igemm_bf16_128x64_dense" : "igemm_bf16_128x64_conv");
-            return launch_tile<128, 64, 4, 1>(p, dense, out_f32, st);
-        }
-        set_kernel_name(dense ? "igemm_bf16_128x128_dense" : "igemm_bf16_128x128_conv");
-        return launch_tile<128, 128, 4, 1>(p, dense, out_f32, st);
-    }
-    if (!get_flag("no_stream") && !get_flag("igemm_tile") && !get_flag("igemm2_tile") &&
-        conv3x3c64_supported(C, K, R, S, sh, sw, ph, pw, dh, dw, in_dtype, out_dtype, residual, M))
-        return conv3x3c64_v2_launch(x, w, scale, shift, y, N, H, W, act, st);
-    if (dense && !get_flag("no_stream") && !get_flag("igemm_tile") && stream1x1_supported(C, K, in_dtype, out_dtype, M))
-        return stream1x1_launch(x, w, scale, shift, residual, y, M, C, K, act, out_dtype, st);
-    // The ping-pong kernels (igemm8.hip) are THE GEMM core: every layer its rule accepts (enough tiles of one of its three
-    // shapes, a reduction of >= 4 k-tiles).  What is left below -- igemm2's 256-row tiles for short reductions, this file's
-    // 128 x 128 tile for small / odd shapes -- is the long tail.
-    const int t8 = forced_old ? 0 : igemm8_wanted(M, C, K, R, S);
-    if (t8 && ok8)
-        return igemm8_launch(x, w, scale, shift, residual, y, N, H, W, C, K, R, S, sh, sw, ph, pw, dh, dw, act, out_dtype, 0, t8,
-                             st);
-    // deep-pipelined 8-wave kernel (igemm2.hip): real convolutions (taps or stride) and big Linears the rule above passed on
-    const long long dense_m = C >= 512 ? 4096 : 32768;
-    const bool want2 = igemm2_wanted(M, C, K, R, S) && (!dense || M >= dense_m || out_f32 || get_flag("igemm2_tile"));
-    if (!get_flag("no_igemm2") && !get_flag("igemm_tile") && want2)
-        return igemm2_launch(x, w, scale, shift, residual, y, N, H, W, C, K, R, S, sh, sw, ph, pw, dh, dw, act, out_dtype, 0, 0, st);
-    p.m_off = 0;
-    int tile = get_flag("igemm_tile");
-    if (tile == 0) tile = (K <= 64) ? 2 : 1;
-    if (tile == 2) {
-        set_kernel_name(dense ? "igemm_bf16_128x64_dense" : "igemm_bf16_128x64_conv");
-        return launch_tile<128, 64, 4, 1>(p, dense, out_f32, st);
-    }
-    set_kernel_name(dense ? "igemm_bf16_128x128_dense" : "igemm_bf16_128x128_conv");
-    return launch_tile<128, 128, 4, 1>(p, dense, out_f32, st);
+    set_error("igemm: not a matrix-core route");
+    return MV_E_UNSUPPORTED;
 }
 
 // Grouped convolution on the matrix cores (ResNeXt conv2, resnet.py:440-471 `groups=32, width_per_group=4|8`; RegNet, regnet.py:49-70,
@@ -461,53 +371,13 @@ int igemm_grouped64_launch(const void* x, const void* w64, const float* scale, c
                            int act, int out_dtype, hipStream_t st) {
     IgemmP p;
     p.x = (const bf16_t*)x; p.w = (const bf16_t*)w64; p.scale = scale; p.shift = shift; p.residual = residual; p.y = y;
-    p.zero = (const bf16_t*)zero_page(st);
-    if (!p.zero) {
-        set_error("igemm_grouped64: zero page allocation failed");
-        return MV_E_OOM;
-    }
-    p.N = N; p.H = H; p.W = W; p.C = igemm_grouped64_window(C, groups); p.K = K; p.R = R; p.S = S;
-    p.xpitch = C; p.grouped = C / groups;
-    p.Ho = (H + 2 * ph - dh * (R - 1) - 1) / sh + 1;
-    p.Wo = (W + 2 * pw - dw * (S - 1) - 1) / sw + 1;
-    p.sh = sh; p.sw = sw; p.ph = ph; p.pw = pw; p.dh = dh; p.dw = dw;
-    p.M = N * p.Ho * p.Wo;
-    p.act = act; p.m_off = 0;
-    set_kernel_name("igemm_grouped64_bf16_128x64");
+    const ConvShape s = {N, H, W, C, K, R, S, sh, sw, ph, pw, dh, dw, groups, act, MV_BF16, out_dtype, residual != nullptr};
+    const int rc = fill_geometry(p, s, "igemm_grouped64", false, st);
+    if (rc != MV_OK) return rc;
+    p.C = igemm_grouped64_window(C, groups);
+    p.xpitch = C; p.grouped = C / groups; p.m_off = 0;
+    set_kernel_name(kGrouped64Name);
     return launch_tile<128, 64, 4, 1>(p, false, out_dtype == MV_F32, st);
-}
-
-// Channel counts that are multiples of 8 but not of 64 (MobileNet-style widths: 16, 24, 32, 96, 144, 160 ...): the 128 x 128 /
-// 128 x 64 kernel of this file with the last k-tile of every tap zero-filled past C.
-int igemm_oddc_supported(int C, int K, int groups, int in_dtype, int out_dtype) {
-    return in_dtype == MV_BF16 && (out_dtype == MV_BF16 || out_dtype == MV_F32) && groups == 1 && C % 8 == 0 && C % 64 != 0 &&
-           K % 8 == 0;
-}
-
-int igemm_oddc_launch(const void* x, const void* w, const float* scale, const float* shift, const void* residual, void* y, int N,
-                      int H, int W, int C, int K, int R, int S, int sh, int sw, int ph, int pw, int dh, int dw, int act,
-                      int out_dtype, hipStream_t st) {
-    IgemmP p;
-    p.x = (const bf16_t*)x; p.w = (const bf16_t*)w; p.scale = scale; p.shift = shift; p.residual = residual; p.y = y;
-    p.zero = (const bf16_t*)zero_page(st);
-    if (!p.zero) {
-        set_error("igemm_oddc: zero page allocation failed");
-        return MV_E_OOM;
-    }
-    p.N = N; p.H = H; p.W = W; p.C = C; p.K = K; p.R = R; p.S = S;
-    p.xpitch = C; p.grouped = 0;
-    p.Ho = (H + 2 * ph - dh * (R - 1) - 1) / sh + 1;
-    p.Wo = (W + 2 * pw - dw * (S - 1) - 1) / sw + 1;
-    p.sh = sh; p.sw = sw; p.ph = ph; p.pw = pw; p.dh = dh; p.dw = dw;
-    p.M = N * p.Ho * p.Wo;
-    p.act = act; p.m_off = 0;
-    const bool dense = (R == 1 && S == 1 && sh == 1 && sw == 1 && ph == 0 && pw == 0);
-    if (K <= 64) {
-        set_kernel_name(dense ? "igemm_bf16_128x64_dense_oddc" : "igemm_bf16_128x64_conv_oddc");
-        return launch_tile<128, 64, 4, 1>(p, dense, out_dtype == MV_F32, st);
-    }
-    set_kernel_name(dense ? "igemm_bf16_128x128_dense_oddc" : "igemm_bf16_128x128_conv_oddc");
-    return launch_tile<128, 128, 4, 1>(p, dense, out_dtype == MV_F32, st);
 }
 
 }  // namespace mv

@@ -388,14 +388,9 @@ static int launch2(Igemm2P& p, bool out_f32, hipStream_t st) {
     return MV_OK;
 }
 
-int igemm2_dual_supported(long long M, int C1, int C2, int K, int dtype) {
-    return dtype == MV_BF16 && C1 % 64 == 0 && C2 % 64 == 0 && C1 >= 64 && C2 >= 64 && K % 8 == 0 && M >= 4096 &&
-           M < (1LL << 31) - 256 && !get_flag("no_dual");
-}
-
 // y[N,Ho,Wo,K] = act(scale[k] * (x[N,Ho,Wo,C1] . w[k, 0:C1] + x2[N, s2*ho, s2*wo, C2] . w[k, C1:C1+C2]) + shift[k])
 int igemm2_dual_launch(const void* x, const void* x2, const void* w, const float* scale, const float* shift, void* y, int N,
-                       int Ho, int Wo, int C1, int H2, int W2, int C2, int s2, int K, int act, hipStream_t st) {
+                       int Ho, int Wo, int C1, int H2, int W2, int C2, int s2, int K, int act, int tile, hipStream_t st) {
     Igemm2P p;
     p.tok = 0;
     p.dbg = 0;
@@ -417,20 +412,15 @@ int igemm2_dual_launch(const void* x, const void* x2, const void* w, const float
     p.M = (int)((long long)N * Ho * Wo);
     p.act = act;
     p.tiles_m = (p.M + 255) / 256;
-    // 256 x 256 tiles measured +2% on resnet50 B=256 over 256 x 128 (the reductions are short: 6-24 k-tiles, so fewer,
-    // larger tiles amortise prologue and epilogue); (a forced-tile switch existed for the tuning runs of round 2)
-    const int tile = (K % 256 == 0) ? 3 : 2;
-    if (tile == 3) {
+    if (tile == 3) {                                        // (route.h: route_conv1x1_dual)
         constexpr int SMEM = 2 * (256 + 256) * 128;
         p.tiles_n = (K + 255) / 256;
-        set_kernel_name("igemm2_dual_bf16_256x256");
         auto kern = igemm2_kernel<2, 4, 4, 2, 2, false, bf16_t, true>;
         MV_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, SMEM));
         hipLaunchKernelGGL(kern, dim3((unsigned)(p.tiles_m * p.tiles_n)), dim3(512), SMEM, st, p);
     } else {
         constexpr int SMEM = 3 * (256 + 128) * 128;
         p.tiles_n = (K + 127) / 128;
-        set_kernel_name("igemm2_dual_bf16_256x128");
         auto kern = igemm2_kernel<4, 2, 2, 2, 3, true, bf16_t, true>;
         MV_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, SMEM));
         hipLaunchKernelGGL(kern, dim3((unsigned)(p.tiles_m * p.tiles_n)), dim3(512), SMEM, st, p);
@@ -439,32 +429,16 @@ int igemm2_dual_launch(const void* x, const void* x2, const void* w, const float
     return MV_OK;
 }
 
-int igemm2_wanted(long long M, int C, int K, int R, int S) {
-    // worth it once there is enough work to fill the chip with 256-row tiles and a reduction of >= 4 k-tiles
-    const long long ktiles = (long long)R * S * (C / 64);
-    (void)K;
-    // (from M = 2048 when the reduction is long, >= 32 k-tiles: Swin stage-3 fc2 3072 -> 768 at M = 3136, +0.5% swin_t)
-    return (M >= 4096 || (M >= 2048 && ktiles >= 32)) && ktiles >= 4 && R * S <= 64;
-}
-
-// block tile igemm2_launch will pick for (M rows, K output channels)
-static thread_local int g_forced_tile = 0;          // set around one launch by the per-shape override (igemm.hip)
-void igemm2_force_tile(int tile) { g_forced_tile = tile; }
-
+// block tile igemm2_launch picks for (M rows, K output channels) when it is not told one
 int igemm2_tile_shape(long long M, int K, int* bm, int* bn) {
-    int tile = g_forced_tile ? g_forced_tile : get_flag("igemm2_tile");
-    if (tile == 0) {
-        const long long big_tiles = ((M + 255) / 256) * (long long)((K + 255) / 256);
-        tile = K <= 64 ? 1 : ((K >= 1024 && big_tiles >= 512) ? 3 : 2);
-    }
+    const int tile = igemm2_tile_rule(M, K, get_flag("igemm2_tile"));
     *bm = 256;
     *bn = tile == 1 ? 64 : (tile == 3 ? 256 : 128);
     return tile;
 }
 
 int igemm2_launch(const void* x, const void* w, const float* scale, const float* shift, const void* residual, void* y,
-                  int N, int H, int W, int C, int K, int R, int S, int sh, int sw, int ph, int pw, int dh, int dw,
-                  int act, int out_dtype, int m_end, int tok, hipStream_t st) {
+                  const ConvShape& s, int tile, int tok, hipStream_t st) {
     Igemm2P p;
     p.tok = tok;
     p.x2 = nullptr; p.C2 = 0; p.H2 = 0; p.W2 = 0; p.s2 = 1;
@@ -475,35 +449,13 @@ int igemm2_launch(const void* x, const void* w, const float* scale, const float*
     p.prof = nullptr;
 #endif
     p.x = (const bf16_t*)x; p.w = (const bf16_t*)w; p.scale = scale; p.shift = shift; p.residual = residual; p.y = y;
-    p.zero = (const bf16_t*)zero_page(st);
-    if (!p.zero) {
-        set_error("igemm2: zero page allocation failed");
-        return MV_E_OOM;
-    }
-    if ((long long)N * H * W >= (1LL << 31) - (1LL << 20)) {          // the kernel indexes input pixels with 32 bits
-        set_error("igemm2: %lld input pixels do not fit the 32-bit pixel index", (long long)N * H * W);
-        return MV_E_UNSUPPORTED;
-    }
-    p.N = N; p.H = H; p.W = W; p.C = C; p.K = K; p.R = R; p.S = S;
-    p.Ho = (H + 2 * ph - dh * (R - 1) - 1) / sh + 1;
-    p.Wo = (W + 2 * pw - dw * (S - 1) - 1) / sw + 1;
-    p.sh = sh; p.sw = sw; p.ph = ph; p.pw = pw; p.dh = dh; p.dw = dw;
-    p.M = (int)((long long)N * p.Ho * p.Wo);
-    if (m_end > 0 && m_end < p.M) p.M = m_end;      // this launch covers output rows [0, m_end) only
-    p.act = act;
-    const bool dense = (R == 1 && S == 1 && sh == 1 && sw == 1 && ph == 0 && pw == 0);
-    const bool out_f32 = out_dtype == MV_F32;
+    const int rc = fill_geometry(p, s, "igemm2", true, st);
+    if (rc != MV_OK) return rc;
+    const bool out_f32 = s.out_dtype == MV_F32;
     int bm_, bn_;
-    const int tile = igemm2_tile_shape((long long)N * p.Ho * p.Wo, K, &bm_, &bn_);   // 1 = 256x64, 2 = 256x128, 3 = 256x256
-    if (tile == 1) {
-        set_kernel_name(dense ? "igemm2_bf16_256x64_dense" : "igemm2_bf16_256x64_conv");
-        return launch2<8, 1, 1, 2, 3, true>(p, out_f32, st);
-    }
-    if (tile == 3) {
-        set_kernel_name(dense ? "igemm2_bf16_256x256_dense" : "igemm2_bf16_256x256_conv");
-        return launch2<2, 4, 4, 2, 2, false>(p, out_f32, st);
-    }
-    set_kernel_name(dense ? "igemm2_bf16_256x128_dense" : "igemm2_bf16_256x128_conv");
+    if (tile == 0) tile = igemm2_tile_shape(s.M(), s.K, &bm_, &bn_);   // 1 = 256x64, 2 = 256x128, 3 = 256x256
+    if (tile == 1) return launch2<8, 1, 1, 2, 3, true>(p, out_f32, st);
+    if (tile == 3) return launch2<2, 4, 4, 2, 2, false>(p, out_f32, st);
     return launch2<4, 2, 2, 2, 3, true>(p, out_f32, st);
 }
 

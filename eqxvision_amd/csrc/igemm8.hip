@@ -781,48 +781,11 @@ int device_status(int clear, unsigned* out) {
     return MV_OK;
 }
 
-int igemm8_supported(long long M, int C, int K, int R, int S, long long x_bytes, long long w_bytes) {
-    // 64-channel k-tiles; the tap mask is 32 bits; byte offsets are 31 bits (the out-of-range marker is bit 31)
-    return C % 64 == 0 && C >= 64 && K % 8 == 0 && R * S <= 32 && M < (1LL << 31) - 256 && x_bytes < (1LL << 31) - (1 << 22) &&
-           w_bytes < (1LL << 31);
-}
-
-// The dispatch rule (igemm.hip, generic.hip).  Returns the tile: 0 = not this kernel family, 1 = 256 x 256,
-// 2 = 128 pixels x 256 channels, 3 = 256 pixels x 128 channels.  Measured (tools/g8_bench.py, round 2, ViT / Swin / ResNet
-// shapes at full and half batch): the 256 x 256 kernel wins from ~0.6 of a round of CUs up; below that the half-size tiles
-// fill the chip; layers with <= 128 output channels take the 256 x 128 tile; reductions shorter than 4 k-tiles stay on the
-// streaming / 128 x 128 kernels (prologue + epilogue of the big tiles dominate).
-int igemm8_wanted(long long M, int C, int K, int R, int S) {
-    if (get_flag("no_igemm8")) return 0;
-    const long long nk = (long long)R * S * (C / 64);
-    if (nk < 4 || K < 96) return 0;
-    const long long tm256 = (M + 255) / 256, tm128 = (M + 127) / 128;
-    if (K <= 128) return tm256 >= 90 ? 3 : 0;
-    const long long tn = (K + 255) / 256, t256 = tm256 * tn, t128 = tm128 * tn;
-    // (a "rounds x relative tile time" refinement that prefers 128 x 256 tiles when the last round of big tiles is nearly empty
-    //  -- ViT fc2 at half batch: 154 -> 144 us alone -- LOSES 5% on the whole model: with two graph lanes the other lane's
-    //  kernels fill that round.  The plain threshold below is what tools/tune_tiles.py confirms on whole-model time.)
-    if (t256 >= 150) return 1;
-    return t128 >= 40 ? 2 : 0;
-}
-
-// Two-way split-K of the half-size tiles (igemm8s_kernel): a launch that leaves half of the 256 CUs idle and has a reduction long
-// enough for two main loops.  `tiles` = tiles of the 128 x 256 / 256 x 128 shape, `nk` = 64-channel k-tiles of the whole reduction.
-static bool splitk_rule(long long tiles, long long nk) {
-    if (get_flag("no_splitk")) return false;
-    // the hand-over costs ~8 us (two atomics, 128 KB out of one CU and into another): it pays from ~40 k-tiles up
-    // (tools/time_splitk.py: 72 k-tiles x1.34, 48 x1.10-1.22, 32 x1.05, 12 x0.75)
-    const int min_nk = get_flag("splitk_min_nk") ? get_flag("splitk_min_nk") : 40;
-    const int max_tiles = 128;
-    return tiles <= max_tiles && nk >= min_nk;
-}
-constexpr size_t SPLITK_SYNC_BYTES = SCRATCH_SYNC_BYTES;            // 2 words x 512 tiles
-
 size_t splitk_scratch_bytes(long long M, long long N, long long kred) {
     if (N <= 0 || M <= 0) return 0;
     // which of the two half-size shapes the dispatch picks is its business: room for the one with more tiles
     const long long ta = ((M + 127) / 128) * ((N + 255) / 256), tb = ((M + 255) / 256) * ((N + 127) / 128);
-    if (!splitk_rule(ta < tb ? ta : tb, kred / 64)) return 0;
+    if (!splitk_rule(ta < tb ? ta : tb, kred / 64, get_flag)) return 0;
     return SPLITK_SYNC_BYTES + (size_t)(ta > tb ? ta : tb) * 128 * 256 * 4;
 }
 
@@ -836,8 +799,9 @@ static int igemm8_go(Igemm2P& p, bool dual, bool out_f32, int tile, hipStream_t 
 #endif
     const int tiles = p.tiles_m * p.tiles_n;
     p.sync = nullptr; p.ws = nullptr;
-    if (tile != 0 && splitk_rule(tiles, (long long)p.R * p.S * (p.C / 64) + (dual ? p.C2 / 64 : 0))) {
-        void* sc = take_scratch(st, SPLITK_SYNC_BYTES + (size_t)tiles * 128 * 256 * 4);      // the host's mv_set_scratch for this launch
+    const size_t need = tile != 0 ? splitk_need_bytes(tiles, (long long)p.R * p.S * (p.C / 64) + (dual ? p.C2 / 64 : 0), get_flag) : 0;
+    if (need) {
+        void* sc = take_scratch(st, need);                               // the host's mv_set_scratch for this launch
         if (sc) { p.sync = (unsigned*)sc; p.ws = (float*)((char*)sc + SPLITK_SYNC_BYTES); }
     }
     const dim3 grid((unsigned)(p.sync ? 16 * ((tiles + 7) / 8) : tiles)), block(512);
@@ -896,40 +860,29 @@ static int igemm8_go(Igemm2P& p, bool dual, bool out_f32, int tile, hipStream_t 
 }
 
 int igemm8_launch(const void* x, const void* w, const float* scale, const float* shift, const void* residual, void* y,
-                  int N, int H, int W, int C, int K, int R, int S, int sh, int sw, int ph, int pw, int dh, int dw,
-                  int act, int out_dtype, int tok, int tile, hipStream_t st) {
+                  const ConvShape& s, int tok, int tile, hipStream_t st) {
     Igemm2P p;
     memset(&p, 0, sizeof(p));
     p.tok = tok;
     p.x = (const bf16_t*)x; p.w = (const bf16_t*)w; p.scale = scale; p.shift = shift; p.residual = residual; p.y = y;
-    p.N = N; p.H = H; p.W = W; p.C = C; p.K = K; p.R = R; p.S = S;
-    p.Ho = (H + 2 * ph - dh * (R - 1) - 1) / sh + 1;
-    p.Wo = (W + 2 * pw - dw * (S - 1) - 1) / sw + 1;
-    p.sh = sh; p.sw = sw; p.ph = ph; p.pw = pw; p.dh = dh; p.dw = dw;
+    p.N = s.N; p.H = s.H; p.W = s.W; p.C = s.C; p.K = s.K; p.R = s.R; p.S = s.S;
+    p.Ho = s.Ho(); p.Wo = s.Wo();
+    p.sh = s.sh; p.sw = s.sw; p.ph = s.ph; p.pw = s.pw; p.dh = s.dh; p.dw = s.dw;
     p.s2 = 1;
-    const long long M = (long long)N * p.Ho * p.Wo;
-    if (!igemm8_supported(M, C, K, R, S, 2LL * N * H * W * C, 2LL * K * R * S * C)) {
-        set_error("igemm8: unsupported shape M=%lld C=%d K=%d R=%d S=%d", M, C, K, R, S);
+    const long long M = s.M();
+    if (!igemm8_supported(M, s.C, s.K, s.R, s.S, 2LL * s.N * s.H * s.W * s.C, 2LL * s.K * s.R * s.S * s.C)) {
+        set_error("igemm8: unsupported shape M=%lld C=%d K=%d R=%d S=%d", M, s.C, s.K, s.R, s.S);
         return MV_E_UNSUPPORTED;
     }
     p.M = (int)M;
-    p.act = act;
+    p.act = s.act;
 #ifdef MV_I8_PROF
     p.prof = (long long*)(((unsigned long long)(unsigned)get_flag("prof_hi") << 32) | (unsigned)get_flag("prof_lo"));
     p.dbg = get_flag("i8_ablate");
 #endif
-    const bool dense = (R == 1 && S == 1 && sh == 1 && sw == 1 && ph == 0 && pw == 0);
-    {   // one name per kernel SYMBOL (template instance), so that a rocprofv3 summary row and a bench row are the same launches:
-        // <tile>_{conv | dense | lin}[_f32out]  <->  igemm8_kernel<OutT, false, MODE> / igemm8s_kernel<OutT, ARR, false, DENSE>
-        const bool fast = dense && !get_flag("no_i8_lin");
-        const char* mode = !fast ? (dense ? "dense0" : "conv") : ((tile == 1 && !scale) ? "lin" : "dense");
-        static thread_local char nm[64];
-        snprintf(nm, sizeof(nm), "igemm8_bf16_%s_%s%s", tile == 2 ? "128x256" : (tile == 3 ? "256x128" : "256x256"), mode,
-                 out_dtype == MV_F32 ? "_f32out" : "");
-        set_kernel_name(nm);
-    }
+    const int out_dtype = s.out_dtype;
     const int rc = igemm8_go(p, false, out_dtype == MV_F32, tile - 1, st);
-    if (p.sync) append_kernel_name("_splitk");
+    if (p.sync) append_kernel_name(kSplitkSuffix);
     return rc;
 }
 
@@ -996,14 +949,8 @@ int igemm8_dual_launch(const void* x, const void* x2, const void* w, const float
     }
     p.M = (int)M;
     p.act = act;
-    {
-        static thread_local char nm[64];
-        snprintf(nm, sizeof(nm), "igemm8_dual_bf16_%s%s", tile == 2 ? "128x256" : (tile == 3 ? "256x128" : "256x256"),
-                 out_dtype == MV_F32 ? "_f32out" : "");
-        set_kernel_name(nm);
-    }
     const int rc = igemm8_go(p, true, out_dtype == MV_F32, tile - 1, st);
-    if (p.sync) append_kernel_name("_splitk");
+    if (p.sync) append_kernel_name(kSplitkSuffix);
     return rc;
 }
 

@@ -168,24 +168,13 @@ __global__ __launch_bounds__(256) void skinny_f32_kernel(const float* __restrict
     }
 }
 
-int skinny_f32_supported(long long M, int C, int K, int in_dtype, int out_dtype, const void* residual) {
-    return in_dtype == MV_F32 && out_dtype == MV_F32 && residual == nullptr && M >= 1 && M <= 1024 && C % 8 == 0 && C >= 64 &&
-           K >= 8 && !get_flag("force_generic");
-}
-
 int skinny_f32_launch(const void* x, const void* w, const float* scale, const float* shift, void* y, long long M, int C, int K,
                       int act, hipStream_t st) {
     const int tiles_n = (K + 31) / 32, tiles_m = (int)((M + 31) / 32);
-    set_kernel_name("skinny_linear_f32_mfma");
     hipLaunchKernelGGL(skinny_f32_kernel, dim3(tiles_n * tiles_m), dim3(256), 0, st, (const float*)x, (const float*)w, scale, shift,
                        (float*)y, (int)M, K, C, act, tiles_n);
     MV_LAUNCH_CHECK();
     return MV_OK;
-}
-
-int skinny_supported(long long M, int C, int K, int in_dtype, const void* residual) {
-    // C = reduction length, K = output channels (igemm naming)
-    return in_dtype == MV_BF16 && residual == nullptr && M >= 1 && M <= 256 && C % 16 == 0 && C >= 64 && K >= 8;
 }
 
 int skinny_launch(const void* x, const void* w, const float* scale, const float* shift, void* y, long long M, int C, int K,
@@ -195,7 +184,6 @@ int skinny_launch(const void* x, const void* w, const float* scale, const float*
     p.M = (int)M; p.N = K; p.K = C; p.act = act;
     p.tiles_n = (K + 31) / 32;
     const int tiles_m = (int)((M + 31) / 32);
-    set_kernel_name("skinny_linear_mfma");
     if (out_dtype == MV_F32)
         hipLaunchKernelGGL(skinny_linear_kernel<float>, dim3(p.tiles_n * tiles_m), dim3(256), 0, st, p);
     else

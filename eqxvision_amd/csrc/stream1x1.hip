@@ -288,18 +288,6 @@ __global__ __launch_bounds__(WAVES * 64) void stream1x1_kernel(const StreamP p) 
     }
 }
 
-int stream1x1_supported(int C, int K, int in_dtype, int out_dtype, long long M) {
-    // C = reduction length, K = output channels (igemm naming)
-    // the narrow / odd widths (16 ... 248 in steps of 8: the expansions / projections of MobileNet / EfficientNet / RegNet stacks,
-    // whose outputs dominate the bytes) came later: before, they ran on the 128 x 128 tile kernel with a zero-filled k-tile at
-    // 1.2-1.8 TB/s.  Multiples of 8 that are not multiples of 16 take the KPAD variant (half-empty last k-step).
-    const bool wide = C == 64 || C == 96 || C == 128 || C == 192 || C == 256;
-    const int kc = (C + 15) / 16;
-    const bool narrow = C % 8 == 0 && C >= 16 && C < 256 && !get_flag("no_stream_narrow") &&
-                        (C % 16 == 0 || (kc >= 2 && kc <= 13) || kc == 15);
-    return in_dtype == MV_BF16 && (out_dtype == MV_BF16 || out_dtype == MV_F32) && (wide || narrow) && K % 8 == 0 && M >= 8192;
-}
-
 template <int TN, int KC, typename OutT, bool LN = false, typename XT = bf16_t, bool KPAD = false>
 static int stream_go(StreamP& p, int tiles_n, hipStream_t st) {
     constexpr int WAVES = 8;
@@ -363,9 +351,6 @@ int stream1x1_launch(const void* x, const void* w, const float* scale, const flo
     const bool f32o = out_dtype == MV_F32;
     const int bn = (K <= 64) ? 64 : 128;
     const int tiles_n = (K + bn - 1) / bn;
-    char name[64];
-    snprintf(name, sizeof(name), "stream1x1_bf16_bn%d_k%d", bn, C);
-    set_kernel_name(name);
 #define GO(TN_, KC_)                                                              \
     return f32o ? stream_go<TN_, KC_, float>(p, tiles_n, st) : stream_go<TN_, KC_, bf16_t>(p, tiles_n, st)
 #define GOP(TN_, KC_)                                                             \

@@ -1,6 +1,6 @@
 """Greedy per-shape kernel search on WHOLE-MODEL time (one process, one GPU box; box-to-box variance is larger than the
 effects looked for).  For every GEMM-shaped launch of the model's forward that the igemm / stream kernels serve, try
-the alternative kernels through the "ov:..." override flags (igemm.hip: tile_override) and keep a choice only when the
+the alternative kernels through the "ov:..." override flags (csrc/route.h: tile_override) and keep a choice only when the
 whole forward gets faster by more than THRESH.  Prints rows for eqxvision_amd/csrc/tuned_tiles.h.
 
 usage: tune_tiles.py MODEL [BATCH] [LANES]"""
