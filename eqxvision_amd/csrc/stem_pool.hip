@@ -1,26 +1,44 @@
 // Network entry of the ResNet family in ONE kernel (reference resnet.py:243-254): Conv2d(3 -> 64, 7x7, stride 2,
 // pad 3) from the raw NCHW image + folded BatchNorm + ReLU + MaxPool2d(3, stride 2, pad 1) -> NHWC bf16, gfx950.
 // The same kernel, other template values, is AlexNet's entry (reference alexnet.py:44-46): Conv2d(3 -> 64, 11x11, stride 4,
-// pad 2) + bias + ReLU + MaxPool2d(3, stride 2): the 55 x 55 x 64 map never reaches HBM either (the numbers below are ResNet's;
-// AlexNet: 75 x 84 x 3 patch, 66 fragments = 33 k-steps -- the 11-wide filter row is two fragments of 8, the second 3 / 8 full --,
-// the weight slab is 69 KB so ONE block per CU, and a wave owns TWO pixel tiles that share every weight fragment it reads).
+// pad 2) + bias + ReLU + MaxPool2d(3, stride 2): the 55 x 55 x 64 map never reaches HBM either.
 //
 // Un-fused (stem.hip + max-pool) the 112x112x64 map costs a 411 MB write and a 623 MB read per batch of 256
-// (profiles/r01 PMC traffic) and 0.38 ms; here it never leaves the CU:
-//   * a block owns an 8 x 8 tile of POOLED pixels = 17 x 17 convolution outputs (one halo row / column is
-//     recomputed: 289 vs 256 pixels) = a 39 x 39 x 3 input patch, kept in LDS as bf16;
-//   * the 289 conv pixels are 10 MFMA pixel tiles of 32 (5 waves x 2); A = the 64 x 176 weight slab in the
-//     (c, r, s8) fragment order of stem.hip (zero padded), resident in LDS; B fragments are gathered from the
-//     patch (8 consecutive input pixels of one filter row);
-//   * scale / shift / ReLU are applied to the fp32 accumulators (per-lane constants for the lane's 32
-//     channels), the bf16 result goes to an LDS tile [289][64]; conv positions outside the image store 0, which
-//     is neutral for a max over post-ReLU values (every pool window holds at least one real pixel);
+// (profiles/r01 PMC traffic) and 0.38 ms; here it never leaves the CU.  One body, three instances:
+//
+//   ResNet (the default)                    8 x 7 pooled tile, 4 waves, weights in registers, three blocks per CU
+//   ResNet behind the switch `no_stem_wreg`  8 x 8 pooled tile, 5 waves, weights in LDS, two blocks per CU (the kernel before)
+//   AlexNet                                  8 x 8 pooled tile, 5 waves, weights in LDS, one block per CU, two pixel tiles per wave
+//
+// What all three do (the numbers are the default instance's):
+//   * a block owns a PTY x PTX = 8 x 7 tile of POOLED pixels = 17 x 15 convolution outputs (one halo row / column is
+//     recomputed: 255 vs 224 pixels) = a 39 x 40 x 3 input patch, kept in LDS as bf16, fetched as aligned 4-pixel chunks
+//     (columns 4 px0 - 8 ..), 5 loads per thread; 56 pooled columns are exactly 8 tiles at 224 px;
+//   * the 255 conv pixels are 8 MFMA pixel tiles of 32, two per wave, 99.6 % full; A = the 64 x 176 weight slab in the
+//     (c, r, s8) fragment order of stem.hip (zero padded); B fragments are gathered from the patch (8 consecutive input
+//     pixels of one filter row);
+//   * scale / shift / ReLU are applied to the fp32 accumulators (constants read from LDS), the bf16 result goes to an LDS
+//     tile [255][64]; conv positions outside the image store 0, which is neutral for a max over post-ReLU values (every
+//     pool window holds at least one real pixel);
 //   * after a barrier every thread pools 8 channels of one output pixel: 9 x ds_read_b128 + packed int16 max
-//     (non-negative bf16 order like their bit patterns) and ONE 16-byte store, 8 lanes per 128-byte NHWC line;
-//   * TWO blocks share a CU (<= 128 VGPRs: `amdgpu_waves_per_eu(4, 4)` -- with 154 registers and five waves per block
-//     the second block was never co-resident, measured with per-block time stamps), so one block's patch load and
-//     pooling run under the other's MFMAs; the patch is fetched as aligned 4-pixel chunks (columns 4 px0 - 8 ..),
-//     5 loads per thread instead of 15 scalar ones.
+//     (non-negative bf16 order like their bit patterns) and ONE 16-byte store, 8 lanes per 128-byte NHWC line.
+//
+// Weights in registers (WREG): the prologue builds the slab in LDS as before, inside the area that later holds the patch
+// and the conv tile, and every lane then loads the 22 fragments its MFMAs will ever need (rows fr and 32 + fr, 11 k-steps):
+// 88 VGPRs for the whole persistent loop.  The 8 x 8 / LDS-slab kernel re-read both 1 KB fragments in front of every MFMA
+// pair, 220 KB of the 450 KB a tile moved through LDS.  Without the slab a block holds 46.6 KB of LDS: three blocks per CU
+// = 3 waves per SIMD = a 168-register budget (`amdgpu_waves_per_eu(3, 3)`; 167 / 168 used, no scratch), so one block's
+// patch load and pooling run under the MFMAs of two others.  Four waves split the 8 pixel tiles evenly over the 4 SIMDs
+// (10 tiles over 5 waves left one SIMD with twice the matrix work).  Fragment order, k order and MFMA shape are those of the
+// LDS-slab instance, so both give the same bits (tests/test_stem_wreg_gpu.py).
+// Measured per 128 images, alone (profiles/stem_wreg_ab.json): 74 -> 60 us, the resnet50 step -1.6 % / -2.2 %.  Two blocks per CU
+// with the same body: 67 us; the 7 x 8 tile (15 x 17 conv pixels, 48-wide patch): the same as 8 x 7 at either block count; two pixel
+// tiles per wave at once: no gain; the B gather issued 1 - 3 k-steps ahead of its MFMAs, by hand: no gain, and it spills.
+// AlexNet's slab (33 k-steps, 264 VGPRs for both channel halves) does not fit; that instance is as it was: 75 x 84 x 3 patch,
+// 66 fragments -- the 11-wide filter row is two fragments of 8, the second 3 / 8 full --, 69 KB slab so ONE block per CU, and a
+// wave owns TWO pixel tiles that share every weight fragment it reads.  The LDS-slab instances run under
+// `amdgpu_waves_per_eu(4, 4)` (<= 128 VGPRs: with 154 registers and five waves per block the second block was never
+// co-resident, measured with per-block time stamps).
 #include "mfma_common.h"
 
 namespace mv {
@@ -62,31 +80,34 @@ template <> struct Img4<bf16_t> {
 // TPW: pixel tiles a wave works on at once (they share the weight fragments).  Columns: the patch starts at image column
 // 2 STRIDE px0 - ALN (a multiple of 4: aligned 4-pixel chunks), the window of conv column cx at patch column STRIDE cx + WO; a B
 // fragment must start on an even element (4-byte aligned ds_read_b32): SHIFT = 1 starts it one pixel LEFT of the window.
-template <typename TX, bool VEC, int R, int STRIDE, int PAD, int PPAD, int PWP, int TPW>
-__global__ __launch_bounds__(320) __attribute__((amdgpu_waves_per_eu(4, 4))) void stem_pool_kernel(const StemPoolP p) {
+// PTY x PTX: the block's tile of pooled pixels; NW: waves per block; WPE: waves per SIMD the register budget is cut for;
+// WREG: the lane's weight fragments live in registers (the slab's LDS is only a staging area of the prologue).
+template <typename TX, bool VEC, int R, int STRIDE, int PAD, int PPAD, int PWP, int TPW, int PTY, int PTX, int NW, int WPE, bool WREG>
+__global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(WPE, WPE))) void stem_pool_kernel(const StemPoolP p) {
     constexpr int C = 3, S = R, K = 64;
-    constexpr int CT = 17;                                  // conv tile edge (2 * 8 + 1)
-    constexpr int NPIX = CT * CT;                           // 289
+    constexpr int CTY = 2 * PTY + 1, CTX = 2 * PTX + 1;     // conv tile: one halo row / column for the 3 x 3 / 2 pool
+    constexpr int NPIX = CTY * CTX;                         // 289 | 255
     constexpr int BC = STRIDE * PPAD + PAD;                 // image row / column of conv (2 py0, 2 px0)'s window = 2 STRIDE py0 - BC
     constexpr int ALN = (BC + 3) & ~3, WO = ALN - BC, SHIFT = WO & 1;
     constexpr int SB = (S + SHIFT + 7) / 8;                 // fragments of 8 per filter row
-    constexpr int PH = STRIDE * (CT - 1) + R;               // 39 patch rows
+    constexpr int PH = STRIDE * (CTY - 1) + R;              // 39 patch rows
     constexpr int PWp = PWP;                                // patch row pitch (elements): image columns 4 px0 - 8 .. + 47
-    static_assert(PWp % 4 == 0 && PWp >= STRIDE * (CT - 1) + WO - SHIFT + 8 * SB, "patch row must hold the last fragment");
+    static_assert(PWp % 4 == 0 && PWp >= STRIDE * (CTX - 1) + WO - SHIFT + 8 * SB, "patch row must hold the last fragment");
     constexpr int PATCH = C * PH * PWp;                     // 5616
     constexpr int NCHUNK = C * PH * (PWp / 4);              // 1404 chunks of 4 pixels
     constexpr int NFRAG = C * R * SB;                       // 21 fragments of 8 (s padded 7 -> 8)
     constexpr int NK16 = (NFRAG + 1) / 2;                   // 11
     constexpr int WPITCH = ((2 * NK16) | 1) * 16;           // 368 bytes
     constexpr int CPITCH = 144;                             // conv tile row pitch (bytes): 64 bf16 + 16
-    constexpr int NT = 320, NEMAX = 8, NE = (NCHUNK + NT - 1) / NT;    // 5 chunks per thread
+    constexpr int NT = NW * 64, NEMAX = 8, NE = (NCHUNK + NT - 1) / NT;    // 5 chunks per thread
     constexpr int NPASS = (NE + NEMAX - 1) / NEMAX, NEP = (NE + NPASS - 1) / NPASS;   // patch load in passes of <= 8 chunks per thread
-    constexpr int OFF_PATCH = K * WPITCH;                                  // 23552
+    constexpr int OFF_PATCH = WREG ? 0 : K * WPITCH;                       // 23552 | 0
     constexpr int OFF_CTILE = OFF_PATCH + ((PATCH * 2 + 15) & ~15);         // + 11232
     constexpr int OFF_FTAB = OFF_CTILE + NPIX * CPITCH;                     // + 41616
-    static_assert(K * C * R * S * 2 <= OFF_FTAB - OFF_PATCH, "raw weights are staged in the patch + conv tile area");
-    extern __shared__ __attribute__((aligned(16))) char smem[];             // 76.9 KB: two blocks per CU
-    char* wl = smem;
+    constexpr int WRAW = (K * C * R * S * 2 + 15) & ~15;                    // the OIHW weights as they are
+    static_assert(WRAW + (WREG ? K * WPITCH : 0) <= OFF_FTAB - OFF_PATCH, "raw weights (WREG: and the slab) are staged in the patch + conv tile area");
+    extern __shared__ __attribute__((aligned(16))) char smem[];             // 76.9 KB: two blocks per CU | 46.6 KB
+    char* wl = WREG ? smem + WRAW : smem;
     bf16_t* patch = (bf16_t*)(smem + OFF_PATCH);
     char* ctile = smem + OFF_CTILE;
     float* sct = (float*)(smem + OFF_FTAB);
@@ -104,14 +125,13 @@ __global__ __launch_bounds__(320) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
         constexpr int U = (NCH16 + NT - 1) / NT;               // 4
         bf16_t* wraw = (bf16_t*)(smem + OFF_PATCH);        // patch + conv tile area, idle now
         const bool al = ((uintptr_t)p.w & 15) == 0;
-        uint4 v[U];
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            const int i = u * NT + tid;
-            const int ic = i < NCH16 ? i : NCH16 - 1;
-            if (al) v[u] = *(const uint4*)(p.w + ic * 8);
-        }
         if (al) {
+            uint4 v[U];
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+                const int i = u * NT + tid;
+                v[u] = *(const uint4*)(p.w + (i < NCH16 ? i : NCH16 - 1) * 8);
+            }
 #pragma unroll
             for (int u = 0; u < U; ++u) {
                 const int i = u * NT + tid;
@@ -137,6 +157,18 @@ __global__ __launch_bounds__(320) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
         }
     }
 
+    // WREG: lane (fr, fh) keeps the A operands of all its MFMAs -- rows fr and 32 + fr, fragments 2 kk + fh -- for the whole
+    // persistent loop; the in-loop barrier in front of the first patch store comes after these reads
+    uint4 wa[WREG ? 2 * NK16 : 1];
+    if constexpr (WREG) {
+        __syncthreads();
+#pragma unroll
+        for (int kk = 0; kk < NK16; ++kk) {
+            wa[kk] = *(const uint4*)(wl + fr * WPITCH + (2 * kk + fh) * 16);
+            wa[NK16 + kk] = *(const uint4*)(wl + (32 + fr) * WPITCH + (2 * kk + fh) * 16);
+        }
+    }
+
     // epilogue constants live in LDS (64 + 64 floats): as per-lane registers they cost 64 VGPRs and the second
     // block per CU; accumulator quad g of channel tile a holds channels a*32 + 8g + 4fh + 0..3
     if (tid < 64) {
@@ -150,8 +182,8 @@ __global__ __launch_bounds__(320) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
         const int tx = tile % p.tiles_x;
         const int ty = (tile / p.tiles_x) % p.tiles_y;
         b = tile / (p.tiles_x * p.tiles_y);
-        py0 = ty * 8;
-        px0 = tx * 8;
+        py0 = ty * PTY;
+        px0 = tx * PTX;
     };
     // chunk i of thread: i = j * NT + tid -> (c, yy, q): input row 4*py0 - 5 + yy, columns 4*px0 - 8 + 4q .. + 3
     // XCD-aware tile order: blocks are dispatched round-robin over the 8 XCDs, each with its own L2.  XCD x owns the
@@ -205,16 +237,16 @@ __global__ __launch_bounds__(320) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
         }
         __syncthreads();
 
-        // ---- convolution: 10 pixel tiles of 32 over the 17 x 17 conv region (conv origin 2*py0 - PPAD, 2*px0 - PPAD), TPW at a time
+        // ---- convolution: 10 | 8 pixel tiles of 32 over the 17 x 17 | 17 x 15 conv region (conv origin 2*py0 - PPAD, 2*px0 - PPAD), TPW at a time
         constexpr int NTILE = (NPIX + 31) / 32;
 #pragma unroll 1
-        for (int t0 = wave * TPW; t0 < NTILE; t0 += 5 * TPW) {
+        for (int t0 = wave * TPW; t0 < NTILE; t0 += NW * TPW) {
             int idx[TPW], lbase[TPW], cyx[TPW];
 #pragma unroll
             for (int u = 0; u < TPW; ++u) {
                 idx[u] = (t0 + u) * 32 + fr;
                 const int ic = idx[u] < NPIX ? idx[u] : NPIX - 1;
-                const int cy = ic / CT, cx = ic - cy * CT;
+                const int cy = ic / CTX, cx = ic - cy * CTX;
                 cyx[u] = cy * 32 + cx;
                 lbase[u] = (STRIDE * cy) * PWp + STRIDE * cx + WO - SHIFT;   // SHIFT = 1: one pixel left of my window origin -> even
             }
@@ -233,8 +265,14 @@ __global__ __launch_bounds__(320) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
                 const int f0 = 2 * kk < NFRAG ? 2 * kk : NFRAG - 1, f1 = 2 * kk + 1 < NFRAG ? 2 * kk + 1 : NFRAG - 1;
                 const int o0 = (((f0 / SB) / R) * PH + (f0 / SB) % R) * PWp + 8 * (f0 % SB);
                 const int o1 = (((f1 / SB) / R) * PH + (f1 / SB) % R) * PWp + 8 * (f1 % SB);
-                const uint4 a0 = *(const uint4*)(wl + fr * WPITCH + f * 16);
-                const uint4 a1 = *(const uint4*)(wl + (32 + fr) * WPITCH + f * 16);
+                uint4 a0, a1;
+                if constexpr (WREG) {
+                    a0 = wa[kk];
+                    a1 = wa[NK16 + kk];
+                } else {
+                    a0 = *(const uint4*)(wl + fr * WPITCH + f * 16);
+                    a1 = *(const uint4*)(wl + (32 + fr) * WPITCH + f * 16);
+                }
 #pragma unroll
                 for (int u = 0; u < TPW; ++u) {
                     const uint32_t* src = (const uint32_t*)(patch + lbase[u] + (fh ? o1 : o0));   // 4-byte aligned
@@ -274,19 +312,19 @@ __global__ __launch_bounds__(320) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
         }
         __syncthreads();
 
-        // ---- max-pool 3x3 / 2 over the conv tile: item = (pooled pixel 0..63, 8-channel group 0..7)
-        for (int it = tid; it < 64 * 8; it += NT) {
+        // ---- max-pool 3x3 / 2 over the conv tile: item = (pooled pixel 0 .. PTY PTX - 1, 8-channel group 0..7)
+        for (int it = tid; it < PTY * PTX * 8; it += NT) {
             const int c8 = it & 7, pp = it >> 3;
-            const int ly = pp >> 3, lx = pp & 7;
+            const int ly = pp / PTX, lx = pp - ly * PTX;
             const int py = py0 + ly, px = px0 + lx;
-            const char* base = ctile + ((2 * ly) * CT + 2 * lx) * CPITCH + c8 * 16;   // window origin = conv (2ly, 2lx) of the tile
+            const char* base = ctile + ((2 * ly) * CTX + 2 * lx) * CPITCH + c8 * 16;   // window origin = conv (2ly, 2lx) of the tile
             i16x8 m = *(const i16x8*)base;
 #pragma unroll
             for (int dy = 0; dy < 3; ++dy)
 #pragma unroll
                 for (int dx = 0; dx < 3; ++dx) {
                     if (dy == 0 && dx == 0) continue;
-                    const i16x8 v = *(const i16x8*)(base + (dy * CT + dx) * CPITCH);
+                    const i16x8 v = *(const i16x8*)(base + (dy * CTX + dx) * CPITCH);
                     m = __builtin_elementwise_max(m, v);
                 }
             if (py < p.Po && px < p.Qo)
@@ -304,18 +342,18 @@ int stem_pool_supported(int C, int K, int R, int S, int sh, int sw, int ph, int 
            act == MV_ACT_RELU && (x_dtype == MV_F32 || x_dtype == MV_BF16) && out_dtype == MV_BF16 && in_elems < (1LL << 31);
 }
 
-template <int R, int STRIDE, int PAD, int PPAD, int PWP, int TPW>
+template <int R, int STRIDE, int PAD, int PPAD, int PWP, int TPW, int PTY, int PTX, int NW, int WPE, bool WREG>
 static int stem_pool_go(StemPoolP p, int x_dtype, int blocks_per_cu, const char* name_f32, const char* name_bf16, hipStream_t st) {
     constexpr int SB = (R + (((((STRIDE * PPAD + PAD) + 3) & ~3) - (STRIDE * PPAD + PAD)) & 1) + 7) / 8;
-    constexpr int NK16 = (3 * R * SB + 1) / 2, WPITCH = ((2 * NK16) | 1) * 16, PH = STRIDE * 16 + R;
-    constexpr int SMEM = 64 * WPITCH + ((3 * PH * PWP * 2 + 15) & ~15) + 289 * 144 + 128 * 4;
+    constexpr int NK16 = (3 * R * SB + 1) / 2, WPITCH = ((2 * NK16) | 1) * 16, PH = STRIDE * 2 * PTY + R;
+    constexpr int SMEM = (WREG ? 0 : 64 * WPITCH) + ((3 * PH * PWP * 2 + 15) & ~15) + (2 * PTY + 1) * (2 * PTX + 1) * 144 + 128 * 4;
     static_assert(SMEM <= 160 * 1024, "LDS");
     p.Ho = (p.H + 2 * PAD - R) / STRIDE + 1;
     p.Wo = (p.W + 2 * PAD - R) / STRIDE + 1;
     p.Po = (p.Ho + 2 * PPAD - 3) / 2 + 1;
     p.Qo = (p.Wo + 2 * PPAD - 3) / 2 + 1;
-    p.tiles_y = (p.Po + 7) / 8;
-    p.tiles_x = (p.Qo + 7) / 8;
+    p.tiles_y = (p.Po + PTY - 1) / PTY;
+    p.tiles_x = (p.Qo + PTX - 1) / PTX;
     const long long tiles = (long long)p.N * p.tiles_y * p.tiles_x;
     if (tiles >= (1LL << 31)) {
         set_error("stem_pool: too many tiles");
@@ -328,9 +366,9 @@ static int stem_pool_go(StemPoolP p, int x_dtype, int blocks_per_cu, const char*
     const bool vec = p.W % 4 == 0 && ((uintptr_t)p.x & 15) == 0;
 #define GO(TX_, V_)                                                                                              \
     do {                                                                                                         \
-        auto kern = stem_pool_kernel<TX_, V_, R, STRIDE, PAD, PPAD, PWP, TPW>;                                   \
+        auto kern = stem_pool_kernel<TX_, V_, R, STRIDE, PAD, PPAD, PWP, TPW, PTY, PTX, NW, WPE, WREG>;                                  \
         MV_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, SMEM));        \
-        hipLaunchKernelGGL(kern, dim3(gx), dim3(320), SMEM, st, p);                                              \
+        hipLaunchKernelGGL(kern, dim3(gx), dim3(NW * 64), SMEM, st, p);                                          \
     } while (0)
     if (x_dtype == MV_F32) { if (vec) GO(float, true); else GO(float, false); }
     else { if (vec) GO(bf16_t, true); else GO(bf16_t, false); }
@@ -346,8 +384,12 @@ int stem_pool_launch(const void* x, const void* w, const float* scale, const flo
     p.N = N; p.H = H; p.W = W;
     if (R == 11)                                          // 145 KB of LDS: one block per CU; two pixel tiles per wave at once (+1.5 % on the model;
                                                           // the same on the ResNet entry is 2.7 % SLOWER: it costs the second block per CU its slack)
-        return stem_pool_go<11, 4, 2, 0, 84, 2>(p, x_dtype, 1, "stem_pool11_mfma_f32in", "stem_pool11_mfma_bf16in", st);
-    return stem_pool_go<7, 2, 3, 1, 48, 1>(p, x_dtype, 2, "stem_pool_mfma_f32in", "stem_pool_mfma_bf16in", st);   // two blocks per CU
+        return stem_pool_go<11, 4, 2, 0, 84, 2, 8, 8, 5, 4, false>(p, x_dtype, 1, "stem_pool11_mfma_f32in", "stem_pool11_mfma_bf16in", st);
+    const char *nf = "stem_pool_mfma_f32in", *nb = "stem_pool_mfma_bf16in";
+    if (get_flag("no_stem_wreg"))
+        return stem_pool_go<7, 2, 3, 1, 48, 1, 8, 8, 5, 4, false>(p, x_dtype, 2, nf, nb, st);   // two blocks per CU
+    // weights in registers, 8 x 7 pooled tiles, 4 waves, THREE blocks per CU (46.6 KB of LDS, 168 VGPRs)
+    return stem_pool_go<7, 2, 3, 1, 40, 1, 8, 7, 4, 3, true>(p, x_dtype, 3, nf, nb, st);
 }
 
 }  // namespace mv
