@@ -361,10 +361,13 @@ __global__ void mha_generic_kernel(const T* __restrict__ qkv, T* __restrict__ ou
 // qkv NHWC [B,Hf,Wf,3C] with channel order [q|k|v][head][dh]; roll / partition / reverse / mask
 // are index arithmetic.
 // ------------------------------------------------------------------------------------------
-template <typename T>
+// COS (Swin V2, swin.py:159-168): q and k times `rnorm` ([B][2][n][C], swin_qk_rnorm.hip) -- rounded to T like the operands of
+// the MFMA kernel -- and logit_mul[h] instead of dh^-0.5.
+template <typename T, bool COS>
 __global__ void swin_attn_generic_kernel(const T* __restrict__ qkv, const float* __restrict__ bias,
                                          T* __restrict__ out, int B, int Hf, int Wf, int C, int heads, int wsh,
-                                         int wsw, int shh, int shw) {
+                                         int wsw, int shh, int shw, const float* __restrict__ rnorm,
+                                         const float* __restrict__ logit_mul) {
     extern __shared__ float sm[];  // [n] probs + [dh] q
     const int n = wsh * wsw;
     const int dh = C / heads;
@@ -383,7 +386,9 @@ __global__ void swin_attn_generic_kernel(const T* __restrict__ qkv, const float*
     const long long rs = 3LL * C;
     const T* qrow = qkv + (((long long)b * Hf + oy) * Wf + ox) * rs + h * dh;
     const float qscale = rsqrtf((float)dh);
-    for (int d = lane; d < dh; d += 64) qs[d] = io<T>::ld(qrow + d) * qscale;
+    auto rnd = [](float v) { return sizeof(T) == 2 ? bf2f(f2bf(v)) : v; };
+    const float* rq = COS ? rnorm + ((long long)b * 2 * n + ti) * C + h * dh : nullptr;
+    for (int d = lane; d < dh; d += 64) qs[d] = COS ? rnd(io<T>::ld(qrow + d) * rq[d]) : io<T>::ld(qrow + d) * qscale;
     __syncthreads();
     const bool shifted = (shh + shw) > 0;
     auto region = [&](int y, int x) {
@@ -398,7 +403,13 @@ __global__ void swin_attn_generic_kernel(const T* __restrict__ qkv, const float*
         const int yy = (ky + shh) % Hf, xx = (kx + shw) % Wf;
         const T* krow = qkv + (((long long)b * Hf + yy) * Wf + xx) * rs + C + h * dh;
         float s = 0.f;
-        for (int d = 0; d < dh; ++d) s = fmaf(qs[d], io<T>::ld(krow + d), s);
+        if (COS) {
+            const float* rk = rnorm + (((long long)b * 2 + 1) * n + j) * C + h * dh;
+            for (int d = 0; d < dh; ++d) s = fmaf(qs[d], rnd(io<T>::ld(krow + d) * rk[d]), s);
+            s *= logit_mul[h];
+        } else {
+            for (int d = 0; d < dh; ++d) s = fmaf(qs[d], io<T>::ld(krow + d), s);
+        }
         s += bias[((long long)h * n + ti) * n + j];
         if (shifted && region(ky, kx) != qreg) s += -100.0f;
         sc[j] = s;
@@ -803,6 +814,31 @@ template <int WIDTH> __device__ __forceinline__ float group_sum(float v) {
     return v;
 }
 
+// The row code of the vectorised LayerNorms (layernorm_vec_kernel, layernorm_add_kernel): WIDTH lanes hold one row as CHUNKS chunks
+// of N values each (chunk i of lane sl is live when sl + WIDTH * i < nch); two-pass mean / variance on the registers.
+template <int N, int CHUNKS, int WIDTH>
+__device__ __forceinline__ void row_stats(const float (*a)[N], int sl, int nch, float invC, float eps, float& mean, float& rstd) {
+    float s = 0.f;
+#pragma unroll
+    for (int i = 0; i < CHUNKS; ++i) {
+        const bool on = sl + WIDTH * i < nch;
+#pragma unroll
+        for (int e = 0; e < N; ++e) s += on ? a[i][e] : 0.f;
+    }
+    mean = group_sum<WIDTH>(s) * invC;
+    float q = 0.f;
+#pragma unroll
+    for (int i = 0; i < CHUNKS; ++i) {
+        const bool on = sl + WIDTH * i < nch;
+#pragma unroll
+        for (int e = 0; e < N; ++e) {
+            const float d = a[i][e] - mean;
+            q += on ? d * d : 0.f;
+        }
+    }
+    rstd = rsqrtf(group_sum<WIDTH>(q) * invC + eps);
+}
+
 template <typename TI, typename TO, int CHUNKS, int WIDTH>
 __global__ __launch_bounds__(256) void layernorm_vec_kernel(const TI* __restrict__ x, const float* __restrict__ gamma,
                                                             const float* __restrict__ beta, TO* __restrict__ y, long long M,
@@ -850,25 +886,8 @@ __global__ __launch_bounds__(256) void layernorm_vec_kernel(const TI* __restrict
     auto step = [&](float (*a)[N], float (*b)[N], long long gg) {
         load(b, gg + nw);
         asm volatile("" : "+v"(a[0][0]) : : "memory");  // keep the prefetch ahead of the arithmetic on `a`
-        float s = 0.f;
-#pragma unroll
-        for (int i = 0; i < CHUNKS; ++i) {
-            const bool on = sl + WIDTH * i < nch;
-#pragma unroll
-            for (int e = 0; e < N; ++e) s += on ? a[i][e] : 0.f;
-        }
-        const float mean = group_sum<WIDTH>(s) * invC;
-        float q = 0.f;
-#pragma unroll
-        for (int i = 0; i < CHUNKS; ++i) {
-            const bool on = sl + WIDTH * i < nch;
-#pragma unroll
-            for (int e = 0; e < N; ++e) {
-                const float d = a[i][e] - mean;
-                q += on ? d * d : 0.f;
-            }
-        }
-        const float rstd = rsqrtf(group_sum<WIDTH>(q) * invC + eps);
+        float mean, rstd;
+        row_stats<N, CHUNKS, WIDTH>(a, sl, nch, invC, eps, mean, rstd);
         const long long row = gg * RPW + sub;
         const bool live = gg < groups && row < M;
         TO* yr = y + row * C;
@@ -886,6 +905,60 @@ __global__ __launch_bounds__(256) void layernorm_vec_kernel(const TI* __restrict
     for (; g < groups; g += 2 * nw) {
         step(cur, nxt, g);
         step(nxt, cur, g + nw);
+    }
+}
+
+// Post-norm residual step (Swin V2: x + norm(branch(x)), swin.py:629-635; _PatchMergingV2's norm with res = NULL, :83-87):
+//     y[m][:] = res[m][:] + gamma * n(z[m][:]) + beta      z bf16 / fp32, res fp32 or NULL, y fp32
+// and, when y_lo is given, the same row rounded once to TL -- the operand plane the next Linear reads, so no cast launch stands in
+// front of the GEMMs that consume the fp32 stream.  Row layout and statistics are layernorm_vec_kernel's (row_stats); one row group
+// at a time per wave (the kernel is a plain stream: two reads, two writes).
+template <typename TI, typename TL, int CHUNKS, int WIDTH>
+__global__ __launch_bounds__(256) void layernorm_add_kernel(const TI* __restrict__ z, const float* __restrict__ res,
+                                                            const float* __restrict__ gamma, const float* __restrict__ beta,
+                                                            float* __restrict__ y, TL* __restrict__ y_lo, long long M, int C, float eps) {
+    constexpr int N = Vec16<TI>::N;
+    constexpr int RPW = 64 / WIDTH;
+    const int lane = threadIdx.x & 63;
+    const int sub = lane / WIDTH, sl = lane % WIDTH;
+    const long long gw = (long long)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+    const long long nw = (long long)gridDim.x * (blockDim.x >> 6);
+    const int nch = C / N;
+    const float invC = 1.0f / (float)C;
+    const long long groups = (M + RPW - 1) / RPW;
+    int cc[CHUNKS];
+#pragma unroll
+    for (int i = 0; i < CHUNKS; ++i) {
+        const int c = sl + WIDTH * i;
+        cc[i] = c < nch ? c : nch - 1;
+    }
+    for (long long g = gw; g < groups; g += nw) {
+        long long row = g * RPW + sub;
+        const bool live = row < M;
+        if (!live) row = M - 1;                           // clamped re-read: the group reductions need every lane
+        float a[CHUNKS][N];
+#pragma unroll
+        for (int i = 0; i < CHUNKS; ++i) Vec16<TI>::ld(z + row * C + cc[i] * N, a[i]);
+        float mean, rstd;
+        row_stats<N, CHUNKS, WIDTH>(a, sl, nch, invC, eps, mean, rstd);
+#pragma unroll
+        for (int i = 0; i < CHUNKS; ++i) {
+            if (!(live && sl + WIDTH * i < nch)) continue;
+            const long long off = row * C + cc[i] * N;
+            float o[N];
+#pragma unroll
+            for (int e = 0; e < N; e += 4) {
+                const float4 gv = *(const float4*)(gamma + cc[i] * N + e), bv = *(const float4*)(beta + cc[i] * N + e);
+                float4 rv = make_float4(0.f, 0.f, 0.f, 0.f);
+                if (res) rv = *(const float4*)(res + off + e);
+                o[e] = rv.x + ((a[i][e] - mean) * rstd * gv.x + bv.x);
+                o[e + 1] = rv.y + ((a[i][e + 1] - mean) * rstd * gv.y + bv.y);
+                o[e + 2] = rv.z + ((a[i][e + 2] - mean) * rstd * gv.z + bv.z);
+                o[e + 3] = rv.w + ((a[i][e + 3] - mean) * rstd * gv.w + bv.w);
+            }
+            StN<float, N>::st(y + off, o);
+            if (y_lo) StN<TL, N>::st(y_lo + off, o);
+        }
     }
 }
 
@@ -1723,6 +1796,48 @@ int mv_layernorm_fwd(const void* x, const float* gamma, const float* beta, void*
     return MV_OK;
 }
 
+int mv_layernorm_add_fwd(const void* z, const float* res, const float* gamma, const float* beta, float* y, void* y_lo, int64_t M,
+                         int C, float eps, int z_dtype, int lo_dtype, mv_stream_t stream) {
+    MV_CHECK_ARG(z && gamma && beta && y && M > 0 && C > 0, "layernorm_add: bad args");
+    MV_CHECK_ARG((z_dtype == MV_BF16 || z_dtype == MV_F32) && (lo_dtype == MV_BF16 || lo_dtype == MV_F32), "layernorm_add: bad dtype");
+    MV_CHECK_ARG((const void*)y != z && y_lo != z, "layernorm_add: an output aliases z");
+    const int epc = z_dtype == MV_BF16 ? 8 : 4;
+    const int nch = C / epc;
+    if (C % epc || nch > 64 * 8) {
+        set_error("layernorm_add: unsupported width C=%d (whole 16-byte chunks of z, at most 512 of them)", C);
+        return MV_E_UNSUPPORTED;
+    }
+    hipStream_t st = (hipStream_t)stream;
+    set_kernel_name("layernorm_add");
+    const int width = nch <= 16 ? 16 : (nch <= 32 ? 32 : 64);
+    const long long groups = (M + 64 / width - 1) / (64 / width);
+    long long nb = (groups + 3) / 4;
+    if (nb > 256 * 8) nb = 256 * 8;
+    dim3 vgrid((unsigned)nb), vblock(256);
+#define GO4(TI, TL, CH, WD)                                                                                                  \
+    hipLaunchKernelGGL((layernorm_add_kernel<TI, TL, CH, WD>), vgrid, vblock, 0, st, (const TI*)z, res, gamma, beta, y, (TL*)y_lo, \
+                       (long long)M, C, eps)
+#define GO2(TI, TL)                                   \
+    do {                                              \
+        if (width == 16) GO4(TI, TL, 1, 16);          \
+        else if (width == 32) GO4(TI, TL, 1, 32);     \
+        else if (nch <= 64) GO4(TI, TL, 1, 64);       \
+        else if (nch <= 128) GO4(TI, TL, 2, 64);      \
+        else if (nch <= 192) GO4(TI, TL, 3, 64);      \
+        else if (nch <= 256) GO4(TI, TL, 4, 64);      \
+        else if (nch <= 384) GO4(TI, TL, 6, 64);      \
+        else GO4(TI, TL, 8, 64);                      \
+    } while (0)
+    if (z_dtype == MV_BF16 && lo_dtype == MV_BF16) GO2(bf16_t, bf16_t);
+    else if (z_dtype == MV_BF16) GO2(bf16_t, float);
+    else if (lo_dtype == MV_BF16) GO2(float, bf16_t);
+    else GO2(float, float);
+#undef GO2
+#undef GO4
+    MV_LAUNCH_CHECK();
+    return MV_OK;
+}
+
 int mv_mha_fwd(const void* qkv, void* out, float* probs, int B, int N, int H, int dh, float scale, int dtype,
                mv_stream_t stream) {
     MV_CHECK_ARG(qkv && out && B > 0 && N > 0 && H > 0 && dh > 0, "mha: bad args");
@@ -1859,11 +1974,48 @@ int mv_swin_window_attn_fwd(const void* qkv, const float* bias, void* out, int B
     const size_t smem = (size_t)(n + dh) * sizeof(float);
     set_kernel_name("swin_attn_generic");
     if (dtype == MV_BF16)
-        hipLaunchKernelGGL(swin_attn_generic_kernel<bf16_t>, dim3(tokens, heads, B), dim3(64), smem, st,
-                           (const bf16_t*)qkv, bias, (bf16_t*)out, B, Hf, Wf, C, heads, ws_h, ws_w, shift_h, shift_w);
+        hipLaunchKernelGGL((swin_attn_generic_kernel<bf16_t, false>), dim3(tokens, heads, B), dim3(64), smem, st,
+                           (const bf16_t*)qkv, bias, (bf16_t*)out, B, Hf, Wf, C, heads, ws_h, ws_w, shift_h, shift_w, nullptr, nullptr);
     else
-        hipLaunchKernelGGL(swin_attn_generic_kernel<float>, dim3(tokens, heads, B), dim3(64), smem, st,
-                           (const float*)qkv, bias, (float*)out, B, Hf, Wf, C, heads, ws_h, ws_w, shift_h, shift_w);
+        hipLaunchKernelGGL((swin_attn_generic_kernel<float, false>), dim3(tokens, heads, B), dim3(64), smem, st,
+                           (const float*)qkv, bias, (float*)out, B, Hf, Wf, C, heads, ws_h, ws_w, shift_h, shift_w, nullptr, nullptr);
+    MV_LAUNCH_CHECK();
+    return MV_OK;
+}
+
+int mv_swin_window_attn_cos_fwd(const void* qkv, const float* rnorm, const float* logit_mul, const float* bias, void* out,
+                                const void* keys, float keep_prob, int B, int Hf, int Wf, int C, int heads, int ws_h, int ws_w,
+                                int shift_h, int shift_w, int dtype, mv_stream_t stream) {
+    MV_CHECK_ARG(qkv && rnorm && logit_mul && bias && out && B > 0 && Hf > 0 && Wf > 0 && C > 0 && heads > 0, "swin_attn_cos: bad args");
+    MV_CHECK_ARG(dtype == MV_BF16 || dtype == MV_F32, "swin_attn_cos: dtype %d", dtype);
+    MV_CHECK_ARG(C % heads == 0, "swin_attn_cos: C %% heads != 0");
+    MV_CHECK_ARG(ws_h > 0 && ws_w > 0 && Hf % ws_h == 0 && Wf % ws_w == 0,
+                 "swin_attn_cos: feature map %dx%d is not a multiple of the window %dx%d (reference swin.py:782-790)", Hf, Wf, ws_h, ws_w);
+    MV_CHECK_ARG(shift_h >= 0 && shift_w >= 0 && shift_h < ws_h && shift_w < ws_w, "swin_attn_cos: bad shift");
+    MV_CHECK_ARG(!keys || (keep_prob > 0.f && keep_prob <= 1.f), "swin_attn_cos: keep_prob %g outside (0, 1]", (double)keep_prob);
+    if (ws_h >= Hf) shift_h = 0;  // swin.py:116-120
+    if (ws_w >= Wf) shift_w = 0;
+    hipStream_t st = (hipStream_t)stream;
+    const bool mfma = swin_mfma_supported(C, heads, ws_h, ws_w, dtype) != 0;
+    if (keys && !mfma) {
+        set_error("swin_attn_cos: attention dropout needs bf16, 32 channels per head and <= 64 tokens (C=%d heads=%d window %dx%d dtype=%d)",
+                  C, heads, ws_h, ws_w, dtype);
+        return MV_E_UNSUPPORTED;
+    }
+    if (mfma && (keys || !get_flag("force_generic")))
+        return swin_mfma_launch(qkv, bias, out, B, Hf, Wf, C, heads, ws_h, ws_w, shift_h, shift_w, (const uint32_t*)keys, keep_prob, st,
+                                rnorm, logit_mul);
+    const int n = ws_h * ws_w, dh = C / heads;
+    MV_CHECK_ARG(heads <= 65535 && B <= 65535, "swin_attn_cos: grid too large");
+    const size_t smem = (size_t)(n + dh) * sizeof(float);
+    MV_CHECK_ARG(smem <= 64 * 1024, "swin_attn_cos: window too large for the generic kernel (n=%d)", n);
+    set_kernel_name("swin_attn_generic_cos");
+    if (dtype == MV_BF16)
+        hipLaunchKernelGGL((swin_attn_generic_kernel<bf16_t, true>), dim3(Hf * Wf, heads, B), dim3(64), smem, st, (const bf16_t*)qkv,
+                           bias, (bf16_t*)out, B, Hf, Wf, C, heads, ws_h, ws_w, shift_h, shift_w, rnorm, logit_mul);
+    else
+        hipLaunchKernelGGL((swin_attn_generic_kernel<float, true>), dim3(Hf * Wf, heads, B), dim3(64), smem, st, (const float*)qkv,
+                           bias, (float*)out, B, Hf, Wf, C, heads, ws_h, ws_w, shift_h, shift_w, rnorm, logit_mul);
     MV_LAUNCH_CHECK();
     return MV_OK;
 }

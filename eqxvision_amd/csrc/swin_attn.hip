@@ -25,12 +25,30 @@ struct SwinP {
     int n, nWw, nW, total_windows;
     const uint32_t* drop_keys;   // DROP: one Threefry key per sample, [B][2]
     float keep;
+    const float* rnorm;          // COS: [B][2][n][C], 1 / norm over the windows of an image (swin_qk_rnorm.hip); [.][0] = q, [.][1] = k
+    const float* logit_mul;      // COS: [heads], exp(min(logit_scale, log 100))
 };
 
 // DROP: the reference's `_func_dropout(attn, attention_dropout, key)` (swin.py:227, applied in EVERY mode): probability
 // (window w, head h, query i, key j) of a sample is kept (/ keep) or zeroed by word ((w * heads + h) * n + i) * n + j of the
 // sample's Threefry stream = jax.random.bernoulli(key, keep, (nW, heads, n, n)), between the softmax and P . V.
-template <bool DROP>
+//
+// COS: Swin V2's cosine logits (swin.py:159-168).  q and k are divided by their norm over AXIS 0 of (nW, heads, n, dh) -- the
+// windows of one image, one value per (token-in-window, channel): the reference's axis, kept as it is -- which arrives as the
+// reciprocal `rnorm`.  Each 8-channel Q / K fragment is multiplied by its eight values in fp32 and rounded ONCE to bf16 before the
+// first MFMA; logit_mul[h] takes the place of dh^-0.5.  Bias, mask, softmax, dropout and P . V are the V1 code.
+__device__ __forceinline__ uint4 scale_frag(uint4 f, const float* rn) {
+    const float4 a = *(const float4*)rn, b = *(const float4*)(rn + 4);
+    const float r[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
+    const uint32_t w[4] = {f.x, f.y, f.z, f.w};
+    uint32_t o[4];
+#pragma unroll
+    for (int e = 0; e < 4; ++e)
+        o[e] = pack_bf2(__uint_as_float(w[e] << 16) * r[2 * e], __uint_as_float(w[e] & 0xffff0000u) * r[2 * e + 1]);
+    return make_uint4(o[0], o[1], o[2], o[3]);
+}
+
+template <bool DROP, bool COS>
 __global__ __launch_bounds__(256) void swin_attn_mfma_kernel(const SwinP p) {
     constexpr int DH = 32;
     constexpr int VPITCH = 64 * 2 + 8;                  // bytes per V^T row (64 keys + pad): 8 * odd
@@ -58,7 +76,8 @@ __global__ __launch_bounds__(256) void swin_attn_mfma_kernel(const SwinP p) {
     const int fr = lane & 31, fh = lane >> 5;
     const long long rs = 3LL * p.C;
     const bool shifted = (p.shh + p.shw) > 0;
-    const float scale = rsqrtf((float)DH);
+    float scale = rsqrtf((float)DH);
+    if constexpr (COS) scale = p.logit_mul[h];
     char* vt = vt_l[wave];
     int* kreg = kreg_l[wave];
 
@@ -114,6 +133,15 @@ __global__ __launch_bounds__(256) void swin_attn_mfma_kernel(const SwinP p) {
             for (int kk = 0; kk < 2; ++kk) {
                 qf[tl][kk] = *(const uint4*)(row + kk * 16);
                 kf[tl][kk] = *(const uint4*)(row + p.C + kk * 16);
+            }
+            if constexpr (COS) {
+                const float* rq = p.rnorm + ((long long)b * 2 * n + tc) * p.C + h * DH + fh * 8;
+                const float* rk = rq + (long long)n * p.C;
+#pragma unroll
+                for (int kk = 0; kk < 2; ++kk) {
+                    qf[tl][kk] = scale_frag(qf[tl][kk], rq + kk * 16);
+                    kf[tl][kk] = scale_frag(kf[tl][kk], rk + kk * 16);
+                }
             }
         }
         // my query's region id and output row (q-tile tq: query = 32*tq + fr)
@@ -230,9 +258,11 @@ int swin_mfma_supported(int C, int heads, int ws_h, int ws_w, int dtype) {
 }
 
 int swin_mfma_launch(const void* qkv, const float* bias, void* out, int B, int Hf, int Wf, int C, int heads, int ws_h,
-                     int ws_w, int shift_h, int shift_w, const uint32_t* drop_keys, float keep, hipStream_t st) {
+                     int ws_w, int shift_h, int shift_w, const uint32_t* drop_keys, float keep, hipStream_t st, const float* rnorm,
+                     const float* logit_mul) {
     SwinP p;
     p.drop_keys = drop_keys; p.keep = keep;
+    p.rnorm = rnorm; p.logit_mul = logit_mul;
     p.qkv = (const bf16_t*)qkv; p.bias = bias; p.out = (bf16_t*)out;
     p.B = B; p.Hf = Hf; p.Wf = Wf; p.C = C; p.heads = heads; p.wsh = ws_h; p.wsw = ws_w; p.shh = shift_h; p.shw = shift_w;
     p.n = ws_h * ws_w;
@@ -254,9 +284,16 @@ int swin_mfma_launch(const void* qkv, const float* bias, void* out, int B, int H
         set_error("swin_attn: more than 2^32 probabilities per sample");
         return MV_E_UNSUPPORTED;
     }
+    if (rnorm) {
+        set_kernel_name(drop_keys ? "swin_attn_mfma_cos_dropout" : "swin_attn_mfma_cos");
+        if (drop_keys) hipLaunchKernelGGL((swin_attn_mfma_kernel<true, true>), dim3(gx, heads), dim3(256), 0, st, p);
+        else hipLaunchKernelGGL((swin_attn_mfma_kernel<false, true>), dim3(gx, heads), dim3(256), 0, st, p);
+        MV_LAUNCH_CHECK();
+        return MV_OK;
+    }
     set_kernel_name(drop_keys ? "swin_attn_mfma_dropout" : "swin_attn_mfma");
-    if (drop_keys) hipLaunchKernelGGL(swin_attn_mfma_kernel<true>, dim3(gx, heads), dim3(256), 0, st, p);
-    else hipLaunchKernelGGL(swin_attn_mfma_kernel<false>, dim3(gx, heads), dim3(256), 0, st, p);
+    if (drop_keys) hipLaunchKernelGGL((swin_attn_mfma_kernel<true, false>), dim3(gx, heads), dim3(256), 0, st, p);
+    else hipLaunchKernelGGL((swin_attn_mfma_kernel<false, false>), dim3(gx, heads), dim3(256), 0, st, p);
     MV_LAUNCH_CHECK();
     return MV_OK;
 }

@@ -69,7 +69,7 @@ from .classification.densenet import (
 from .segmentation.deeplabv3 import ASPP, DeepLabHead, DeepLabV3, deeplabv3
 from .segmentation.fcn import FCN, FCNHead, fcn
 from .segmentation.lraspp import LRASPP, LRASPPHead, lraspp_mobilenet_v3_large
-from .classification.swin import SwinTransformer, swin_b, swin_s, swin_t
+from .classification.swin import SwinTransformer, swin_b, swin_s, swin_t, swin_v2_b, swin_v2_s, swin_v2_t
 from .classification.vgg import VGG, vgg11, vgg11_bn, vgg13, vgg13_bn, vgg16, vgg16_bn, vgg19, vgg19_bn
 from .classification.vit import (
     _VitAttention,

@@ -1,12 +1,22 @@
-"""Swin Transformer V1 (reference models/classification/swin.py:23-66, 90-366, 526-578, 640-830).
+"""Swin Transformer V1 and V2 (reference models/classification/swin.py:23-946).
 
-Same fields / constructors.  V2 (cosine attention + cpb_mlp) is out of scope.
-Device lowering of one block (reference :572-578):
+Same fields / constructors.
+Device lowering of one V1 block (reference :572-578):
   LayerNorm2d rows | qkv GEMM(+bias) | window attention (roll / partition / bias / mask / softmax / PV /
   reverse folded into addressing) | proj GEMM(+bias,+residual) | LayerNorm2d | fc1 GEMM(+gelu) |
   fc2 GEMM(+residual)
 Feature maps stay NHWC, which is exactly the (H,W,C) view `_shifted_window_attention` transposes to
 (reference :106), so no transposes exist on the device.
+
+V2 (`_PatchMergingV2` :68-87, the logit_scale branch of `_shifted_window_attention` :144-168, `_ShiftedWindowAttentionV2`
+:369-522, `_SwinTransformerBlockV2` :581-635, factories :874-946) is post-norm with cosine logits.  One block in inference mode,
+on the fp32 stream and the bf16 plane the previous mv_layernorm_add_fwd wrote next to it:
+  qkv GEMM(+bias, key third zeroed) | mv_swin_qk_rnorm_fwd (1 / norm over the WINDOWS of an image: the reference's axis 0) |
+  mv_swin_window_attn_cos_fwd | proj GEMM(+bias) | mv_layernorm_add_fwd (x + norm1(.)) | fc1 GEMM(+gelu) | fc2 GEMM |
+  mv_layernorm_add_fwd (x + norm2(.))
+The continuous position bias (cpb_mlp on the log-spaced table, the reference's raw reshape, 16 sigmoid) and exp(min(logit_scale,
+log 100)) are weight preprocessing on the host (ops.swin_v2_operands).  A stage with ONE window per image (256 px: the last stage)
+turns q / norm into sign(q): see DESIGN.md section 3 on what that does to parity.
 """
 from __future__ import annotations
 
@@ -187,6 +197,205 @@ class _SwinTransformerBlock(Module):
         return ops.add(x, sd(m, key=keys[3]))
 
 
+def _refuse_grad_v2():
+    from ... import grad as _grad
+    if _grad.active():
+        # the cosine attention, the window norms and the post-norm residual step have no backward: refuse rather than return a
+        # gradient without them
+        raise NotImplementedError("Swin V2 was launched inside filter_value_and_grad by an op without a backward "
+                                  "(eqxvision_amd/grad.py lists what is differentiable)")
+
+
+class _PatchMergingV2(Module):
+    reduction: Linear2d
+    norm: Callable
+
+    def __init__(self, dim: int, norm_layer: Callable = LayerNorm2d, *, key=None):
+        self.norm = norm_layer(2 * dim)
+        self.reduction = Linear2d(4 * dim, 2 * dim, use_bias=False, key=key)
+
+    @boundary
+    def __call__(self, x, *, key=None):                                # reference :83-87: pad / gather, reduction, norm
+        _refuse_grad_v2()
+        x = ops.as_map(x)
+        x = ops.patch_merge_gather(ops.stream_plane(x) if x.t.dtype == ops.torch.float32 else x)      # the operand plane is what is gathered
+        if type(self.reduction) is Linear2d:      # produces the residual stream: split-precision weights (ops.linear_split)
+            z = ops.linear_split(x, self.reduction, out_fp32=ops.compute_dtype() == "bf16")
+        else:
+            z = self.reduction(x)
+        if isinstance(self.norm, nn.LayerNorm) and self.norm.weight is not None and self.norm.bias is not None:
+            return ops.layernorm_add(z, self.norm)
+        return self.norm(z)
+
+
+class _ShiftedWindowAttentionV2(Module):
+    window_size: List[int]
+    shift_size: List[int]
+    num_heads: int
+    attention_dropout: float
+    dropout: float
+    logit_scale: np.ndarray
+    relative_position_bias_table: np.ndarray
+    relative_position_index: np.ndarray
+    qkv: nn.Linear
+    proj: nn.Linear
+    cpb_mlp: nn.Sequential
+
+    def __init__(self, dim: int, window_size: List[int], shift_size: List[int], num_heads: int, qkv_bias: bool = True,
+                 proj_bias: bool = True, attention_dropout: float = 0.0, dropout: float = 0.0, *, key=None):
+        if len(window_size) != 2 or len(shift_size) != 2:
+            raise ValueError("window_size and shift_size must be of length 2")
+        keys = jr.split(key if key is not None else jr.PRNGKey(0), 3)
+        self.window_size = list(window_size)
+        self.shift_size = list(shift_size)
+        self.num_heads = num_heads
+        self.attention_dropout = attention_dropout
+        self.dropout = dropout
+        self.qkv = Linear2d(dim, dim * 3, use_bias=qkv_bias, key=keys[0])
+        self.proj = Linear2d(dim, dim, use_bias=proj_bias, key=keys[1])
+        self.relative_position_bias_table = self.define_relative_position_bias_table(key=keys[2])
+        self.relative_position_index = self.define_relative_position_index()
+        self.logit_scale = np.log(10 * np.ones((num_heads, 1, 1), np.float32)).astype(np.float32)       # reference :416
+        self.cpb_mlp = nn.Sequential([                                 # reference :418-426: keys[1] and keys[2] are re-used
+            nn.Lambda(partial(np.transpose, axes=(2, 0, 1))),
+            Linear2d(2, 512, use_bias=True, key=keys[1]),
+            nn.Lambda(nn.relu),
+            Linear2d(512, num_heads, use_bias=False, key=keys[2]),
+            nn.Lambda(partial(np.transpose, axes=(0, 1, 2))),
+        ])
+        if qkv_bias:                                                   # reference :427-433: the key third starts at zero
+            b = np.array(self.qkv.bias, np.float32)
+            n = b.size // 3
+            b[n:2 * n] = 0
+            self.qkv.bias = b
+
+    def define_relative_position_index(self):
+        # reference :435-456: the same quirk as V1 -- relative_coords.sum(-1) in [-(Wh+Ww-2), Wh+Ww-2]
+        ch, cw = np.arange(self.window_size[0]), np.arange(self.window_size[1])
+        coords = np.stack(np.meshgrid(ch, cw, indexing="ij")).reshape(2, -1)
+        rel = coords[:, :, None] - coords[:, None, :]
+        return rel.transpose(1, 2, 0).sum(-1).reshape(-1).astype(np.int32)
+
+    def define_relative_position_bias_table(self, key):
+        # reference :458-484: NOT a table of biases but the log-spaced relative coordinates (2Wh-1, 2Ww-1, 2) the cpb_mlp reads;
+        # the divisor is the window size (not size - 1) and the offset -1, as the reference has them
+        wh, ww = self.window_size
+        rh = np.arange(-(wh - 1), wh, dtype=np.float32)
+        rw = np.arange(-(ww - 1), ww, dtype=np.float32)
+        t = np.stack(np.meshgrid(rh, rw, indexing="ij")).transpose(1, 2, 0)
+        t = np.stack([t[:, :, 0] / np.float32(wh) - 1, t[:, :, 1] / np.float32(ww) - 1], axis=-1).astype(np.float32)
+        t = np.float32(8) * t
+        return (np.sign(t) * np.log2(np.abs(t) + np.float32(1.0)) / np.float32(3.0)).astype(np.float32)
+
+    def get_relative_position_bias(self) -> np.ndarray:
+        l1, l2 = ops._cpb_linears(self)
+        return ops.swin_v2_rel_bias_host(self.relative_position_bias_table, self.relative_position_index, l1.weight, l1.bias,
+                                         l2.weight, self.num_heads, self.window_size)
+
+    def _live(self) -> bool:
+        """`_func_dropout` (swin.py:17-20, 227, 233) has no inference switch: a non-zero rate drops in EVERY mode."""
+        return self.attention_dropout > 0 or self.dropout > 0
+
+    def _forward(self, x: Act, key=None, precise: Optional[bool] = None) -> Act:
+        """The attention branch WITHOUT the residual (the V2 block normalises it first): fp32 rows where the compute dtype is bf16
+        and nothing is dropped (they go straight into the LayerNorm), else the compute dtype."""
+        _refuse_grad_v2()
+        x = ops.as_map(x)
+        B, Hf, Wf, C = x.t.shape
+        if Hf % self.window_size[0] or Wf % self.window_size[1]:
+            raise ValueError(f"feature map {Hf}x{Wf} is not a multiple of the window {self.window_size} "
+                             "(the reference does not pad either, swin.py:782-790)")
+        if precise is None:
+            precise = ops.swin_precise(C)
+        lin = ops.linear_split if precise else ops.linear
+        plane = ops.stream_plane(x) if x.t.dtype == ops.torch.float32 else x
+        qkv = lin(plane, ops.swin_v2_qkv(self))                       # reference :144-153
+        bias, mul = ops.swin_v2_operands(self)
+        rn = ops.swin_qk_rnorm(qkv, self.window_size, self.shift_size)
+        if not self._live():
+            a = ops.swin_window_attention_cos(qkv, rn, mul, bias, self.num_heads, self.window_size, self.shift_size)
+            return lin(a, self.proj, out_fp32=ops.compute_dtype() == "bf16")      # reference :232
+        if key is None:
+            raise RuntimeError("Swin attention_dropout / dropout > 0 requires a key (drawn in every mode, swin.py:17-20)")
+        kd = ops._keys_dev(key, B)                                     # ONE key for both draws (reference :227, :233)
+        drop = (self.attention_dropout, kd) if self.attention_dropout > 0 else None
+        a = ops.swin_window_attention_cos(qkv, rn, mul, bias, self.num_heads, self.window_size, self.shift_size, drop=drop)
+        y = ops.linear(a, self.proj)
+        if self.dropout > 0:
+            y = ops.dropout_windows(y, self.dropout, kd, self.window_size, self.shift_size)
+        return y
+
+    @boundary
+    def __call__(self, x, *, key=None):
+        return self._forward(x, key=key)
+
+
+class _SwinTransformerBlockV2(Module):
+    norm1: Callable
+    attn: Module
+    stochastic_depth: DropPath
+    norm2: Callable
+    mlp: MlpProjection
+
+    def __init__(self, dim: int, num_heads: int, window_size: List[int], shift_size: List[int], mlp_ratio: float = 4.0,
+                 dropout: float = 0.0, attention_dropout: float = 0.0, stochastic_depth_prob: float = 0.0,
+                 norm_layer: Callable[..., Module] = LayerNorm2d,
+                 attn_layer: Callable[..., Module] = _ShiftedWindowAttentionV2, *, key=None):
+        keys = jr.split(key if key is not None else jr.PRNGKey(0), 2)
+        self.norm1 = norm_layer(dim)
+        self.attn = attn_layer(dim, window_size, shift_size, num_heads, attention_dropout=attention_dropout,
+                               dropout=dropout, key=keys[0])
+        self.stochastic_depth = DropPath(stochastic_depth_prob, mode="local")
+        self.norm2 = norm_layer(dim)
+        self.mlp = MlpProjection(dim, int(dim * mlp_ratio), dim, lin_layer=Linear2d, act_layer=nn.gelu, drop=dropout,
+                                 key=keys[1])
+
+    @boundary
+    def __call__(self, x, *, key=None):                                # reference :629-635: x + sd(norm(branch(x))), twice
+        _refuse_grad_v2()
+        x = ops.as_map(x)
+        if x.t.dtype != ops.torch.float32:                             # the V2 stream is fp32 in every mode
+            x = ops.cast(x, "fp32")
+        sd = self.stochastic_depth
+        sd_live = not (sd.inference or sd.p == 0.0)
+        attn_live = bool(getattr(self.attn, "_live", lambda: False)())
+        mlp_live = isinstance(self.mlp, MlpProjection) and self.mlp._live()
+        v2_attn = type(self.attn) is _ShiftedWindowAttentionV2
+        plain_mlp = (isinstance(self.mlp, MlpProjection) and not mlp_live and nn.act_name(self.mlp.act) is not None
+                     and isinstance(self.mlp.fc1, nn.Linear))
+        affine = all(isinstance(n, nn.LayerNorm) and n.weight is not None and n.bias is not None for n in (self.norm1, self.norm2))
+        live = sd_live or attn_live or mlp_live
+        if live and key is None:
+            raise RuntimeError("stochastic depth outside inference mode / Swin dropout > 0 requires a key")
+        # keys as the reference splits them (:630): attention, path, MLP, path; nothing draws when nothing is live
+        keys = jr.split(ops._batched_keys(key, x.t.shape[0]), 4) if live else [None] * 4
+        # block Linears with split-precision weights exactly where V1 takes them (swin_v2_b's widths, the 18-block stages), in the
+        # fused and in the literal composition alike
+        precise = ops.swin_precise(x.t.shape[-1]) or (getattr(self, "_deep_stage", False) and ops.swin_precise(0))
+        lin = ops.linear_split if precise else ops.linear
+        f32_out = ops.compute_dtype() == "bf16"
+
+        def mlp_branch(x):
+            if plain_mlp:                                              # fp32 rows out: they go straight into the LayerNorm
+                h = lin(ops.stream_plane(x), self.mlp.fc1, act=nn.act_name(self.mlp.act))
+                return lin(h, self.mlp.fc2, out_fp32=f32_out)
+            if isinstance(self.mlp, MlpProjection):
+                return self.mlp._forward(x, keys=keys[2], precise=precise) if mlp_live else self.mlp._forward(x, precise=precise)
+            return self.mlp(x, key=keys[2])
+
+        a = self.attn._forward(x, key=keys[0], precise=precise) if v2_attn else self.attn(x, key=keys[0])
+        if not sd_live and not attn_live and affine and v2_attn and plain_mlp:
+            x = ops.layernorm_add(a, self.norm1, res=x)               # inference: 8 launches per block
+            return ops.layernorm_add(mlp_branch(x), self.norm2, res=x)
+        # training mode / non-zero dropout rates: the literal composition
+        x = ops.add(x, sd(self._norm_f32(self.norm1, a), key=keys[1]))
+        return ops.add(x, sd(self._norm_f32(self.norm2, mlp_branch(x)), key=keys[3]))
+
+    @staticmethod
+    def _norm_f32(norm, z):
+        return ops.layernorm(z, norm, out_fp32=True) if isinstance(norm, nn.LayerNorm) else norm(z)
+
+
 class SwinTransformer(Module):
     features: nn.Sequential
     norm: Callable
@@ -259,6 +468,9 @@ class SwinTransformer(Module):
 
     @boundary
     def __call__(self, x, *, key=None):                                # reference :760-772
+        if any(isinstance(l, _PatchMergingV2) or (isinstance(l, nn.Sequential) and len(l) and isinstance(l.layers[0], _SwinTransformerBlockV2))
+               for l in self.features.layers):
+            _refuse_grad_v2()
         x = self._features(x, None if key is None else jr.split(key, 2)[0])
         if head_fp32() and isinstance(self.norm, nn.LayerNorm) and type(self.avgpool) is nn.AdaptiveAvgPool2d:
             x = ops.layernorm(x, self.norm, out_fp32=True)             # reference :768-771 with fp32 features
@@ -291,3 +503,18 @@ def swin_s(torch_weights: str = None, **kwargs: Any) -> SwinTransformer:
 
 def swin_b(torch_weights: str = None, **kwargs: Any) -> SwinTransformer:
     return _swin_transformer("swin_b", [4, 4], 128, [2, 2, 18, 2], [4, 8, 16, 32], [7, 7], 0.5, torch_weights, **kwargs)
+
+
+def swin_v2_t(torch_weights: str = None, **kwargs: Any) -> SwinTransformer:
+    return _swin_transformer("swin_v2_t", [4, 4], 96, [2, 2, 6, 2], [3, 6, 12, 24], [8, 8], 0.2, torch_weights,
+                             block=_SwinTransformerBlockV2, downsample_layer=_PatchMergingV2, **kwargs)
+
+
+def swin_v2_s(torch_weights: str = None, **kwargs: Any) -> SwinTransformer:
+    return _swin_transformer("swin_v2_s", [4, 4], 96, [2, 2, 18, 2], [3, 6, 12, 24], [8, 8], 0.3, torch_weights,
+                             block=_SwinTransformerBlockV2, downsample_layer=_PatchMergingV2, **kwargs)
+
+
+def swin_v2_b(torch_weights: str = None, **kwargs: Any) -> SwinTransformer:
+    return _swin_transformer("swin_v2_b", [4, 4], 128, [2, 2, 18, 2], [4, 8, 16, 32], [8, 8], 0.5, torch_weights,
+                             block=_SwinTransformerBlockV2, downsample_layer=_PatchMergingV2, **kwargs)

@@ -1498,6 +1498,137 @@ def dropout_windows(x: Act, p: float, key, window, shift) -> Act:
     return Act(y, "map", x.batched)
 
 
+# ------------------------------------------------------------------ Swin V2 (models/classification/swin.py, reference :68-87, :144-168, :369-522, :581-635)
+def swin_v2_fused() -> bool:
+    """Library switch "no_swin_v2_fused": V2 blocks and patch merging on the literal composition (LayerNorm, add and cast launches
+    instead of mv_layernorm_add_fwd) -- the A/B of tools/ab_flag.py / tools/time_swin_v2.py and the tests' cross-check."""
+    return not _lib.get_flag("no_swin_v2_fused")
+
+
+def swin_v2_rel_bias_host(table, index, w1, b1, w2, heads: int, window) -> np.ndarray:
+    """`_ShiftedWindowAttentionV2.get_relative_position_bias` (reference :486-495) on the host, fp32 numpy: the cpb_mlp
+    (transpose, Linear2d(2, 512), relu, Linear2d(512, heads, no bias): :418-426) on the log-spaced coordinate table gives
+    (heads, 2Wh-1, 2Ww-1); that array is reshaped RAW to (-1, heads) -- not transposed: the reference mixes heads and positions,
+    and so does this -- gathered by the index (negative entries wrap), laid out (heads, n, n) and mapped through 16 * sigmoid."""
+    t = np.asarray(table, np.float32).reshape(-1, 2)
+    hid = np.maximum(t @ np.asarray(w1, np.float32).T + np.asarray(b1, np.float32).reshape(1, -1), np.float32(0))
+    out = np.ascontiguousarray((hid @ np.asarray(w2, np.float32).T).T)          # (heads, (2Wh-1)(2Ww-1)): the MLP's output layout
+    raw = out.reshape(-1, heads)                                                # reference :488-490
+    n = int(window[0]) * int(window[1])
+    idx = np.asarray(index).reshape(-1).astype(np.int64)
+    b = np.ascontiguousarray(raw[idx].reshape(n, n, heads).transpose(2, 0, 1))  # reference :34-43
+    return (np.float32(16) / (np.float32(1) + np.exp(-b))).astype(np.float32)
+
+
+def _cpb_linears(attn):
+    lins = [m for m in attn.cpb_mlp.layers if hasattr(m, "weight")]
+    if len(lins) != 2 or lins[0].bias is None or lins[1].bias is not None:
+        raise ValueError("cpb_mlp must be Linear2d(2, hidden) -> relu -> Linear2d(hidden, heads, use_bias=False) (reference :418-426)")
+    return lins
+
+
+def swin_v2_operands(attn):
+    """(bias [heads][n][n], logit_mul [heads]) of a _ShiftedWindowAttentionV2 on the device -- weight preprocessing like the
+    LayerNorm folding of swin_block_attention -- cached on the module, keyed by the identities of the leaves they are made of."""
+    l1, l2 = _cpb_linears(attn)
+    leaves = (l1.weight, l1.bias, l2.weight, attn.logit_scale, attn.relative_position_index, attn.relative_position_bias_table)
+    key = ("v2_operands",) + tuple(id(a) for a in leaves)
+    cache = attn._cache()
+    hit = cache.get(key)
+    if hit is None:
+        bias = swin_v2_rel_bias_host(attn.relative_position_bias_table, attn.relative_position_index, l1.weight, l1.bias, l2.weight,
+                                     attn.num_heads, attn.window_size)
+        ls = np.asarray(attn.logit_scale, np.float32).reshape(-1)
+        mul = np.exp(np.minimum(ls, np.float32(np.log(100.0)))).astype(np.float32)       # reference :165-167
+        hit = (_dev(bias, torch.float32), _dev(mul, torch.float32), leaves)              # leaves: keeps the ids alive
+        cache[key] = hit
+    return hit[0], hit[1]
+
+
+def swin_v2_rel_bias(attn) -> torch.Tensor:
+    return swin_v2_operands(attn)[0]
+
+
+def swin_v2_qkv(attn):
+    """The qkv Linear2d as the reference applies it in the V2 attention: the key third of the bias is zeroed on EVERY call
+    (:144-150), whatever the leaf holds (a checkpoint may carry a non-zero one).  A shadow layer sharing the weight, cached on the
+    module; the module's own leaf stays as it is."""
+    lin = attn.qkv
+    if lin.bias is None:
+        return lin
+    key = ("v2_qkv", id(lin.weight), id(lin.bias))
+    cache = attn._cache()
+    hit = cache.get(key)
+    if hit is None:
+        from ._module import tree_at
+        b = np.array(np.asarray(lin.bias, np.float32))
+        n = b.size // 3
+        b.reshape(-1)[n:2 * n] = 0
+        hit = (tree_at(lambda l: l.bias, lin, b), lin.weight, lin.bias)
+        cache[key] = hit
+    return hit[0]
+
+
+def swin_qk_rnorm(qkv: Act, window, shift) -> torch.Tensor:
+    """fp32 [B][2][n][C]: 1 / norm of q and k over the windows of each image (reference :161-163, axis 0)."""
+    B, Hf, Wf, C3 = qkv.t.shape
+    C = C3 // 3
+    rn = empty((B, 2, int(window[0]) * int(window[1]), C), torch.float32)
+    _lib.call("mv_swin_qk_rnorm_fwd", _ptr(qkv.t), _ptr(rn), B, Hf, Wf, C, int(window[0]), int(window[1]), int(shift[0]), int(shift[1]),
+              qkv.dt, stream_ptr())
+    return rn
+
+
+def swin_window_attention_cos(qkv: Act, rnorm: torch.Tensor, logit_mul: torch.Tensor, bias: torch.Tensor, heads: int, window, shift,
+                              drop=None) -> Act:
+    """The V2 attention core (reference :159-173, then as V1).  `drop` = (p, per-sample keys): the attention dropout of :227."""
+    B, Hf, Wf, C3 = qkv.t.shape
+    C = C3 // 3
+    out = empty((B, Hf, Wf, C), qkv.t.dtype)
+    keys, keep = None, 1.0
+    if drop is not None:
+        p, key = drop
+        if not 0.0 < float(p) < 1.0:
+            raise NotImplementedError(f"Swin attention_dropout = {p}")
+        keys, keep = _keys_dev(key, B), float(1.0 - p)
+    _lib.call("mv_swin_window_attn_cos_fwd", _ptr(qkv.t), _ptr(rnorm), _ptr(logit_mul), _ptr(bias), _ptr(out), _ptr(keys), keep,
+              B, Hf, Wf, C, heads, int(window[0]), int(window[1]), int(shift[0]), int(shift[1]), qkv.dt, stream_ptr())
+    return Act(out, "map", qkv.batched)
+
+
+_LO = object()      # Act.pre = (_LO, plane): `plane` holds the same rows rounded once to the compute dtype (mv_layernorm_add_fwd's y_lo)
+
+
+def stream_plane(x: Act) -> Act:
+    """The fp32 stream's rows in the compute dtype: the plane written next to them, or one cast launch."""
+    if x.pre is not None and x.pre[0] is _LO:
+        return x.pre[1]
+    return cast(x, compute_dtype())
+
+
+def layernorm_add(z: Act, ln, res: Optional[Act] = None) -> Act:
+    """res + ln(z) as the fp32 stream (reference :629-635, :83-87), one launch; in bf16 mode the bf16 plane the next Linear reads is
+    written by the same launch (`stream_plane`).  With "no_swin_v2_fused": LayerNorm, add, and the consumer's cast."""
+    z = as_map(z)
+    C = z.t.shape[-1]
+    if int(np.prod(ln.shape)) != C or ln.weight is None or ln.bias is None:
+        raise ValueError(f"layernorm_add: an affine LayerNorm over {C} channels is required, got {ln.shape}")
+    if res is not None and (tuple(res.t.shape) != tuple(z.t.shape) or res.t.dtype != torch.float32):
+        raise ValueError(f"layernorm_add: the residual must be the fp32 stream of z's shape: {res} vs {z}")
+    if not swin_v2_fused():
+        y = layernorm(z, ln, out_fp32=True)
+        return y if res is None else add(res, y)
+    dt = compute_dtype()
+    y = empty(tuple(z.t.shape), torch.float32)
+    lo = empty(tuple(z.t.shape), TORCH_DT[dt]) if dt != "fp32" else None
+    _lib.call("mv_layernorm_add_fwd", _ptr(z.t), _ptr(None if res is None else res.t), _ptr(prep_f32(ln, "weight", ln.weight)),
+              _ptr(prep_f32(ln, "bias", ln.bias)), _ptr(y), _ptr(lo), z.t.numel() // C, C, float(ln.eps), z.dt, DT[dt], stream_ptr())
+    out = Act(y, "map", z.batched)
+    if lo is not None:
+        out.pre = (_LO, Act(lo, "map", z.batched))
+    return out
+
+
 def resize_bilinear(x: Act, size, final: bool = False) -> Act:
     """jax.image.resize(x, (C,) + size, "bilinear") of a feature map (up-sampling).  `final`: the result is what the caller of the
     model receives -> written directly as fp32 NCHW; otherwise an NHWC map in the compute dtype for further layers."""

@@ -57,7 +57,10 @@ enum { MV_OK = 0, MV_E_INVALID = -1, MV_E_UNSUPPORTED = -2, MV_E_OOM = -3 };
  *   whole blocks    "no_bneck_tail",
  *                   "no_ln_mlp", "ln_mlp_waves" (8 / 12 / 16), "no_ln_mlp_stream" (both also govern the _res entries),
  *                   "no_swin_block_attn", "swin_c96_shared" (the two-windows-per-workgroup kernel at C = 96), "no_patch_merge_ln",
- *                   "no_patch4_ln", "no_fc_stream", "no_cnblock_dw" (ConvNeXt blocks on the composition of the generic entries)
+ *                   "no_patch4_ln", "no_fc_stream", "no_cnblock_dw" (ConvNeXt blocks on the composition of the generic entries),
+ *                   "no_swin_v2_fused" (host: Swin V2 blocks and patch merging on the literal composition -- LayerNorm, add and cast
+ *                   launches instead of mv_layernorm_add_fwd; A/B with tools/time_swin_v2.py -- tools/ab_flag.py feeds 224 px images,
+ *                   which 8 x 8 windows do not divide)
  *   entry / misc    "stem_v0", "no_stem_pool", "no_stem_pool11", "no_patch_f32out", "no_ln_slim", "no_grouped64", "no_dwconv",
  *                   "dwconv_generic", "dwconv_no_tile", "dwconv_tile3", "no_oddc", "no_se_fused", "se_fused_always", "eltwise_scalar",
  *                   "affine_scalar", "dropout_x8", "dropout_scalar", "no_f32_mfma" (fp32 contractions back on the VALU kernel), "no_f32_lds" (only the direct fp32 matrix-core kernel), "no_attn_f32_lds" (fp32 attention back on the one-wave-per-query kernels),
@@ -610,6 +613,31 @@ int mv_swin_window_attn_dropout_fwd(const void* qkv, const float* bias, void* ou
                                     int dtype, mv_stream_t stream);
 int mv_dropout_windows_fwd(const void* x, const void* keys, void* y, int B, int Hf, int Wf, int C, int ws_h, int ws_w,
                            int shift_h, int shift_w, float keep_prob, int dtype, mv_stream_t stream);
+
+/* Swin V2's cosine attention (`_shifted_window_attention` with logit_scale, swin.py:144-168; `_ShiftedWindowAttentionV2` :369-522).
+ * mv_swin_qk_rnorm_fwd: the reference divides q and k, shaped (nW, heads, n, dh), by jnp.linalg.norm(., ord=2, axis=0) (:161-163):
+ * axis 0 is the WINDOWS of one image.  rnorm fp32 [B][2][n][C] (s = 0: q, s = 1: k; n = ws_h * ws_w) =
+ * 1 / sqrt(sum over the nW windows w of x_s[w][t][c]^2) on the rolled, partitioned map (the token walk of mv_swin_window_attn_fwd);
+ * fp32 accumulation in increasing window order; the value third of qkv is never read.  A map that is not a multiple of the window,
+ * or C that is not a whole number of 16-byte chunks: MV_E_UNSUPPORTED.  A zero norm gives inf, as the reference's division does.
+ * mv_swin_window_attn_cos_fwd: the attention core with logits (q * rnorm_q) . (k * rnorm_k)^T * logit_mul[h] + bias (:161-173; no
+ * dh^-0.5): logit_mul fp32 [heads] = exp(min(logit_scale, log 100)) (:165-167), bias fp32 [heads][n][n] = 16 sigmoid(cpb_mlp(..))
+ * gathered on the host (:486-495).  bf16 with 32 channels per head and n <= 64 runs on the MFMA kernel (the scaled q / k fragments
+ * are rounded once to bf16); everything else on the one-wave-per-query kernel.  keys != NULL: the reference's attention dropout
+ * (:227) as in mv_swin_window_attn_dropout_fwd, MFMA path only, else MV_E_UNSUPPORTED; keys NULL: keep_prob is ignored. */
+int mv_swin_qk_rnorm_fwd(const void* qkv, float* rnorm, int B, int Hf, int Wf, int C, int ws_h, int ws_w, int shift_h,
+                         int shift_w, int dtype, mv_stream_t stream);
+int mv_swin_window_attn_cos_fwd(const void* qkv, const float* rnorm, const float* logit_mul, const float* bias, void* out,
+                                const void* keys, float keep_prob, int B, int Hf, int Wf, int C, int heads, int ws_h, int ws_w,
+                                int shift_h, int shift_w, int dtype, mv_stream_t stream);
+
+/* The post-norm residual step of `_SwinTransformerBlockV2` (swin.py:629-635: x + norm(branch(x))) and the norm of `_PatchMergingV2`
+ * (:83-87, res = NULL):  y[m][:] = res[m][:] + gamma * n(z[m][:]) + beta  over M rows of C; z bf16 / fp32 (z_dtype), res fp32 or
+ * NULL, y fp32.  y_lo (lo_dtype, or NULL): the same row rounded once (round-to-nearest-even) -- the operand plane of the next
+ * Linear, so the fp32 stream needs no cast launch.  C a whole number of 16-byte chunks of z, at most 512 of them (96 .. 1024 and
+ * beyond), else MV_E_UNSUPPORTED. */
+int mv_layernorm_add_fwd(const void* z, const float* res, const float* gamma, const float* beta, float* y, void* y_lo, int64_t M,
+                         int C, float eps, int z_dtype, int lo_dtype, mv_stream_t stream);
 
 /* _patch_merging_pad (swin.py:23-31): NHWC [B,H,W,C] -> [B,H/2,W/2,4C], channel blocks
  * [x(0::2,0::2) | x(1::2,0::2) | x(0::2,1::2) | x(1::2,1::2)], zero pad odd H/W. */
