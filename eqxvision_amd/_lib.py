@@ -168,6 +168,8 @@ PROTOTYPES = {
     "mv_swin_window_attn_bwd_f32": [_vp] * 5 + [_i] * 9 + [_vp],
     "mv_scatter_rows_sum_f32": [_vp, _vp, _vp, _i, _i, _i, _vp],
     "mv_patch_merge_gather_bwd_f32": [_vp, _vp, _i, _i, _i, _i, _vp],
+    "mv_resize_bilinear_bwd_nhwc_f32": [_vp, _vp] + [_i] * 7 + [_vp],
+    "mv_softmax_xent_map_f32": [_vp] * 6 + [_i, _i, _i64, _vp],
     "mv_graph_begin_capture": [_vp],
     "mv_graph_end_capture": [_vp, C.POINTER(_vp)],
     "mv_graph_launch": [_vp, _vp],
@@ -301,6 +303,9 @@ def check_device_status(clear: bool = True) -> int:
     if rc != 0:
         msg = load().mv_last_error()
         raise MVError(f"mv_device_status failed (rc={rc}): {msg.decode() if msg else ''}")
+    if v.value & 2:
+        raise MVError(f"device status 0x{v.value:x}: mv_softmax_xent_map_f32 met a label outside [0, classes) on a counted pixel; the "
+                      "pixel was left out of the loss and its gradient")
     if v.value:
         raise MVError(f"device status 0x{v.value:x}: a split-K tile was finished without its partner's partial sums -- the scratch of "
                       "mv_set_scratch was shared by concurrent launches or not zero-initialised; results of that launch are wrong")

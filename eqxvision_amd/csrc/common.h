@@ -220,6 +220,7 @@ int chain_stream_supported(long long M, int C, int K, int N2, int dtype);
 int chain_stream_launch(const void* x, const void* w3, const float* scale3, const float* shift3, const void* residual, void* y,
                         const void* w1, const float* scale1, const float* shift1, void* t1, long long M, hipStream_t st);
 int device_status(int clear, unsigned* out);              // igemm8.hip: the status word of mv_device_status
+unsigned* device_status_word();                           // its device address (nullptr if the runtime cannot give it)
 int igemm8_launch(const void* x, const void* w, const float* scale, const float* shift, const void* residual, void* y,
                   const ConvShape& s, int tok, int tile, hipStream_t st);       // tile: 1 = 256x256, 2 = 128x256, 3 = 256x128
 bool igemm8_ln_supported(long long M, int N, int K);

@@ -40,7 +40,8 @@ namespace {
 
 constexpr unsigned OOB = 0x80000000u;          // >= num_records of every descriptor: the DMA writes zeros
 
-// Device status word (mv_device_status): bit 0 = a split-K block gave up waiting for its partner's partial tile.  A kernel that
+// Device status word (mv_device_status): bit 0 = a split-K block gave up waiting for its partner's partial tile; bit 1 = a counted
+// pixel of mv_softmax_xent_map_f32 had a label outside [0, C) (seg_bwd.hip, through device_status_word()).  A kernel that
 // finds its hand-over broken RECORDS it here and finishes with what it has -- it does not trap: a trap is a sticky
 // hipErrorLaunchFailure that poisons the whole context (an in-flight graph replay, other streams) and surfaces at an unrelated
 // call (advisor, round 5).  The host reads the word at its own synchronisation points and fails with a clear message.
@@ -779,6 +780,16 @@ int device_status(int clear, unsigned* out) {
     }
     *out = v;
     return MV_OK;
+}
+
+// the word's address on the current device, for kernels of other translation units (a __device__ variable is private to its own)
+unsigned* device_status_word() {
+    void* p = nullptr;
+    if (hipGetSymbolAddress(&p, HIP_SYMBOL(g_dev_status)) != hipSuccess) {
+        (void)hipGetLastError();
+        return nullptr;
+    }
+    return (unsigned*)p;
 }
 
 size_t splitk_scratch_bytes(long long M, long long N, long long kred) {

@@ -24,7 +24,11 @@ that state outside the differentiated pytree: the gradient treats the statistics
 Scope: the layers of alexnet / vgg / resnet / resnext (basic and bottleneck, un-fused) / mobilenet v2 + v3 / efficientnet / regnet /
 vit: Conv2d (any groups), Linear, BatchNorm, LayerNorm, every MV_ACT_* activation, MaxPool2d, AdaptiveAvgPool2d to (1,1) or to the
 input size, Dropout, DropPath, SqueezeExcitation (un-fused: pool, two pointwise convolutions, channel scale), attention, cls /
-position embeddings, Swin's shifted-window attention (with the relative-position bias table's gradient) and patch merging."""
+position embeddings, Swin's shifted-window attention (with the relative-position bias table's gradient) and patch merging; and the
+dense-prediction models fcn / deeplabv3 / lraspp_mobilenet_v3_large: bilinear up-sampling (`g_resize_bilinear`, its adjoint is
+mv_resize_bilinear_bwd_nhwc_f32), channel concatenation (`g_concat_channels`), the `(aux, out)` tuple they return through `vmap`,
+and the per-pixel loss `softmax_cross_entropy_with_integer_labels(out, labels, axis=1, where=...)` (mv_softmax_xent_map_f32), whose
+scalars combine as `loss(out) + 0.4 * loss(aux)`."""
 from __future__ import annotations
 
 import functools
@@ -774,11 +778,63 @@ def g_patch_merge_gather(x: Act) -> Act:
     return _mk(y, "map", x.batched, [_node(x)], backward)
 
 
+# ------------------------------------------------------------------------------------------------------------ dense prediction
+@_op
+def g_resize_bilinear(x: Act, size, final: bool = False) -> Act:
+    """ops.resize_bilinear in fp32: `final` -> the NCHW "img" the caller of the model receives, else an NHWC map (the input itself
+    when the size does not change).  The backward is the adjoint kernel, reading the gradient in the layout the forward wrote."""
+    x = g_as_map.__wrapped__(x)
+    B, h, w, C = x.t.shape
+    H, W = int(size[0]), int(size[1])
+    if not final and (H, W) == (h, w):
+        return x
+    nchw = 1 if final else 0
+    y = _new((B, C, H, W) if final else (B, H, W, C))
+    _call("mv_resize_bilinear_nhwc_fwd", _p(x.t), _p(y), B, h, w, C, H, W, F32, F32, nchw, _S())
+
+    def backward(g):
+        dx = _new((B, h, w, C))
+        _call("mv_resize_bilinear_bwd_nhwc_f32", _p(g), _p(dx), B, h, w, C, H, W, nchw, _S())
+        return (dx,)
+    return _mk(y, "img" if final else "map", x.batched, [_node(x)], backward)
+
+
+@_op
+def g_concat_channels(xs) -> Act:
+    """ops.concat_channels: one mv_copy_rows per map into its channel slice; the backward copies every parent's slice back out of the
+    gradient (parents that are not on the tape get none)."""
+    maps = [g_as_map.__wrapped__(x) for x in xs]
+    B, H, W, _ = maps[0].t.shape
+    for m in maps:
+        if tuple(m.t.shape[:3]) != (B, H, W):
+            raise ValueError(f"concat_channels: mismatched maps {[tuple(m.t.shape) for m in maps]}")
+    widths = [int(m.t.shape[3]) for m in maps]
+    ctot, rows = sum(widths), B * H * W
+    y = _new((B, H, W, ctot))
+    off = 0
+    for m, c in zip(maps, widths):
+        _call("mv_copy_rows", _p(m.t), y.data_ptr() + 4 * off, rows, 4 * c, 4 * c, 4 * ctot, _S())
+        off += c
+    nodes = [_node(m) for m in maps]
+
+    def backward(g):
+        out, off = [], 0
+        for n, c in zip(nodes, widths):
+            d = None
+            if n is not None:
+                d = _new((B, H, W, c))
+                _call("mv_copy_rows", g.data_ptr() + 4 * off, _p(d), rows, 4 * c, 4 * ctot, 4 * c, _S())
+            out.append(d)
+            off += c
+        return tuple(out)
+    return _mk(y, "map", maps[0].batched, nodes, backward)
+
+
 # ------------------------------------------------------------------------------------------------------------ the transform
 HOOKED = ("as_map", "as_rows", "cast", "flatten", "first_row", "eltwise", "add", "dropout", "drop_path", "channel_scale", "maxpool2d",
           "adaptive_avgpool2d", "batchnorm", "conv2d", "stem_conv_pool", "linear", "linear_head", "layernorm", "ln_linear",
           "layernorm_first_row", "prep_f32", "patch_embed_tokens", "qkv_attention", "swin_rel_bias", "swin_window_attention",
-          "patch_merge_gather")
+          "patch_merge_gather", "resize_bilinear", "concat_channels")
 
 
 def hook(name: str, orig: Callable) -> Callable:
@@ -808,8 +864,41 @@ class GTensor:
         return tuple(self.act.t.shape)
 
 
+def _launching(fn, *a):
+    """fn(*a) with its C-ABI calls allowed under the tape (the loss functions and `Scalar` arithmetic are not ops.* entries)."""
+    t = tape()
+    if t is None:
+        return fn(*a)
+    t.inside += 1
+    try:
+        return fn(*a)
+    finally:
+        t.inside -= 1
+
+
+def _scale(x: torch.Tensor, f: float) -> torch.Tensor:
+    y = _new(x.shape)
+    s = torch.full((1,), float(f), dtype=torch.float32, device=device())
+    _call("mv_channel_affine_fwd", _p(x), _p(s), None, _p(y), x.numel(), 1, _lib.ACT_NONE, F32, _S())
+    return y
+
+
+def _seed(g) -> float:
+    """The gradient that reaches a scalar's node: None (the implicit 1 of the root) or the product of the factors on the way."""
+    return 1.0 if g is None else float(g)
+
+
+def _seeded(d: torch.Tensor, f: float) -> torch.Tensor:
+    return d if f == 1.0 else _scale(d, f)
+
+
+def _scalar_node(parents, backward) -> Optional[Node]:
+    return Node(parents, backward) if active() and any(p is not None for p in parents) else None
+
+
 class Scalar:
-    """A differentiable device scalar (the loss)."""
+    """A differentiable device scalar (the loss).  `a + b`, `a * 0.4` and `0.4 * a` give one differentiable scalar; the backward pass
+    seeds each branch with its factor."""
 
     def __init__(self, t: torch.Tensor, node: Optional[Node]):
         self.t, self.node = t, node
@@ -820,6 +909,20 @@ class Scalar:
     def item(self) -> float:
         return float(self.t.reshape(-1)[0].item())
 
+    def __add__(self, other):
+        if not isinstance(other, Scalar):
+            return NotImplemented
+        t = _launching(_add, self.t.reshape(1), other.t.reshape(1))
+        return Scalar(t, _scalar_node([self.node, other.node], lambda g: (_seed(g), _seed(g))))
+
+    def __mul__(self, f):
+        if isinstance(f, bool) or not isinstance(f, (int, float)):
+            return NotImplemented
+        f = float(f)
+        return Scalar(_launching(_scale, self.t.reshape(1), f), _scalar_node([self.node], lambda g: (_seed(g) * f,)))
+
+    __rmul__ = __mul__
+
 
 class _Rows:
     """Per-sample losses; `.mean()` is the scalar the reference differentiates (tests/test_grads.py:41)."""
@@ -829,6 +932,30 @@ class _Rows:
 
     def mean(self) -> Scalar:
         return Scalar(self._mean, self.node)
+
+
+class _PixelLosses:
+    """Per-element losses of `softmax_cross_entropy_with_integer_labels` on a map, shape [B, H, W], 0 where `where` masks.  `.mean()`
+    divides by the number of ALL elements, masked ones counting as 0 (optax's `where`); `.sum()` does not divide."""
+
+    def __init__(self, losses: torch.Tensor, sums: torch.Tensor, dl: torch.Tensor, parent: Optional[Node]):
+        self.losses, self._sums, self._dl, self._parent = losses, sums, dl, parent
+
+    @property
+    def counted(self) -> int:
+        """Number of pixels that `where` left in (synchronises)."""
+        return int(self._sums[1].item())
+
+    def _reduced(self, f: float) -> Scalar:
+        dl = self._dl                                   # the gradient of the SUM of the losses; the seed carries the 1 / n of a mean
+        t = self._sums[0:1] if f == 1.0 else _launching(_scale, self._sums[0:1], f)
+        return Scalar(t, _scalar_node([self._parent], lambda g: (_seeded(dl, _seed(g) * f),)))
+
+    def mean(self) -> Scalar:
+        return self._reduced(1.0 / self.losses.numel())
+
+    def sum(self) -> Scalar:
+        return self._reduced(1.0)
 
 
 def one_hot(labels, num_classes: int) -> np.ndarray:
@@ -858,10 +985,60 @@ def softmax_cross_entropy(logits, targets) -> _Rows:
             t.inside -= 1
     node = None
     if t is not None and act is not None and _node(act) is not None:
-        def backward(g):                       # g: the incoming scalar gradient (1 for the loss itself)
-            return (dl,)
+        def backward(g):                       # g: the incoming scalar gradient (None = 1, the loss itself; else its factor)
+            return (_seeded(dl, _seed(g)),)
         node = Node([_node(act)], backward)
     return _Rows(rows, mean, node)
+
+
+def softmax_cross_entropy_with_integer_labels(logits, labels, axis: int = -1, where=None):
+    """optax.softmax_cross_entropy_with_integer_labels: per-element -log_softmax(logits)[label] over the class axis.
+    [B, classes] logits with axis=-1: today's per-sample loss (`softmax_cross_entropy` on the one-hot of `labels`).
+    [B, classes, H, W] logits with axis=1 -- what the segmentation models return -- and labels [B, H, W]: one loss per pixel, 0 where
+    the optional boolean `where` [B, H, W] is false; `.mean()` averages over ALL pixels, `.sum()` adds them.  A label outside
+    [0, classes) on a counted pixel is refused (on a masked pixel it is ignored: the 255 of the VOC void convention)."""
+    act = logits.act if isinstance(logits, GTensor) else None
+    shape = tuple(act.t.shape) if act is not None else tuple(np.shape(logits))
+    if len(shape) == 2 and axis in (-1, 1):
+        if where is not None:
+            raise ValueError("softmax_cross_entropy_with_integer_labels: `where` is supported for [B, classes, H, W] logits only")
+        if int(np.size(labels)) != shape[0]:
+            raise ValueError(f"softmax_cross_entropy_with_integer_labels: {shape[0]} rows of logits, labels of shape {tuple(np.shape(labels))}")
+        return softmax_cross_entropy(logits, one_hot(labels, shape[1]))
+    if len(shape) != 4 or axis not in (1, -3):
+        raise ValueError(f"softmax_cross_entropy_with_integer_labels: logits of shape {shape} with axis={axis}; supported are "
+                         "[B, classes] with axis=-1 and [B, classes, H, W] with axis=1")
+    if act is not None and act.kind != "img":
+        raise ValueError(f"softmax_cross_entropy_with_integer_labels: expected the [B, classes, H, W] result of a model, got {act}")
+    B, C, H, W = shape
+    on_device =isinstance(labels, torch.Tensor) and labels.is_cuda
+    if tuple(labels.shape if on_device else np.shape(labels)) != (B, H, W):
+        raise ValueError(f"softmax_cross_entropy_with_integer_labels: logits {shape} need labels of shape {(B, H, W)}, got "
+                         f"{tuple(np.shape(labels))}")
+    mask = None
+    if where is not None:
+        mask = where.detach().cpu().numpy() if isinstance(where, torch.Tensor) else np.asarray(where)
+        if tuple(mask.shape) != (B, H, W):
+            raise ValueError(f"softmax_cross_entropy_with_integer_labels: `where` of shape {tuple(mask.shape)}, expected {(B, H, W)}")
+        mask = np.ascontiguousarray(mask != 0)
+    if on_device:
+        lab = labels.to(torch.int32).contiguous()
+    else:
+        lab_h = np.rint(np.asarray(labels.cpu().numpy() if isinstance(labels, torch.Tensor) else labels)).astype(np.int64)
+        bad = (lab_h < 0) | (lab_h >= C)
+        if mask is not None:
+            bad &= mask
+        if bad.any():                              # host labels: refused before the launch; device labels: the status word below
+            raise ValueError(f"softmax_cross_entropy_with_integer_labels: {int(bad.sum())} counted pixel(s) carry a label outside "
+                             f"[0, {C}) (first: {int(lab_h[bad][0])})")
+        lab = torch.from_numpy(np.ascontiguousarray(lab_h.astype(np.int32))).to(device())
+    md = None if mask is None else torch.from_numpy(mask.astype(np.uint8)).to(device())
+    lt = act.t if act is not None else (logits if isinstance(logits, torch.Tensor) else _upload(logits)).to(device()).float().contiguous()
+    losses, sums, dl = (torch.empty(s, dtype=torch.float32, device=device()) for s in ((B, H, W), (2,), (B, C, H, W)))
+    _launching(_call, "mv_softmax_xent_map_f32", _p(lt), _p(lab), _p(md), _p(losses), _p(dl), _p(sums), B, C, H * W, _S())
+    if on_device:
+        _lib.check_device_status()
+    return _PixelLosses(losses, sums, dl, _node(act) if act is not None and active() else None)
 
 
 def _backward(root: Node):
@@ -879,7 +1056,8 @@ def _backward(root: Node):
                 if parent is None or gp is None:
                     continue
                 if id(parent) in grads:
-                    grads[id(parent)] = (parent, _add(grads[id(parent)][1], gp))
+                    old = grads[id(parent)][1]      # tensors, or the float seeds of scalar arithmetic (the same loss used twice)
+                    grads[id(parent)] = (parent, _add(old, gp) if isinstance(gp, torch.Tensor) else old + gp)
                 else:
                     grads[id(parent)] = (parent, gp)
                 if id(parent) not in seen:
@@ -907,7 +1085,7 @@ def filter_value_and_grad(fn: Callable) -> Callable:
         try:
             with precision("fp32"):
                 loss = fn(model, *args, **kwargs)
-                if isinstance(loss, _Rows):
+                if isinstance(loss, (_Rows, _PixelLosses)):
                     loss = loss.mean()
                 if not isinstance(loss, Scalar) or loss.node is None:
                     raise TypeError("filter_value_and_grad: the function must return a scalar that depends on the model "

@@ -31,11 +31,13 @@ class _SimpleSegmentationModel(Module):
 
     @boundary
     def _forward(self, x, key):
-        k_backbone = jr.split(jr.PRNGKey(0), 3)[0] if key is None else key
+        # backbone, classifier, auxiliary head (reference _utils.py:47-55): dead values in inference, the Dropout masks of the two
+        # heads in training mode
+        k_backbone, k_clf, k_aux = jr.split(jr.PRNGKey(0) if key is None else key, 3)
         size = tuple(x.shape[-2:])               # logical (C, H, W) of the sample
         _, feats = self.backbone(x, key=k_backbone)
-        out = ops.resize_bilinear(self.classifier(feats[-1]), size, final=True)
+        out = ops.resize_bilinear(self.classifier(feats[-1], key=k_clf), size, final=True)
         if self.aux_classifier is None:
             return None, out
-        aux = ops.resize_bilinear(self.aux_classifier(feats[0]), size, final=True)
+        aux = ops.resize_bilinear(self.aux_classifier(feats[0], key=k_aux), size, final=True)
         return aux, out

@@ -76,7 +76,8 @@ int mv_get_flag(const char* name);
 int mv_flags_epoch(void);                        /* hash of this thread's current switch settings (0 = all default): recorded launch lists key on it */
 /* Device status word: kernels that detect a broken protocol at run time record it here instead of trapping (a trap poisons the whole
  * HIP context, graph replays and other streams included).  bit 0: a split-K block gave up waiting for its partner's partial sums
- * (dirty / shared scratch; the tile it wrote is incomplete).  Writes the word to *status, clears it if `clear`; SYNCHRONISES the
+ * (dirty / shared scratch; the tile it wrote is incomplete).  bit 1: mv_softmax_xent_map_f32 met a label outside [0, C) on a counted
+ * pixel (the pixel was left out; loss, gradient and sums of that call are not those of the labels given).  Writes the word to *status, clears it if `clear`; SYNCHRONISES the
  * device -- call it where the host synchronises anyway (after a forward, at the end of a test). */
 int mv_device_status(int clear, unsigned* status);
 /* name of the kernel variant the last call on this thread dispatched to (for tests/bench) */
@@ -743,6 +744,17 @@ int mv_swin_window_attn_bwd_f32(const float* qkv, const float* bias, const float
 int mv_scatter_rows_sum_f32(const float* src, const int* index, float* out, int M, int C, int T, mv_stream_t stream);
 /* Backward of mv_patch_merge_gather_nhwc (swin.py:23-31) for even H, W: dx[B,H,W,C] from dy[B,H/2,W/2,4C]. */
 int mv_patch_merge_gather_bwd_f32(const float* dy, float* dx, int B, int H, int W, int C, mv_stream_t stream);
+/* Adjoint of mv_resize_bilinear_nhwc_fwd for H >= h, W >= w (half-pixel centres, edge clamp: jax.image.resize "bilinear"; down-sampling
+ * returns MV_E_INVALID): dx[N,h,w,C] from dy, which is [N,C,H,W] when dy_nchw (the out_nchw = 1 form the segmentation models return),
+ * else [N,H,W,C].  Gather form: every dx element sums its own footprint of dy in a fixed order -- one launch, no atomics, bit-reproducible. */
+int mv_resize_bilinear_bwd_nhwc_f32(const float* dy, float* dx, int N, int h, int w, int C, int H, int W, int dy_nchw,
+                                    mv_stream_t stream);
+/* optax.softmax_cross_entropy_with_integer_labels over the class axis of NCHW logits [B, C, HW]: labels int32 [B, HW]; where uint8
+ * [B, HW] or NULL (every pixel counts).  loss[B, HW] per pixel (0 where masked), dlogits[B, C, HW] = d sum(loss) / d logits (0 where
+ * masked; the caller applies the 1 / n of a mean), sums[2] = {sum of loss, number of counted pixels}, added in a fixed order.
+ * A label outside [0, C) on a counted pixel is never used as an index; it raises bit 1 of the device status word (mv_device_status). */
+int mv_softmax_xent_map_f32(const float* logits, const int32_t* labels, const uint8_t* where, float* loss, float* dlogits, float* sums,
+                            int B, int C, int64_t HW, mv_stream_t stream);
 /* y[C][R] = x[R][C]^T, rows of x x_row_stride elements apart (0 = dense). */
 int mv_transpose2d_f32(const float* x, float* y, int R, int C, int64_t x_row_stride, mv_stream_t stream);
 
