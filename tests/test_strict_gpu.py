@@ -19,7 +19,8 @@ bits") are operands here: the reference reads the same folded values, so no term
 
 Shapes are the smallest that reach the kernel with a ragged M tail, a ragged N tail and >= 2 reduction steps; where a dispatch gate
 needs more rows the case says which.  Out of scope (outputs not exactly representable; a separate derivation is needed): the
-LayerNorm-, softmax- and GELU-bearing kernels (`ln_*`, `cnblock`, `swin_*`, `mha`), and every activation but none / ReLU.
+LayerNorm- and GELU-bearing kernels (`ln_*`, `cnblock`, `mv_swin_block_attn_fwd`), and every activation but none / ReLU.  The
+softmax attention kernels (`mha_*`, `swin_attn_*`) are covered in tests/test_strict_attn_gpu.py.
 """
 import functools
 
