@@ -175,6 +175,11 @@ def _to_device_f32(x) -> torch.Tensor:
     else:
         t = torch.from_numpy(np.ascontiguousarray(np.asarray(x)))
     if t.dtype not in (torch.float32, torch.bfloat16):
+        if t.dtype == torch.uint8 and getattr(_lib._tls, "rec", None) is not None:
+            # filter_jit hands uint8 images through as bytes (for eqxvision_amd.preprocess); a cast here would be a torch kernel
+            # the recording does not hold, and every replay would read the first call's pixels
+            raise ValueError("uint8 images inside filter_jit must go through eqxvision_amd.preprocess (or be converted to "
+                             "float before the call)")
         t = t.to(torch.float32)
     return t.to(device(), non_blocking=True).contiguous()
 

@@ -102,6 +102,7 @@ PROTOTYPES = {
     "mv_conv2d_nchw_split_fwd": [_vp, _vp, _vp, _vp, _vp, _vp] + [_i] * 11 + [_i, _i, _i, _vp],
     "mv_resize_bilinear_nhwc_fwd": [_vp, _vp] + [_i] * 6 + [_i, _i, _i, _vp],
     "mv_copy_rows": [_vp, _vp, _i64, _i64, _i64, _i64, _vp],
+    "mv_preprocess_u8_fwd": [_vp] * 6 + [_i] * 14 + [_vp],
     "mv_maxpool2d_nhwc_fwd": [_vp, _vp] + [_i] * 10 + [_i, _vp],
     "mv_adaptive_avgpool2d_nhwc_fwd": [_vp, _vp] + [_i] * 6 + [_i, _i, _vp],
     "mv_layernorm_fwd": [_vp, _vp, _vp, _vp, _i64, _i, _i64, _f, _i, _i, _vp],
@@ -306,6 +307,9 @@ def check_device_status(clear: bool = True) -> int:
     if v.value & 2:
         raise MVError(f"device status 0x{v.value:x}: mv_softmax_xent_map_f32 met a label outside [0, classes) on a counted pixel; the "
                       "pixel was left out of the loss and its gradient")
+    if v.value & 4:
+        raise MVError(f"device status 0x{v.value:x}: mv_preprocess_u8_fwd was given a tap table that points outside the image or its "
+                      "tile; the taps were clamped and the output of that call is wrong")
     if v.value:
         raise MVError(f"device status 0x{v.value:x}: a split-K tile was finished without its partner's partial sums -- the scratch of "
                       "mv_set_scratch was shared by concurrent launches or not zero-initialised; results of that launch are wrong")

@@ -1,0 +1,278 @@
+// Image preprocessing on the device, gfx950: uint8 images -> the float tensor the models read, in one launch.
+// resize (separable triangle filter, half-pixel centres, antialiased when down-sampling) -> crop -> y = acc * a[c] + b[c].
+// The filter lives in two tap tables the host builds in float64 (eqxvision_amd/preprocess.py: axis_table); the kernel only
+// applies them, so the same entry serves the antialiased ImageNet preset and plain two-tap up-sampling.  HBM-bound gather, no
+// matrix work: every input byte a tile needs is read once into LDS, both passes run out of LDS, every output is stored once.
+#include "common.h"
+
+namespace mv {
+
+namespace {
+
+// Table of one axis, n = cropped output extent, m = taps per output (the table's pitch): int32 first[n] | int32 count[n] |
+// fp32 weight[n][m].  `first` indexes the INPUT axis; taps first .. first + count - 1 lie inside it.
+struct PrepP {
+    const uint8_t* x;
+    void* y;
+    const int* tab_h;
+    const int* tab_w;
+    const float* a;
+    const float* b;
+    unsigned* status;
+    int Hin, Win, Hout, Wout, mh, mw;
+    int TH, TW;                    // output tile
+    int rows_cap, cols_cap, pitch; // staged input rectangle the LDS was sized for; bytes per staged line (multiple of 16)
+};
+
+__device__ __forceinline__ int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
+
+// One workgroup = one TH x TW tile of the cropped output of one image, all three channels.
+//   1. the tables of the tile's rows / columns -> LDS
+//   2. the input rectangle the tile's taps touch -> LDS as uint8, 16-byte global loads on 16-byte global addresses (a staged line
+//      starts `address & 15` bytes into its LDS line); chunks that would cross the ends of the image go byte by byte
+//   3. horizontal pass: every staged row x tile column x channel -> fp32 LDS
+//   4. vertical pass + affine epilogue -> global
+// Each pass sums about the smallest of its taps, sum_k w[k] (v[k] - vmin) + vmin, as fp32 fmas in tap order.  The weights of an
+// output sum to 1, so this is the same filter, and it buys two things over sum_k w[k] v[k]: every term and every partial sum is
+// >= 0 and <= the result, so the rounding error is bounded by (taps + 1) 2^-24 of the result itself whatever the image; and a
+// constant neighbourhood comes out as that constant exactly, however the fp32 weights happen to round (a flat image gives
+// fma(v, a, b) bit for bit, borders included).  Nothing is shared between workgroups: two runs give the same bits.
+template <bool CHW_IN, bool NHWC_OUT, bool BF16_OUT>
+__global__ __launch_bounds__(256) void preprocess_u8_kernel(const PrepP p) {
+    extern __shared__ uint4 smem4[];
+    const int tid = threadIdx.x;
+    const int y0 = blockIdx.y * p.TH, x0 = blockIdx.x * p.TW, b = blockIdx.z;
+    const int th = min(p.TH, p.Hout - y0), tw = min(p.TW, p.Wout - x0);
+    constexpr int PIX = CHW_IN ? 1 : 3;                      // bytes from one pixel of a channel to the next
+    const int lines_cap = CHW_IN ? 3 * p.rows_cap : p.rows_cap;
+
+    uint8_t* su8 = (uint8_t*)smem4;
+    float* sh = (float*)(su8 + (size_t)lines_cap * p.pitch);
+    int* sfy = (int*)(sh + (size_t)p.rows_cap * 3 * p.TW);
+    int* sny = sfy + p.TH;
+    int* sfx = sny + p.TH;
+    int* snx = sfx + p.TW;
+    float* swy = (float*)(snx + p.TW);
+    float* swx = swy + p.TH * p.mh;
+
+    // the input rectangle: uniform over the workgroup (scalar loads).  The tables are device data the host cannot see at launch
+    // time, so nothing read from them is trusted with an address: the rectangle is cut to the image and to the LDS it was sized
+    // for, tap indices are clamped into it below, and a table that needed either sets bit 2 of the device status word.
+    int r0 = p.Hin, r1 = 0, c0 = p.Win, c1 = 0, bad = 0;
+    for (int i = 0; i < th; ++i) {
+        const int f = p.tab_h[y0 + i], n = p.tab_h[p.Hout + y0 + i];
+        bad |= (f < 0) | (n < 1) | (n > p.mh) | (f + n > p.Hin);
+        r0 = min(r0, f);
+        r1 = max(r1, f + n);
+    }
+    for (int i = 0; i < tw; ++i) {
+        const int f = p.tab_w[x0 + i], n = p.tab_w[p.Wout + x0 + i];
+        bad |= (f < 0) | (n < 1) | (n > p.mw) | (f + n > p.Win);
+        c0 = min(c0, f);
+        c1 = max(c1, f + n);
+    }
+    r0 = clampi(r0, 0, p.Hin - 1);
+    c0 = clampi(c0, 0, p.Win - 1);
+    r1 = clampi(r1, r0 + 1, p.Hin);
+    c1 = clampi(c1, c0 + 1, p.Win);
+    if (r1 - r0 > p.rows_cap) { r1 = r0 + p.rows_cap; bad = 1; }
+    if (c1 - c0 > p.cols_cap) { c1 = c0 + p.cols_cap; bad = 1; }
+    const int nrows = r1 - r0, ncols = c1 - c0;
+    if (bad && tid == 0) atomicOr(p.status, 4u);
+
+    // 1. tables
+    for (int i = tid; i < th; i += 256) {
+        sfy[i] = p.tab_h[y0 + i] - r0;
+        sny[i] = clampi(p.tab_h[p.Hout + y0 + i], 1, p.mh);
+    }
+    for (int i = tid; i < tw; i += 256) {
+        sfx[i] = p.tab_w[x0 + i] - c0;
+        snx[i] = clampi(p.tab_w[p.Wout + x0 + i], 1, p.mw);
+    }
+    {
+        const float* wy = (const float*)(p.tab_h + 2 * (size_t)p.Hout) + (size_t)y0 * p.mh;
+        for (int i = tid; i < th * p.mh; i += 256) swy[i] = wy[i];
+        const float* wx = (const float*)(p.tab_w + 2 * (size_t)p.Wout) + (size_t)x0 * p.mw;
+        for (int i = tid; i < tw * p.mw; i += 256) swx[i] = wx[i];
+    }
+
+    // 2. input rectangle
+    const size_t img_bytes = (size_t)p.Hin * p.Win * 3;
+    const uint8_t* img = p.x + (size_t)b * img_bytes;
+    const uintptr_t img_lo = (uintptr_t)img, img_hi = img_lo + img_bytes;
+    const int lines = CHW_IN ? 3 * nrows : nrows;
+    const int len = ncols * PIX;
+    const int nch = p.pitch >> 4;
+    auto line_addr = [&](int l) -> uintptr_t {
+        if (CHW_IN) {
+            const int c = l / nrows, r = r0 + (l - c * nrows);
+            return img_lo + ((size_t)c * p.Hin + r) * p.Win + c0;
+        }
+        return img_lo + ((size_t)(r0 + l) * p.Win + c0) * 3;
+    };
+    for (int it = tid; it < lines * nch; it += 256) {
+        const int l = it / nch, j = it - l * nch;
+        const uintptr_t g = line_addr(l);
+        const uintptr_t ca = (g & ~(uintptr_t)15) + 16 * (uintptr_t)j;
+        if (ca >= g + len) continue;
+        uint8_t* d = su8 + (size_t)l * p.pitch + 16 * j;
+        if (ca >= img_lo && ca + 16 <= img_hi) {
+            *(uint4*)d = *(const uint4*)ca;
+        } else {                                             // ragged head of the first line / tail of the last line of the image
+            for (int k = 0; k < 16; ++k)
+                if (ca + k >= img_lo && ca + k < img_hi) d[k] = *(const uint8_t*)(ca + k);
+        }
+    }
+    __syncthreads();
+
+    // 3. horizontal pass: sh[(r * 3 + c) * TW + x]
+    for (int it = tid; it < nrows * 3 * tw; it += 256) {
+        const int rc = it / tw, x = it - rc * tw;
+        const int r = rc / 3, c = rc - r * 3;
+        const int l = CHW_IN ? c * nrows + r : r;
+        const uint8_t* src = su8 + (size_t)l * p.pitch + (int)(line_addr(l) & 15) + (CHW_IN ? 0 : c);
+        const int f = sfx[x], n = snx[x];
+        const float* w = swx + x * p.mw;
+        int m = 255;
+        for (int k = 0; k < n; ++k) m = min(m, (int)src[clampi(f + k, 0, ncols - 1) * PIX]);
+        float acc = 0.f;
+        for (int k = 0; k < n; ++k) acc = fmaf(w[k], (float)((int)src[clampi(f + k, 0, ncols - 1) * PIX] - m), acc);
+        sh[rc * p.TW + x] = acc + (float)m;
+    }
+    __syncthreads();
+
+    // 4. vertical pass, epilogue, store
+    const float a0 = p.a[0], a1 = p.a[1], a2 = p.a[2], b0 = p.b[0], b1 = p.b[1], b2 = p.b[2];
+    for (int it = tid; it < th * 3 * tw; it += 256) {
+        int y, c, x;
+        if (NHWC_OUT) {
+            const int yx = it / 3;
+            c = it - yx * 3;
+            y = yx / tw;
+            x = yx - y * tw;
+        } else {
+            const int yc = it / tw;
+            x = it - yc * tw;
+            y = yc / 3;
+            c = yc - y * 3;
+        }
+        const int f = sfy[y], n = sny[y];
+        const float* w = swy + y * p.mh;
+        float m = sh[(clampi(f, 0, nrows - 1) * 3 + c) * p.TW + x];
+        for (int k = 1; k < n; ++k) m = fminf(m, sh[(clampi(f + k, 0, nrows - 1) * 3 + c) * p.TW + x]);
+        float acc = 0.f;
+        for (int k = 0; k < n; ++k) acc = fmaf(w[k], sh[(clampi(f + k, 0, nrows - 1) * 3 + c) * p.TW + x] - m, acc);
+        acc += m;
+        const float v = fmaf(acc, c == 0 ? a0 : (c == 1 ? a1 : a2), c == 0 ? b0 : (c == 1 ? b1 : b2));
+        const size_t o = NHWC_OUT ? (((size_t)b * p.Hout + y0 + y) * p.Wout + x0 + x) * 3 + c
+                                  : (((size_t)b * 3 + c) * p.Hout + y0 + y) * p.Wout + x0 + x;
+        if (BF16_OUT) ((bf16_t*)p.y)[o] = f2bf(v);
+        else ((float*)p.y)[o] = v;
+    }
+}
+
+// input samples a run of T outputs can touch on one axis: (T - 1) * ratio between the first and the last centre, the support on
+// both sides, one for the inclusive end, one for rounding
+int span_cap(int T, int in, int out_full) {
+    const double ratio = (double)in / (double)out_full, sup = ratio > 1.0 ? ratio : 1.0;
+    const double s = (T - 1) * ratio + 2.0 * sup + 2.0;
+    return s >= in ? in : (int)s;
+}
+
+int taps_needed(int in, int out_full) {
+    const double ratio = (double)in / (double)out_full, sup = ratio > 1.0 ? ratio : 1.0;
+    const double n = 2.0 * sup + 1.0;
+    return n >= in ? in : (int)n;
+}
+
+size_t lds_bytes(int TH, int TW, int rows_cap, int cols_cap, int in_chw, int mh, int mw, int* pitch) {
+    const int pix = in_chw ? 1 : 3;
+    *pitch = (cols_cap * pix + 15 + 15) & ~15;
+    const size_t lines = in_chw ? 3 * (size_t)rows_cap : rows_cap;
+    return lines * *pitch + (size_t)rows_cap * 3 * TW * 4 + (size_t)(2 * TH + 2 * TW + TH * mh + TW * mw) * 4;
+}
+
+}  // namespace
+
+}  // namespace mv
+
+using namespace mv;
+
+extern "C" {
+
+int mv_preprocess_u8_fwd(const void* x, void* y, const void* tab_h, const void* tab_w, const float* a, const float* b, int B, int Hin,
+                         int Win, int Hr, int Wr, int top, int left, int Hout, int Wout, int taps_h, int taps_w, int in_chw,
+                         int out_dtype, int out_nhwc, mv_stream_t stream) {
+    MV_CHECK_ARG(B > 0 && Hin > 0 && Win > 0 && Hr > 0 && Wr > 0 && Hout > 0 && Wout > 0 && taps_h > 0 && taps_w > 0,
+                 "preprocess_u8: bad sizes");
+    MV_CHECK_ARG(out_dtype == MV_F32 || out_dtype == MV_BF16, "preprocess_u8: out_dtype must be MV_F32 or MV_BF16");
+    MV_CHECK_ARG(B <= 65535 && (long long)Hin * Win * 3 < (1LL << 31), "preprocess_u8: batch %d or image %dx%d too large", B, Hin, Win);
+    if (!x || !y || !tab_h || !tab_w || !a || !b) {
+        set_error("preprocess_u8: null buffer");
+        return MV_E_UNSUPPORTED;
+    }
+    if (top < 0 || left < 0 || (long long)top + Hout > Hr || (long long)left + Wout > Wr) {
+        set_error("preprocess_u8: crop %dx%d at (%d, %d) does not lie inside the resized image %dx%d", Hout, Wout, top, left, Hr, Wr);
+        return MV_E_UNSUPPORTED;
+    }
+    const int need_h = taps_needed(Hin, Hr), need_w = taps_needed(Win, Wr);
+    if (taps_h > MV_PREPROCESS_MAX_TAPS || taps_w > MV_PREPROCESS_MAX_TAPS || need_h > MV_PREPROCESS_MAX_TAPS ||
+        need_w > MV_PREPROCESS_MAX_TAPS) {
+        set_error("preprocess_u8: %dx%d -> %dx%d needs up to %d x %d taps (tables of %d x %d); at most %d per axis (down-sampling by "
+                  "up to %.1f)", Hin, Win, Hr, Wr, need_h, need_w, taps_h, taps_w, MV_PREPROCESS_MAX_TAPS,
+                  (MV_PREPROCESS_MAX_TAPS - 1) / 2.0);
+        return MV_E_UNSUPPORTED;
+    }
+    const size_t in_bytes = (size_t)B * Hin * Win * 3, out_bytes = (size_t)B * 3 * Hout * Wout * dsize(out_dtype);
+    const uintptr_t xa = (uintptr_t)x, ya = (uintptr_t)y;
+    if (xa < ya + out_bytes && ya < xa + in_bytes) {
+        set_error("preprocess_u8: input and output overlap");
+        return MV_E_UNSUPPORTED;
+    }
+    unsigned* status = device_status_word();
+    MV_CHECK_ARG(status != nullptr, "preprocess_u8: the device status word is not available");
+
+    // Tile: the largest of these whose staged rectangle fits 64 KiB of LDS.  The ImageNet preset on a 500 x 375 image (ratio
+    // 1.46) takes 32 x 32: 51 input rows x 51 columns staged = 51 x 176 B of uint8 + 51 x 3 x 32 fp32 of horizontal sums + 1.3 KiB
+    // of tables = 29.9 KiB -> 5 workgroups of 4 waves per CU = 5 waves per SIMD, 49 tiles per image.  Smaller tiles keep steep
+    // down-sampling (up to 11.5x, 24 taps) inside the budget; their stores are shorter runs, which such a reduction can afford.
+    static const int tiles[][2] = {{32, 32}, {16, 32}, {16, 16}, {8, 16}, {4, 8}};
+    PrepP p;
+    size_t lds = 0;
+    bool fits = false;
+    for (const auto& t : tiles) {
+        p.TH = t[0];
+        p.TW = t[1];
+        p.rows_cap = span_cap(p.TH, Hin, Hr);
+        p.cols_cap = span_cap(p.TW, Win, Wr);
+        lds = lds_bytes(p.TH, p.TW, p.rows_cap, p.cols_cap, in_chw, taps_h, taps_w, &p.pitch);
+        if (lds <= 64 * 1024) {
+            fits = true;
+            break;
+        }
+    }
+    if (!fits) {
+        set_error("preprocess_u8: %dx%d -> %dx%d does not fit the LDS tile (%zu bytes for the smallest tile)", Hin, Win, Hr, Wr, lds);
+        return MV_E_UNSUPPORTED;
+    }
+    p.x = (const uint8_t*)x; p.y = y; p.tab_h = (const int*)tab_h; p.tab_w = (const int*)tab_w; p.a = a; p.b = b; p.status = status;
+    p.Hin = Hin; p.Win = Win; p.Hout = Hout; p.Wout = Wout; p.mh = taps_h; p.mw = taps_w;
+    const dim3 grid((Wout + p.TW - 1) / p.TW, (Hout + p.TH - 1) / p.TH, B);
+    MV_CHECK_ARG(grid.y <= 65535, "preprocess_u8: %d output rows are too many tiles", Hout);
+    hipStream_t st = (hipStream_t)stream;
+    set_kernel_name("preprocess_u8");
+#define GO(CHW, NHWC, BF) hipLaunchKernelGGL((preprocess_u8_kernel<CHW, NHWC, BF>), grid, dim3(256), lds, st, p)
+    const bool bf = out_dtype == MV_BF16;
+    if (in_chw) {
+        if (out_nhwc) { if (bf) GO(true, true, true); else GO(true, true, false); }
+        else { if (bf) GO(true, false, true); else GO(true, false, false); }
+    } else {
+        if (out_nhwc) { if (bf) GO(false, true, true); else GO(false, true, false); }
+        else { if (bf) GO(false, false, true); else GO(false, false, false); }
+    }
+#undef GO
+    MV_LAUNCH_CHECK();
+    return MV_OK;
+}
+
+}  // extern "C"

@@ -83,7 +83,7 @@ def _guard(name: str):
     """Called by _lib.call: a kernel launched from an op that has no g_* twin would drop out of the gradient silently."""
     t = tape()
     if t is not None and t.inside == 0 and not name.startswith(("mv_set_flag", "mv_get_flag", "mv_event", "mv_graph", "mv_comm",
-                                                                "mv_prng_split", "mv_drop_path_noise")):
+                                                                "mv_prng_split", "mv_drop_path_noise", "mv_preprocess_u8")):
         raise NotImplementedError(f"{name} was launched inside filter_value_and_grad by an op without a backward "
                                   "(eqxvision_amd/grad.py lists what is differentiable)")
 

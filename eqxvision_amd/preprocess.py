@@ -1,0 +1,187 @@
+"""Image preprocessing on the device: uint8 images -> the tensor the models read, one launch (csrc/preprocess.hip).
+
+    x = eqv.preprocess.imagenet_eval(images_u8)            # Resize(256, antialias) -> CenterCrop(224) -> ToTensor -> Normalize
+    logits = eqv.vmap(net)(x)
+
+The transform is torchvision's evaluation preset, the one the `torch_weights=` checkpoints were evaluated under: the resized size
+and the crop offsets follow torchvision's rounding, the filter is `torch.nn.functional.interpolate(mode="bilinear", antialias=True)`
+(the triangle filter of `jax.image.resize` -- oracle/np_ops.py restates it -- widened by in / out when down-sampling, weights
+normalised over the taps inside the image).  The host builds the filter as one tap table per axis in float64, rounds the weights
+to fp32, uploads them once per geometry and keeps them; the kernel only applies them.
+
+Outputs: NCHW in fp32 or bf16 are what the models' entry kernels read without a conversion launch (`_act.wrap` takes a [B, 3, H, W]
+tensor as the image batch; the entry convolutions read fp32 or bf16).  The models have no NHWC entry, so `imagenet_eval` does not
+offer one; `resize_crop_normalize(layout="nhwc")` returns a plain tensor for other consumers.
+"""
+from __future__ import annotations
+
+import numpy as np
+import torch
+
+from . import _lib
+from ._act import DT, TORCH_DT, device, empty, stream_ptr
+from ._act import _tls as _act_tls
+
+IMAGENET_MEAN = (0.485, 0.456, 0.406)
+IMAGENET_STD = (0.229, 0.224, 0.225)
+MAX_TAPS = 24          # MV_PREPROCESS_MAX_TAPS of include/eqxvision_amd.h: down-sampling by up to 11.5 per axis
+
+
+def resized_size(h: int, w: int, size: int):
+    """torchvision `Resize(size)` with an int: the shorter side becomes `size`, the longer one int(size * long / short)."""
+    h, w, size = int(h), int(w), int(size)
+    if h <= w:
+        return size, int(size * w / h)
+    return int(size * h / w), size
+
+
+def center_crop_box(hr: int, wr: int, crop):
+    """torchvision `CenterCrop`: (top, left, height, width) with top = int(round((hr - height) / 2.0))."""
+    ch, cw = (int(crop), int(crop)) if isinstance(crop, (int, np.integer)) else (int(crop[0]), int(crop[1]))
+    return int(round((hr - ch) / 2.0)), int(round((wr - cw) / 2.0)), ch, cw
+
+
+def axis_table(n_in: int, n_out: int, start: int = 0, count: int = None):
+    """The filter of one axis for the outputs start .. start + count - 1 of an n_in -> n_out resize.
+    Returns (first int32 [count], taps int32 [count], weight fp32 [count, m]) with m = max(taps): output i is
+    sum_k weight[i, k] * input[first[i] + k] over k < taps[i]; weight[i, taps[i]:] is 0.
+    Sample centre s = (o + 0.5) in / out - 0.5, support max(1, in / out), weight 1 - |x - s| / support over the x inside the
+    support and the axis, divided by their sum (float64), rounded to fp32."""
+    n_in, n_out = int(n_in), int(n_out)
+    count = n_out - start if count is None else int(count)
+    if n_in < 1 or n_out < 1 or start < 0 or count < 1 or start + count > n_out:
+        raise ValueError(f"axis_table: outputs {start}..{start + count} of a {n_in} -> {n_out} resize")
+    ratio = n_in / n_out
+    sup = max(1.0, ratio)
+    o = np.arange(start, start + count, dtype=np.float64)
+    s = (o + 0.5) * ratio - 0.5
+    first = np.maximum(np.floor(s - sup).astype(np.int64) + 1, 0)
+    last = np.minimum(np.ceil(s + sup).astype(np.int64) - 1, n_in - 1)
+    taps = last - first + 1
+    m = int(taps.max())
+    x = first[:, None] + np.arange(m)[None, :]
+    w = np.maximum(0.0, 1.0 - np.abs(x - s[:, None]) / sup)
+    w[np.arange(m)[None, :] >= taps[:, None]] = 0.0
+    w /= w.sum(1, keepdims=True)
+    return first.astype(np.int32), taps.astype(np.int32), w.astype(np.float32)
+
+
+def pack_table(first, taps, weight) -> np.ndarray:
+    """The device layout of `mv_preprocess_u8_fwd`: int32 first[n] | int32 taps[n] | fp32 weight[n][m] as one int32 array."""
+    return np.concatenate([first.astype(np.int32), taps.astype(np.int32), np.ascontiguousarray(weight, np.float32).reshape(-1).view(np.int32)])
+
+
+def affine(mean, std):
+    """(a, b) fp32 [3] of the epilogue y = acc * a + b: a = 1 / (255 std), b = -mean / std, computed in float64."""
+    mean, std = np.asarray(mean, np.float64).reshape(-1), np.asarray(std, np.float64).reshape(-1)
+    if mean.shape != (3,) or std.shape != (3,) or not np.all(std != 0):
+        raise ValueError("preprocess: mean and std must be three numbers each, std non-zero")
+    return (1.0 / (255.0 * std)).astype(np.float32), (-mean / std).astype(np.float32)
+
+
+_tables = {}        # (device, Hin, Win, Hr, Wr, top, left, Hout, Wout) -> (tab_h, tab_w, taps_h, taps_w) on the device
+_affines = {}       # (device, mean, std) -> (a, b) on the device
+
+
+def _geometry(hin, win, resized_hw, crop_box):
+    hr, wr = int(resized_hw[0]), int(resized_hw[1])
+    top, left, hout, wout = (int(v) for v in crop_box)
+    if hr < 1 or wr < 1 or hout < 1 or wout < 1:
+        raise ValueError(f"preprocess: resized size {(hr, wr)} and crop {(hout, wout)} must be positive")
+    if top < 0 or left < 0 or top + hout > hr or left + wout > wr:
+        raise ValueError(f"preprocess: crop {hout}x{wout} at ({top}, {left}) does not lie inside the resized image {hr}x{wr}")
+    return hr, wr, top, left, hout, wout
+
+
+def _device_tables(hin, win, hr, wr, top, left, hout, wout):
+    geo = (hin, win, hr, wr, top, left, hout, wout)
+    for n_in, n_out in ((hin, hr), (win, wr)):               # refused on the host, before the device is touched
+        need = min(n_in, int(2.0 * max(1.0, n_in / n_out) + 1.0))
+        if need > MAX_TAPS:
+            raise ValueError(f"preprocess: {hin}x{win} -> {hr}x{wr} needs {need} filter taps on an axis, at most {MAX_TAPS} "
+                             f"(down-sampling by up to {(MAX_TAPS - 1) / 2})")
+    key = (str(device()),) + geo
+    hit = _tables.get(key)
+    if hit is None:
+        th, tw = axis_table(hin, hr, top, hout), axis_table(win, wr, left, wout)
+        hit = (torch.from_numpy(pack_table(*th)).to(device()), torch.from_numpy(pack_table(*tw)).to(device()),
+               th[2].shape[1], tw[2].shape[1])
+        _tables[key] = hit
+    return hit
+
+
+def _device_affine(mean, std):
+    key = (str(device()), tuple(float(v) for v in np.asarray(mean).reshape(-1)), tuple(float(v) for v in np.asarray(std).reshape(-1)))
+    hit = _affines.get(key)
+    if hit is None:
+        a, b = affine(mean, std)
+        hit = _affines[key] = (torch.from_numpy(a).to(device()), torch.from_numpy(b).to(device()))
+    return hit
+
+
+def _check_input(images_u8, channels_last):
+    """-> (array, batched, chw, Hin, Win); raises ValueError before anything touches the device."""
+    x = images_u8
+    if not isinstance(x, (np.ndarray, torch.Tensor)):
+        raise ValueError(f"preprocess: images must be a uint8 numpy array or torch tensor, got {type(x).__name__}")
+    if x.dtype != (torch.uint8 if isinstance(x, torch.Tensor) else np.uint8):
+        raise ValueError(f"preprocess: images must be uint8 (decoded pixels 0..255), got {x.dtype}")
+    if x.ndim not in (3, 4):
+        raise ValueError(f"preprocess: images must be [H, W, 3] / [3, H, W] or a batch of them, got shape {tuple(x.shape)}")
+    batched = x.ndim == 4
+    s = tuple(int(v) for v in x.shape[-3:])
+    if channels_last is None:
+        if s[2] == 3:
+            chw = False
+        elif s[0] == 3:
+            chw = True
+        else:
+            raise ValueError(f"preprocess: images must have 3 channels first or last, got shape {tuple(x.shape)}")
+    else:
+        chw = not channels_last
+        if s[0 if chw else 2] != 3:
+            raise ValueError(f"preprocess: images must have 3 channels, got shape {tuple(x.shape)} with channels_last={channels_last}")
+    hin, win = (s[1], s[2]) if chw else (s[0], s[1])
+    if hin < 1 or win < 1:
+        raise ValueError(f"preprocess: empty image, shape {tuple(x.shape)}")
+    return x, batched, chw, hin, win
+
+
+def resize_crop_normalize(images_u8, resized_hw, crop_box, mean=IMAGENET_MEAN, std=IMAGENET_STD, dtype="fp32", layout="nchw",
+                          channels_last=None) -> torch.Tensor:
+    """Resize uint8 images to `resized_hw` (antialiased triangle filter), keep `crop_box` = (top, left, height, width) of the resized
+    image, return (x / 255 - mean) / std as a device tensor [B, 3, height, width] (`layout="nchw"`) or [B, height, width, 3], fp32
+    or bf16.  `images_u8`: [B, H, W, 3] or [B, 3, H, W] (or one image without the batch axis), numpy or torch, host or device; the
+    layout is read off which axis is 3 unless `channels_last` says so.  One launch on the current stream; recorded by `filter_jit`
+    like any other (a device-resident input is then read in place, a host array is staged as uint8 once per call)."""
+    x, batched, chw, hin, win = _check_input(images_u8, channels_last)
+    if dtype not in DT:
+        raise ValueError(f"preprocess: dtype must be 'fp32' or 'bf16', got {dtype!r}")
+    if layout not in ("nchw", "nhwc"):
+        raise ValueError(f"preprocess: layout must be 'nchw' or 'nhwc', got {layout!r}")
+    hr, wr, top, left, hout, wout = _geometry(hin, win, resized_hw, crop_box)
+    affine(mean, std)                                        # validates before the device is touched
+    tab_h, tab_w, mh, mw = _device_tables(hin, win, hr, wr, top, left, hout, wout)
+    a, b = _device_affine(mean, std)
+    t = x if isinstance(x, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(x))
+    t = t.to(device(), non_blocking=True).contiguous()
+    B = t.shape[0] if batched else 1
+    y = empty((B, 3, hout, wout) if layout == "nchw" else (B, hout, wout, 3), TORCH_DT[dtype])
+    _lib.call("mv_preprocess_u8_fwd", t.data_ptr(), y.data_ptr(), tab_h.data_ptr(), tab_w.data_ptr(), a.data_ptr(), b.data_ptr(),
+              B, hin, win, hr, wr, top, left, hout, wout, mh, mw, int(chw), DT[dtype], int(layout == "nhwc"), stream_ptr())
+    keep = getattr(_act_tls, "keep", None)
+    if keep is not None and t is not x:                      # uploaded inside a recording: the replayed launch reads this buffer
+        keep.append(t)
+    return y if batched else y[0]
+
+
+def imagenet_eval(images_u8, resize=256, crop=224, mean=IMAGENET_MEAN, std=IMAGENET_STD, dtype="fp32", layout="nchw",
+                  channels_last=None) -> torch.Tensor:
+    """torchvision's ImageNet evaluation preset on the device: shorter side to `resize` (antialiased bilinear), centre crop `crop`,
+    scale by 1 / 255, subtract `mean`, divide by `std`.  Returns [B, 3, crop, crop], fp32 or bf16: what `eqv.vmap(net)` reads."""
+    if layout != "nchw":
+        raise ValueError(f"preprocess.imagenet_eval: the models read NCHW images; layout={layout!r} is not one of their entries "
+                         "(resize_crop_normalize offers NHWC for other consumers)")
+    _, _, _, hin, win = _check_input(images_u8, channels_last)
+    hr, wr = resized_size(hin, win, resize)
+    return resize_crop_normalize(images_u8, (hr, wr), center_crop_box(hr, wr, crop), mean, std, dtype, layout, channels_last)

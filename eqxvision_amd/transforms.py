@@ -89,9 +89,14 @@ def _is_key_array(x) -> bool:
 
 
 def _is_resident(x) -> bool:
-    """A device tensor the kernels can read in place (no staging copy)."""
+    """A device tensor the kernels can read in place (no staging copy): fp32 / bf16 activations, and uint8 images (read by
+    `preprocess`, the one entry that takes them)."""
     return (isinstance(x, torch.Tensor) and x.is_cuda and x.is_contiguous()
-            and x.dtype in (torch.float32, torch.bfloat16))
+            and x.dtype in (torch.float32, torch.bfloat16, torch.uint8))
+
+
+def _is_u8(x) -> bool:
+    return x.dtype == (torch.uint8 if isinstance(x, torch.Tensor) else np.uint8)
 
 
 def _module_sig(m: Module):
@@ -428,7 +433,12 @@ def filter_jit(fn: Callable = None, *, use_graph: bool = True, clone_outputs: bo
             return _is_array(v) and not _is_key_array(v) and (own or not _is_resident(v))
 
         def stage(v):
-            return v.clone() if _is_resident(v) else _to_device_f32(v).clone()
+            if _is_resident(v):
+                return v.clone()
+            if _is_u8(v):                      # decoded images stay bytes: `preprocess` reads them, a quarter of the fp32 copy
+                t = v if isinstance(v, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(v))
+                return t.to(torch.device("cuda", torch.cuda.current_device())).contiguous().clone()
+            return _to_device_f32(v).clone()
 
         flat_arrays = [a for a in args if staged(a)] + [v for _, v in sorted(kwargs.items()) if staged(v)]
         if c is None:

@@ -77,7 +77,8 @@ int mv_flags_epoch(void);                        /* hash of this thread's curren
 /* Device status word: kernels that detect a broken protocol at run time record it here instead of trapping (a trap poisons the whole
  * HIP context, graph replays and other streams included).  bit 0: a split-K block gave up waiting for its partner's partial sums
  * (dirty / shared scratch; the tile it wrote is incomplete).  bit 1: mv_softmax_xent_map_f32 met a label outside [0, C) on a counted
- * pixel (the pixel was left out; loss, gradient and sums of that call are not those of the labels given).  Writes the word to *status, clears it if `clear`; SYNCHRONISES the
+ * pixel (the pixel was left out; loss, gradient and sums of that call are not those of the labels given).  bit 2: mv_preprocess_u8_fwd was given a tap table that points outside the image or
+ * outside what its geometry can need (the taps were clamped; the output of that call is not the resize asked for).  Writes the word to *status, clears it if `clear`; SYNCHRONISES the
  * device -- call it where the host synchronises anyway (after a forward, at the end of a test). */
 int mv_device_status(int clear, unsigned* status);
 /* name of the kernel variant the last call on this thread dispatched to (for tests/bench) */
@@ -513,6 +514,24 @@ int mv_resize_bilinear_nhwc_fwd(const void* x, void* y, int N, int h, int w, int
  * dst offset by the channels already placed).  Sizes and pitches in bytes, multiples of 2. */
 int mv_copy_rows(const void* src, void* dst, int64_t rows, int64_t row_bytes, int64_t src_pitch, int64_t dst_pitch,
                  mv_stream_t stream);
+
+/* Image preprocessing in one launch (torchvision's evaluation preset: Resize(antialias=True) -> CenterCrop -> ToTensor ->
+ * Normalize): B uint8 images of one size, x [B,Hin,Win,3] or, with in_chw, [B,3,Hin,Win], are resized to Hr x Wr with the
+ * separable triangle filter (half-pixel centres; support max(1, in / out) per axis, so it antialiases only when down-sampling and
+ * is plain two-tap bilinear otherwise; weights normalised over the taps inside the image), the Hout x Wout box at (top, left) of
+ * the resized image is kept, and y = acc * a[c] + b[c] (one fma; a = 1 / (255 std), b = -mean / std, fp32 [3]) is stored as
+ * out_dtype (MV_F32 / MV_BF16), NCHW [B,3,Hout,Wout] or, with out_nhwc, [B,Hout,Wout,3].  Only the box is computed.
+ * The filter is given as one DEVICE table per axis covering the outputs of the box only (tab_h: Hout entries, tab_w: Wout):
+ *   int32 first[n] | int32 count[n] | fp32 weight[n][taps]    (taps_h / taps_w: the pitch, >= every count)
+ * output i of the box is sum_k weight[i][k] * input[first[i] + k], k < count[i], all taps inside the input axis.  Sums are fp32
+ * in tap order (columns first, then rows), no atomics: repeated runs give the same bits.  The kernel never forms an address
+ * from a table entry that leaves the image or its LDS tile; a table that would have sets bit 2 (value 4) of mv_device_status.
+ * MV_E_UNSUPPORTED: more than MV_PREPROCESS_MAX_TAPS taps on an axis (tables, or what Hin / Hr, Win / Wr need: down-sampling
+ * beyond 11.5x), a box outside the resized image, a NULL buffer, x and y overlapping. */
+#define MV_PREPROCESS_MAX_TAPS 24
+int mv_preprocess_u8_fwd(const void* x, void* y, const void* tab_h, const void* tab_w, const float* a, const float* b, int B, int Hin,
+                         int Win, int Hr, int Wr, int top, int left, int Hout, int Wout, int taps_h, int taps_w, int in_chw,
+                         int out_dtype, int out_nhwc, mv_stream_t stream);
 
 /* eqx.nn.MaxPool2d (resnet.py:254, alexnet.py:46,49,56): -inf padding, floor output size. */
 int mv_maxpool2d_nhwc_fwd(const void* x, void* y, int N, int H, int W, int C,
