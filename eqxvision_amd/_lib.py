@@ -101,6 +101,8 @@ PROTOTYPES = {
     "mv_maxpool2d_out_nhwc_fwd": [_vp, _vp] + [_i] * 12 + [_i, _vp],
     "mv_conv2d_nchw_split_fwd": [_vp, _vp, _vp, _vp, _vp, _vp] + [_i] * 11 + [_i, _i, _i, _vp],
     "mv_resize_bilinear_nhwc_fwd": [_vp, _vp] + [_i] * 6 + [_i, _i, _i, _vp],
+    "mv_resize_argmax_nhwc_fwd": [_vp, _vp] + [_i] * 7 + [_vp],
+    "mv_softmax_topk_f32": [_vp, _vp, _vp, _i, _i, _i, _i, _vp],
     "mv_copy_rows": [_vp, _vp, _i64, _i64, _i64, _i64, _vp],
     "mv_preprocess_u8_fwd": [_vp] * 6 + [_i] * 14 + [_vp],
     "mv_maxpool2d_nhwc_fwd": [_vp, _vp] + [_i] * 10 + [_i, _vp],

@@ -22,6 +22,13 @@ __device__ __forceinline__ Taps taps_for(int o, int in, int out) {
     return {i0, i1, w1};
 }
 
+// the interpolation of the four taps: ONE expression for every kernel of this file, so that the label kernel below selects among
+// exactly the values the full-resolution kernels write
+__device__ __forceinline__ float bilerp(float v00, float v01, float v10, float v11, float wx, float wy) {
+    const float top = v00 + (v01 - v00) * wx, bot = v10 + (v11 - v10) * wx;
+    return top + (bot - top) * wy;
+}
+
 // one thread per output element; NCHW output: x fastest (coalesced stores, the 2x2 source pixels of neighbouring lanes are the
 // same cache lines); NHWC output: channel fastest.
 template <typename TI, typename TO, bool NCHW>
@@ -46,8 +53,7 @@ __global__ __launch_bounds__(256) void resize_bilinear_kernel(const TI* __restri
         const float v01 = io<TI>::ld(base + ((long long)ty.i0 * w + tx.i1) * C);
         const float v10 = io<TI>::ld(base + ((long long)ty.i1 * w + tx.i0) * C);
         const float v11 = io<TI>::ld(base + ((long long)ty.i1 * w + tx.i1) * C);
-        const float top = v00 + (v01 - v00) * tx.w1, bot = v10 + (v11 - v10) * tx.w1;
-        io<TO>::st(y + idx, top + (bot - top) * ty.w1);
+        io<TO>::st(y + idx, bilerp(v00, v01, v10, v11, tx.w1, ty.w1));
     }
 }
 
@@ -71,10 +77,105 @@ __global__ __launch_bounds__(256) void resize_bilinear_nchw4_kernel(const TI* __
             const Taps tx = taps_for(x4 * 4 + k, w, W);
             const float v00 = io<TI>::ld(r0 + (long long)tx.i0 * C), v01 = io<TI>::ld(r0 + (long long)tx.i1 * C);
             const float v10 = io<TI>::ld(r1 + (long long)tx.i0 * C), v11 = io<TI>::ld(r1 + (long long)tx.i1 * C);
-            const float top = v00 + (v01 - v00) * tx.w1, bot = v10 + (v11 - v10) * tx.w1;
-            o[k] = top + (bot - top) * ty.w1;
+            o[k] = bilerp(v00, v01, v10, v11, tx.w1, ty.w1);
         }
         *(float4*)(y + idx * 4) = make_float4(o[0], o[1], o[2], o[3]);
+    }
+}
+
+// ---- label map: bilinear up-sampling + argmax over the classes, the logits at the output resolution never leave registers ----
+// jnp.argmax: the first maximum; a NaN beats every number and the first NaN stays (nothing compares greater than it)
+__device__ __forceinline__ void argmax_step(float v, int c, float& best, int& arg) {
+    if (v > best || (v != v && best == best)) {
+        best = v;
+        arg = c;
+    }
+}
+
+template <typename TI> struct pix_vec;                  // the 16-byte piece of a pixel's channel vector
+template <> struct pix_vec<float> {
+    static constexpr int N = 4;
+    __device__ static __forceinline__ void ld(const float* p, float* o) {
+        const float4 v = *(const float4*)p;
+        o[0] = v.x; o[1] = v.y; o[2] = v.z; o[3] = v.w;
+    }
+};
+template <> struct pix_vec<bf16_t> {
+    static constexpr int N = 8;
+    __device__ static __forceinline__ void ld(const bf16_t* p, float* o) {
+        const uint4 v = *(const uint4*)p;
+        const uint32_t u[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            o[2 * i] = __uint_as_float(u[i] << 16);
+            o[2 * i + 1] = __uint_as_float(u[i] & 0xffff0000u);
+        }
+    }
+};
+
+// A lane owns four consecutive output x of one row (lanes of a wave: consecutive groups, so the label stores of a wave are one
+// contiguous 256-byte run and the source pixels it reads are a few neighbouring cache lines of a map that lives in L2).  It walks
+// the channels in increasing order; VEC: C is a whole number of 16-byte pieces and x is 16-byte aligned, so every pixel's vector
+// is read in 16-byte loads.  Columns past W (ragged last group) are computed at W - 1 and not stored.
+template <typename TI, bool VEC>
+__global__ __launch_bounds__(256) void resize_argmax_kernel(const TI* __restrict__ x, uint8_t* __restrict__ labels, int B, int h,
+                                                            int w, int C, int H, int W) {
+    const int W4 = (W + 3) >> 2;
+    const long long total = (long long)B * H * W4;
+    for (long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (long long)gridDim.x * blockDim.x) {
+        long long r = idx;
+        const int x4 = (int)(r % W4); r /= W4;
+        const int oy = (int)(r % H);
+        const int b = (int)(r / H);
+        const Taps ty = taps_for(oy, h, H);
+        const TI* r0 = x + ((long long)b * h + ty.i0) * w * C;
+        const TI* r1 = x + ((long long)b * h + ty.i1) * w * C;
+        Taps tx[4];
+        float best[4];
+        int arg[4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const int ox = x4 * 4 + k;
+            tx[k] = taps_for(ox < W ? ox : W - 1, w, W);
+            best[k] = -INFINITY;                     // class 0 stays the answer unless a later class is greater or a NaN
+            arg[k] = 0;
+        }
+        if (VEC) {
+            constexpr int N = pix_vec<TI>::N;
+            for (int c = 0; c < C; c += N) {
+#pragma unroll
+                for (int k = 0; k < 4; ++k) {
+                    float v00[N], v01[N], v10[N], v11[N];
+                    pix_vec<TI>::ld(r0 + (long long)tx[k].i0 * C + c, v00);
+                    pix_vec<TI>::ld(r0 + (long long)tx[k].i1 * C + c, v01);
+                    pix_vec<TI>::ld(r1 + (long long)tx[k].i0 * C + c, v10);
+                    pix_vec<TI>::ld(r1 + (long long)tx[k].i1 * C + c, v11);
+#pragma unroll
+                    for (int j = 0; j < N; ++j) {
+                        const float v = bilerp(v00[j], v01[j], v10[j], v11[j], tx[k].w1, ty.w1);
+                        argmax_step(v, c + j, best[k], arg[k]);
+                    }
+                }
+            }
+        } else {
+            for (int c = 0; c < C; ++c) {
+#pragma unroll
+                for (int k = 0; k < 4; ++k) {
+                    const float v00 = io<TI>::ld(r0 + (long long)tx[k].i0 * C + c), v01 = io<TI>::ld(r0 + (long long)tx[k].i1 * C + c);
+                    const float v10 = io<TI>::ld(r1 + (long long)tx[k].i0 * C + c), v11 = io<TI>::ld(r1 + (long long)tx[k].i1 * C + c);
+                    const float v = bilerp(v00, v01, v10, v11, tx[k].w1, ty.w1);
+                    argmax_step(v, c, best[k], arg[k]);
+                }
+            }
+        }
+        uint8_t* out = labels + ((long long)b * H + oy) * W + (long long)x4 * 4;
+        if (x4 * 4 + 4 <= W && ((uintptr_t)out & 3) == 0) {
+            *(uint32_t*)out = (uint32_t)arg[0] | ((uint32_t)arg[1] << 8) | ((uint32_t)arg[2] << 16) | ((uint32_t)arg[3] << 24);
+        } else {                                     // ragged W % 4 tail, or rows that do not start on a 4-byte boundary
+#pragma unroll
+            for (int k = 0; k < 4; ++k)
+                if (x4 * 4 + k < W) out[k] = (uint8_t)arg[k];
+        }
     }
 }
 
@@ -135,6 +236,32 @@ int mv_resize_bilinear_nhwc_fwd(const void* x, void* y, int N, int h, int w, int
     else if (in_dtype == MV_BF16) GO(bf16_t, bf16_t);
     else if (out_dtype == MV_F32) GO(float, float);
     else GO(float, bf16_t);
+#undef GO
+    MV_LAUNCH_CHECK();
+    return MV_OK;
+}
+
+int mv_resize_argmax_nhwc_fwd(const void* x, void* labels, int B, int h, int w, int C, int H, int W, int x_dtype,
+                              mv_stream_t stream) {
+    MV_CHECK_ARG(x && labels, "resize_argmax: NULL buffer");
+    MV_CHECK_ARG(B > 0 && h > 0 && w > 0 && C > 0 && H > 0 && W > 0, "resize_argmax: bad dimensions B=%d %dx%dx%d -> %dx%d", B, h, w, C,
+                 H, W);
+    MV_CHECK_ARG(C <= 256, "resize_argmax: %d classes do not fit a uint8 label (at most 256)", C);
+    MV_CHECK_ARG(x_dtype == MV_F32 || x_dtype == MV_BF16, "resize_argmax: bad dtype %d", x_dtype);
+    MV_CHECK_ARG(H >= h && W >= w, "resize_argmax: down-sampling (%dx%d -> %dx%d) is not supported, only up-sampling", h, w, H, W);
+    hipStream_t st = (hipStream_t)stream;
+    const int grid = grid_of((long long)B * H * ((W + 3) / 4));
+    const bool vec = (uintptr_t)x % 16 == 0 && C % (x_dtype == MV_BF16 ? 8 : 4) == 0;
+    set_kernel_name(vec ? "resize_argmax_nhwc_v16" : "resize_argmax_nhwc");
+#define GO(TI, V) \
+    hipLaunchKernelGGL((resize_argmax_kernel<TI, V>), dim3(grid), dim3(256), 0, st, (const TI*)x, (uint8_t*)labels, B, h, w, C, H, W)
+    if (x_dtype == MV_BF16) {
+        if (vec) GO(bf16_t, true);
+        else GO(bf16_t, false);
+    } else {
+        if (vec) GO(float, true);
+        else GO(float, false);
+    }
 #undef GO
     MV_LAUNCH_CHECK();
     return MV_OK;

@@ -339,6 +339,8 @@ def filter_jit(fn: Callable = None, *, use_graph: bool = True, clone_outputs: bo
             if not leaves or not all(t is None or (isinstance(t, torch.Tensor) and t.is_cuda and t.shape[0] == step and t.is_contiguous())
                                      for t in leaves) or all(t is None for t in leaves):
                 return                               # only batched tensors (or tuples of them / None) are laned; fall back
+            if any(t is not None and t.dtype not in (torch.float32, torch.bfloat16) for t in leaves):
+                return                               # label maps / indices (postprocess): `gather` copies fp32 / bf16 rows only
             lane_calls.append(calls)
             outs.append(o)
         structured = isinstance(outs[0], (tuple, list))

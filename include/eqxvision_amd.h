@@ -510,6 +510,23 @@ int64_t mv_splitk_scratch_bytes(int64_t M, int64_t N, int64_t K_reduction);
 int mv_resize_bilinear_nhwc_fwd(const void* x, void* y, int N, int h, int w, int C, int H, int W, int in_dtype, int out_dtype,
                                 int out_nchw, mv_stream_t stream);
 
+/* The label map of a dense head in one launch: labels[b][y][x] = the first index of the maximum over c of the value that
+ * mv_resize_bilinear_nhwc_fwd (fp32 output) writes for (b, c, y, x) -- the same taps and the same interpolation expression, so
+ * the result equals argmax over the class axis of that tensor, which is never written.  x NHWC [B,h,w,C], MV_F32 or MV_BF16;
+ * labels uint8 [B,H,W].  Ties go to the lower class, a NaN beats every number and the first NaN wins (jnp.argmax).
+ * MV_E_INVALID: a NULL buffer, a non-positive size, C > 256, an unknown dtype, H < h or W < w. */
+int mv_resize_argmax_nhwc_fwd(const void* x, void* labels, int B, int h, int w, int C, int H, int W, int x_dtype,
+                              mv_stream_t stream);
+
+/* Classifier tail in one launch: the k largest of each row of logits fp32 [B][K], values fp32 [B][k] and indices int32 [B][k]
+ * sorted by value descending, equal values by ascending index (jax.lax.top_k).  want_prob = 0: values are the selected logits,
+ * bit for bit; want_prob = 1: values are softmax probabilities expf(v - max) / sum_j expf(l_j - max) in fp32.  -0 and +0 are
+ * equal values; a NaN orders above every number (and makes the probabilities of its row NaN).  1 <= K <= 65536, 1 <= k <= min(K, 16), else MV_E_INVALID.  One workgroup per row, no scratch, no atomics:
+ * repeated runs give the same bits. */
+#define MV_TOPK_MAX_K 16
+int mv_softmax_topk_f32(const float* logits, float* values, int* indices, int B, int K, int k, int want_prob,
+                        mv_stream_t stream);
+
 /* rows x row_bytes strided copy (jnp.concatenate of NHWC maps along channels, deeplabv3.py:132-136: one call per source with
  * dst offset by the channels already placed).  Sizes and pitches in bytes, multiples of 2. */
 int mv_copy_rows(const void* src, void* dst, int64_t rows, int64_t row_bytes, int64_t src_pitch, int64_t dst_pitch,
