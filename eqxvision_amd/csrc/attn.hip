@@ -349,3 +349,31 @@ int mha_mfma_launch(const void* qkv, int head_major, void* out, float* probs, in
 }
 
 }  // namespace mv
+
+using namespace mv;
+
+extern "C" {
+
+int mv_mha_heads_fwd(const void* qkv, void* out, float* probs, int B, int N, int H, int dh, float scale, int dtype,
+                     mv_stream_t stream) {
+    MV_CHECK_ARG(qkv && out && B > 0 && N > 0 && H > 0 && dh > 0, "mha_heads: bad args");
+    if (dtype != MV_BF16 || !mha_mfma_supported(N, dh, dtype)) {
+        set_error("mha_heads: unsupported N=%d dh=%d dtype=%d", N, dh, dtype);
+        return MV_E_UNSUPPORTED;
+    }
+    return mha_mfma_launch(qkv, 1, out, probs, B, N, H, dh, scale, nullptr, 1.f, (hipStream_t)stream);
+}
+
+int mv_mha_dropout_fwd(const void* qkv, int head_major, void* out, float* probs, const uint32_t* keys, float keep_prob,
+                       int B, int N, int H, int dh, float scale, int dtype, mv_stream_t stream) {
+    MV_CHECK_ARG(qkv && out && keys && B > 0 && N > 0 && H > 0 && dh > 0, "mha_dropout: bad args");
+    MV_CHECK_ARG(keep_prob > 0.f && keep_prob <= 1.f, "mha_dropout: keep_prob %g outside (0, 1]", (double)keep_prob);
+    MV_CHECK_ARG((long long)H * N * N < (1LL << 32), "mha_dropout: more than 2^32 probabilities per sample");
+    if (dtype != MV_BF16 || !mha_mfma_supported(N, dh, dtype)) {
+        set_error("mha_dropout: unsupported N=%d dh=%d dtype=%d (bf16, dh 32 / 64, N <= 256)", N, dh, dtype);
+        return MV_E_UNSUPPORTED;
+    }
+    return mha_mfma_launch(qkv, head_major, out, probs, B, N, H, dh, scale, keys, keep_prob, (hipStream_t)stream);
+}
+
+}  // extern "C"

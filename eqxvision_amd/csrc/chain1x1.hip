@@ -16,6 +16,7 @@
 //   * after the fourth chunk the 32 x 64 result goes through the usual patch transpose and is stored as whole lines.
 // The second GEMM therefore sees y exactly as the next layer would read it from HBM (bf16-rounded): bit-identical to
 // the un-fused pair.
+#include "conv_launchers.h"
 #include "mfma_common.h"
 
 namespace mv {
@@ -323,14 +324,15 @@ int chain1x1_launch(const void* x, const void* w3, const float* scale3, const fl
     return chain_go<128, 6, false>(p, st);
 }
 
-int chain1x1_sub_supported(long long N, int H, int W, int C, int K, int N2, int dtype) {
+static int chain1x1_sub_supported(long long N, int H, int W, int C, int K, int N2, int dtype) {
     return chain1x1_supported(N * H * W, C, K, N2, dtype) && N2 == 128 && H % 2 == 0 && W % 2 == 0 &&
            N * (H / 2) * (W / 2) * K * 2 < (1LL << 31) && !get_flag("no_chain_sub");
 }
 
 // as chain1x1_launch with N2 = 128, y = the stride-2 sub-sampling [N][H/2][W/2][256] of the block output
-int chain1x1_sub_launch(const void* x, const void* w3, const float* scale3, const float* shift3, const void* residual, void* y_sub,
-                        const void* w1, const float* scale1, const float* shift1, void* t1, int N, int H, int W, hipStream_t st) {
+static int chain1x1_sub_launch(const void* x, const void* w3, const float* scale3, const float* shift3, const void* residual,
+                               void* y_sub, const void* w1, const float* scale1, const float* shift1, void* t1, int N, int H, int W,
+                               hipStream_t st) {
     ChainP p;
     p.x = (const bf16_t*)x; p.x2 = nullptr; p.w3 = (const bf16_t*)w3; p.scale3 = scale3; p.shift3 = shift3;
     p.residual = (const bf16_t*)residual; p.y = (bf16_t*)y_sub;
@@ -359,3 +361,26 @@ int chain1x1_dual_launch(const void* x, const void* x2, const void* wcat, const 
 }
 
 }  // namespace mv
+
+using namespace mv;
+
+extern "C" {
+
+int mv_conv1x1_chain_sub_supported(int N, int H, int W, int C, int K, int N2, int dtype) {
+    return !get_flag("force_generic") && !get_flag("no_stream") && N > 0 && H > 0 && W > 0 && chain1x1_sub_supported(N, H, W, C, K, N2, dtype);
+}
+
+int mv_conv1x1_chain_sub_fwd(const void* x, const void* w3, const float* scale3, const float* shift3, const void* residual,
+                             void* y_sub, const void* w1, const float* scale1, const float* shift1, void* t1, int N, int H, int W,
+                             int C, int K, int N2, int dtype, mv_stream_t stream) {
+    MV_CHECK_ARG(x && w3 && residual && y_sub && w1 && t1, "conv1x1_chain_sub: NULL pointer");
+    if (!mv_conv1x1_chain_sub_supported(N, H, W, C, K, N2, dtype)) {
+        set_error("conv1x1_chain_sub: unsupported shape N=%d H=%d W=%d C=%d K=%d N2=%d (ask mv_conv1x1_chain_sub_supported first)", N, H,
+                  W, C, K, N2);
+        return MV_E_UNSUPPORTED;
+    }
+    MV_CHECK_ARG(y_sub != residual && y_sub != x && t1 != y_sub, "conv1x1_chain_sub: y_sub must not alias x / residual / t1");
+    return chain1x1_sub_launch(x, w3, scale3, shift3, residual, y_sub, w1, scale1, shift1, t1, N, H, W, (hipStream_t)stream);
+}
+
+}  // extern "C"

@@ -20,6 +20,7 @@
 // get BUF_OOB), the chunk loop is unrolled by two (buffer parity is a compile-time constant), the last pair is peeled.
 #include <type_traits>
 #include "chain_acc.h"
+#include "conv_launchers.h"
 
 namespace mv {
 

@@ -37,6 +37,7 @@
 // without), NPREV = 1 102-114 us (chain1x1: 109) -- of which ~35 us are its 205 MB of y stores, which do not overlap its 65 us of
 // instruction stream (debug-build ablations, same file); resnet50 B = 256: +2.5 ... 3.1 % with the plan on, same box.
 #include "chain_acc.h"
+#include "conv_launchers.h"
 
 namespace mv {
 
@@ -210,7 +211,7 @@ __global__ __launch_bounds__(WAVES * 64) void chain_rc_kernel(const ChainRcP p) 
     if (tile < p.tiles_m) run_tile(xa, tile, tile);
 }
 
-int chain_rc_supported(long long M, int C, int K, int N2, int dtype) {
+static int chain_rc_supported(long long M, int C, int K, int N2, int dtype) {
     return dtype == MV_BF16 && C == 64 && K == 256 && N2 == 64 && M >= 8192 && M < (1LL << 31) - (1 << 20) && !get_flag("no_chain") &&
            !get_flag("no_chain_rc");
 }
@@ -221,8 +222,8 @@ static int chain_rc_go(ChainRcP& p, hipStream_t st) {
     return chain_acc_go<chain_rc_kernel<NPREV, WAVES, RD>, WAVES, SMEM>(p, chain_acc_grid(p.tiles_m, WAVES), st);
 }
 
-int chain_rc_launch(const void* t2, const void* t2_prev, const void* x0, const void* wfrag, const void* shifts, void* y, void* t1,
-                    long long M, hipStream_t st) {
+static int chain_rc_launch(const void* t2, const void* t2_prev, const void* x0, const void* wfrag, const void* shifts, void* y,
+                           void* t1, long long M, hipStream_t st) {
     ChainRcP p;
     p.t2 = (const bf16_t*)t2; p.t2p = (const bf16_t*)t2_prev; p.x0 = (const bf16_t*)x0; p.wf = (const bf16_t*)wfrag;
     p.sh = (const unsigned*)shifts;
@@ -238,7 +239,8 @@ int chain_rc_launch(const void* t2, const void* t2_prev, const void* x0, const v
 }
 
 // the first boundary without its output map: t2 = the first block's conv2 output, x0 = the stage input
-int chain_rc0_launch(const void* t2, const void* x0, const void* wfrag, const void* shifts, void* t1, long long M, hipStream_t st) {
+static int chain_rc0_launch(const void* t2, const void* x0, const void* wfrag, const void* shifts, void* t1, long long M,
+                            hipStream_t st) {
     ChainRcP p;
     p.t2 = nullptr; p.t2p = (const bf16_t*)t2; p.x0 = (const bf16_t*)x0; p.wf = (const bf16_t*)wfrag; p.sh = (const unsigned*)shifts;
     p.y = nullptr; p.t1 = (bf16_t*)t1;
@@ -461,3 +463,38 @@ int chain_res_launch(const void* t2, const void* residual, const void* wfrag, co
 }
 
 }  // namespace mv
+
+using namespace mv;
+
+extern "C" {
+
+int mv_conv1x1_chain_rc_supported(int64_t M, int C, int K, int N2, int dtype) {
+    return !get_flag("force_generic") && !get_flag("no_stream") && chain_rc_supported(M, C, K, N2, dtype);
+}
+
+int mv_conv1x1_chain_rc_fwd(const void* t2, const void* t2_prev, const void* x0, const void* wfrag, const void* shifts, void* y,
+                            void* t1, int64_t M, int C, int K, int N2, int dtype, mv_stream_t stream) {
+    MV_CHECK_ARG(t2 && t2_prev && x0 && wfrag && shifts && y && t1, "conv1x1_chain_rc: NULL pointer");
+    if (!mv_conv1x1_chain_rc_supported(M, C, K, N2, dtype)) {
+        set_error("conv1x1_chain_rc: unsupported shape M=%lld C=%d K=%d N2=%d (ask mv_conv1x1_chain_rc_supported first)", (long long)M, C,
+                  K, N2);
+        return MV_E_UNSUPPORTED;
+    }
+    MV_CHECK_ARG(y != t2 && y != t2_prev && y != x0 && t1 != y && t1 != t2 && t1 != t2_prev && t1 != x0,
+                 "conv1x1_chain_rc: outputs must not alias inputs");
+    return chain_rc_launch(t2, t2_prev, x0, wfrag, shifts, y, t1, M, (hipStream_t)stream);
+}
+
+int mv_conv1x1_chain_rc0_fwd(const void* t2, const void* x0, const void* wfrag, const void* shifts, void* t1, int64_t M, int C, int K,
+                             int N2, int dtype, mv_stream_t stream) {
+    MV_CHECK_ARG(t2 && x0 && wfrag && shifts && t1, "conv1x1_chain_rc0: NULL pointer");
+    if (!mv_conv1x1_chain_rc_supported(M, C, K, N2, dtype)) {
+        set_error("conv1x1_chain_rc0: unsupported shape M=%lld C=%d K=%d N2=%d (ask mv_conv1x1_chain_rc_supported first)", (long long)M, C,
+                  K, N2);
+        return MV_E_UNSUPPORTED;
+    }
+    MV_CHECK_ARG(t1 != t2 && t1 != x0, "conv1x1_chain_rc0: t1 must not alias an input");
+    return chain_rc0_launch(t2, x0, wfrag, shifts, t1, M, (hipStream_t)stream);
+}
+
+}  // extern "C"

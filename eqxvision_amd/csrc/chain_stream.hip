@@ -24,6 +24,7 @@
 // values) and nothing between a load and its use is conditional -- stores of rows past the end go to row M-1 instead, with
 // the values row M-1 gets anyway (its x and residual rows are what the clamped loads returned), so y must not alias residual.
 #include <type_traits>
+#include "conv_launchers.h"
 #include "mfma_common.h"
 
 namespace mv {

@@ -79,6 +79,18 @@ __device__ __forceinline__ float apply_act_rt(float v, int act) {
     return v;
 }
 
+// reductions over the 64 lanes of a wave (every lane gets the result)
+__device__ __forceinline__ float wave_max(float v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o));
+    return v;
+}
+__device__ __forceinline__ float wave_sum(float v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+    return v;
+}
+
 // ---- host side ------------------------------------------------------------------------
 void set_error(const char* fmt, ...);
 void set_kernel_name(const char* name);
@@ -167,92 +179,46 @@ template <class P> int fill_geometry(P& p, const ConvShape& s, const char* who, 
     return MV_OK;
 }
 
-// The launchers that execute a route (route.h holds the rule, its predicates and the kernels' names), implemented in the kernel
-// translation units.  igemm_launch: every route of route_conv but Kern::generic.
-int igemm_launch(const void* x, const void* w, const float* scale, const float* shift, const void* residual, void* y,
-                 const ConvShape& s, Route r, hipStream_t stream);
-int igemm_grouped64_supported(int C, int K, int R, int S, int groups, int in_dtype, int out_dtype);
-int igemm_grouped64_window(int C, int groups);
-int igemm_grouped64_launch(const void* x, const void* w64, const float* scale, const float* shift, const void* residual, void* y,
-                           int N, int H, int W, int C, int K, int R, int S, int sh, int sw, int ph, int pw, int dh, int dw, int groups,
-                           int act, int out_dtype, hipStream_t stream);
-int dwconv_supported(int C, int K, int groups, int R, int S, int in_dtype, int out_dtype);
-int dwconv_launch(const void* x, const void* w, const float* scale, const float* shift, void* y, int N, int H, int W, int C, int R,
-                  int S, int sh, int sw, int ph, int pw, int dh, int dw, int act, hipStream_t stream);
+// Launch grids of the grid-stride kernels: one thread per element, capped at 16 blocks per CU
+inline int grid_for(long long n, int block = 256) {
+    long long g = (n + block - 1) / block;
+    if (g > 256 * 16) g = 256 * 16;
+    if (g < 1) g = 1;
+    return (int)g;
+}
+
+// One (in, out) dtype ladder for the memory-bound entries: dispatch_io calls f(TI{}, TO{}) with the element types of the two
+// dtypes (a generic lambda that launches its kernel and returns a status); a dtype outside {MV_F32, MV_BF16} is an error that
+// names the entry, raised before any HIP call.  dispatch_dtype is the same for entries with one dtype.
+template <class F> int dispatch_dtype(const char* who, int dtype, F&& f) {
+    if (dtype == MV_BF16) return f(bf16_t{});
+    if (dtype == MV_F32) return f(float{});
+    set_error("%s: unknown dtype %d", who, dtype);
+    return MV_E_INVALID;
+}
+template <class F> int dispatch_io(const char* who, int in_dtype, int out_dtype, F&& f) {
+    return dispatch_dtype(who, in_dtype, [&](auto ti) { return dispatch_dtype(who, out_dtype, [&](auto to) { return f(ti, to); }); });
+}
+
+// Launchers with a caller in ANOTHER translation unit than the one that defines them (route.h holds the rule that picks among
+// them, its predicates and the kernels' names).  A launcher only its own file's entries call is static there; the ones only the
+// routing entries of conv_fallback.hip call are declared in conv_launchers.h.
 int stream1x1_launch(const void* x, const void* w, const float* scale, const float* shift, const void* residual,
                      void* y, long long M, int C, int K, int act, int out_dtype, hipStream_t stream);
-int ln_mlp_supported(long long M, int C, int hidden, int x_dtype);
-int ln_mlp_launch(const void* x, const void* w1, const float* b1, const void* w2, const float* b2, void* y, long long M,
-                  float eps, int x_dtype, hipStream_t st);
-int ln_mlp_res_launch(const void* x, const float* res, const void* w1, const float* b1, const void* w2, const float* b2, float* y,
-                      long long M, float eps, int x_dtype, hipStream_t st);
-int stream1x1_ln_supported(long long M, int C, int K, int x_dtype, int out_dtype);
-int stream1x1_ln_launch(const void* x, const void* w, const float* shift, void* y, long long M, int C, int K, float eps, int act,
-                        int x_dtype, hipStream_t st);
 int igemm2_launch(const void* x, const void* w, const float* scale, const float* shift, const void* residual, void* y,
                   const ConvShape& s, int tile, int tok, hipStream_t stream);   // tile: 1 = 256x64, 2 = 256x128, 3 = 256x256, 0 = its own rule
-int igemm2_tile_shape(long long M, int K, int* bm, int* bn);
-int igemm2_dual_launch(const void* x, const void* x2, const void* w, const float* scale, const float* shift, void* y, int N,
-                       int Ho, int Wo, int C1, int H2, int W2, int C2, int s2, int K, int act, int tile, hipStream_t st);   // tile: 2 = 256x128, 3 = 256x256
-int chain1x1_supported(long long M, int C, int K, int N2, int dtype);
-int chain1x1_dual_supported(long long M, int C1, int C2, int K, int N2, int dtype);
-int chain1x1_dual_launch(const void* x, const void* x2, const void* wcat, const float* scale3, const float* shift3, void* y,
-                         const void* w1, const float* scale1, const float* shift1, void* t1, long long M, hipStream_t st);
-int chain1x1_launch(const void* x, const void* w3, const float* scale3, const float* shift3, const void* residual, void* y,
-                    const void* w1, const float* scale1, const float* shift1, void* t1, long long M, int N2, hipStream_t st);
-int chain1x1_sub_supported(long long N, int H, int W, int C, int K, int N2, int dtype);
-int chain1x1_sub_launch(const void* x, const void* w3, const float* scale3, const float* shift3, const void* residual, void* y_sub,
-                        const void* w1, const float* scale1, const float* shift1, void* t1, int N, int H, int W, hipStream_t st);
-int chain_rc_supported(long long M, int C, int K, int N2, int dtype);
-int chain_rc_launch(const void* t2, const void* t2_prev, const void* x0, const void* wfrag, const void* shifts, void* y, void* t1,
-                    long long M, hipStream_t st);
-int chain_rc0_launch(const void* t2, const void* x0, const void* wfrag, const void* shifts, void* t1, long long M, hipStream_t st);
-int chain_res_supported(long long N, int H, int W, int C, int K, int N2, int sub, int dtype);
-int chain_res_launch(const void* t2, const void* residual, const void* wfrag, const void* shifts, void* y, void* t1, int N, int H, int W,
-                     int sub, hipStream_t st);
-int chain_l2_res_supported(long long N, int H, int W, int C, int K, int N2, int sub, int dtype);
-int chain_l2_res_launch(const void* t2, const void* residual, const void* wfrag, const void* shifts, void* y, void* t1, int N, int H,
-                        int W, int N2, int sub, hipStream_t st);
-int chain_l2_dual_supported(long long M, int C1, int C2, int K, int N2, int dtype);
-int chain_l2_dual_launch(const void* t2, const void* x, const void* wfrag, const void* shifts, void* y, void* t1, long long M,
-                         hipStream_t st);
-int chain_stream_supported(long long M, int C, int K, int N2, int dtype);
-int chain_stream_launch(const void* x, const void* w3, const float* scale3, const float* shift3, const void* residual, void* y,
-                        const void* w1, const float* scale1, const float* shift1, void* t1, long long M, hipStream_t st);
 int device_status(int clear, unsigned* out);              // igemm8.hip: the status word of mv_device_status
 unsigned* device_status_word();                           // its device address (nullptr if the runtime cannot give it)
 int igemm8_launch(const void* x, const void* w, const float* scale, const float* shift, const void* residual, void* y,
                   const ConvShape& s, int tok, int tile, hipStream_t st);       // tile: 1 = 256x256, 2 = 128x256, 3 = 256x128
-bool igemm8_ln_supported(long long M, int N, int K);
-int igemm8_lnout_launch(const void* x, const void* w, const float* shift, const void* res, const void* res_lo, void* y, void* y_lo,
-                        float* stats, long long M, int N, int K, hipStream_t st);
-int igemm8_lnin_launch(const void* x, const float* stats, const void* w, const float* colsum, const float* shift, void* y, long long M,
-                       int N, int K, float eps, int act, int tok, hipStream_t st);
-int igemm8_dual_launch(const void* x, const void* x2, const void* w, const float* scale, const float* shift,
-                       const void* residual, void* y, int N, int Ho, int Wo, int C1, int H2, int W2, int C2, int s2, int K,
-                       int act, int out_dtype, int tile, hipStream_t st);
-int stem_supported(int C, int K, int R, int S, int x_dtype, int out_dtype);
-int stem_f32out_supported(int C, int H, int W, int K, int R, int S, int sh, int sw, int ph, int pw, int x_dtype);
-int stem_launch(const void* x, const void* w, const float* scale, const float* shift, void* y, int N, int C,
-                int H, int W, int K, int R, int S, int sh, int sw, int ph, int pw, int act, int x_dtype,
-                int out_dtype, int tok_stride, int tok_offset, const float* pos, hipStream_t stream,
-                const void* w_lo = nullptr);   // w_lo: low halves of split-precision weights (generic kernel only)
-int skinny_f32_launch(const void* x, const void* w, const float* scale, const float* shift, void* y, long long M, int C, int K,
-                      int act, hipStream_t stream);
 int swin_mfma_supported(int C, int heads, int ws_h, int ws_w, int dtype);
 int swin_mfma_launch(const void* qkv, const float* bias, void* out, int B, int Hf, int Wf, int C, int heads, int ws_h,
                      int ws_w, int shift_h, int shift_w, const uint32_t* drop_keys, float keep, hipStream_t st,
                      const float* rnorm = nullptr, const float* logit_mul = nullptr);   // rnorm given: Swin V2's cosine logits
-int swin_qk_rnorm_launch(const void* qkv, float* rnorm, int B, int Hf, int Wf, int C, int ws_h, int ws_w, int shift_h, int shift_w,
-                         int dtype, hipStream_t st);
 int conv3x3c64_v2_launch(const void* x, const void* w, const float* scale, const float* shift, void* y, int N, int H,
                          int W, int act, hipStream_t stream);
 int skinny_launch(const void* x, const void* w, const float* scale, const float* shift, void* y, long long M, int C, int K,
                   int act, int out_dtype, hipStream_t stream);
-int stem_pool_supported(int C, int K, int R, int S, int sh, int sw, int ph, int pw, int pk, int ps, int pp, int act,
-                        int x_dtype, int out_dtype, long long in_elems);
-int stem_pool_launch(const void* x, const void* w, const float* scale, const float* shift, void* y, int N, int H, int W, int R,
-                     int x_dtype, hipStream_t stream);
 int mha_mfma_supported(int N, int dh, int dtype);
 int mha_mfma_launch(const void* qkv, int head_major, void* out, float* probs, int B, int N, int H, int dh, float scale,
                     const uint32_t* drop_keys, float keep, hipStream_t st);

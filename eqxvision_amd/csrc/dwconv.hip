@@ -223,12 +223,12 @@ __global__ __launch_bounds__(256) void dwconv_tile_kernel(const DwP p) {
     }
 }
 
-int dwconv_supported(int C, int K, int groups, int R, int S, int in_dtype, int out_dtype) {
+static int dwconv_supported(int C, int K, int groups, int R, int S, int in_dtype, int out_dtype) {
     return groups == C && K == C && C % 8 == 0 && R * S <= 49 && in_dtype == MV_BF16 && out_dtype == MV_BF16;
 }
 
-int dwconv_launch(const void* x, const void* w, const float* scale, const float* shift, void* y, int N, int H, int W, int C, int R,
-                  int S, int sh, int sw, int ph, int pw, int dh, int dw, int act, hipStream_t st) {
+static int dwconv_launch(const void* x, const void* w, const float* scale, const float* shift, void* y, int N, int H, int W, int C,
+                         int R, int S, int sh, int sw, int ph, int pw, int dh, int dw, int act, hipStream_t st) {
     DwP p;
     p.x = (const bf16_t*)x; p.w = (const bf16_t*)w; p.scale = scale; p.shift = shift; p.y = (bf16_t*)y;
     p.N = N; p.H = H; p.W = W; p.C = C; p.R = R; p.S = S;
@@ -280,3 +280,28 @@ int dwconv_launch(const void* x, const void* w, const float* scale, const float*
 }
 
 }  // namespace mv
+
+using namespace mv;
+
+extern "C" {
+
+int mv_dwconv2d_supported(int C, int K, int groups, int R, int S, int in_dtype, int out_dtype) {
+    return !get_flag("force_generic") && !get_flag("no_dwconv") && dwconv_supported(C, K, groups, R, S, in_dtype, out_dtype);
+}
+
+int mv_dwconv2d_nhwc_fwd(const void* x, const void* w_rsc, const float* scale, const float* shift, void* y, int N, int H, int W,
+                         int C, int R, int S, int sh, int sw, int ph, int pw, int dh, int dw, int act, int in_dtype, int out_dtype,
+                         mv_stream_t stream) {
+    MV_CHECK_ARG(x && w_rsc && y, "dwconv2d: NULL pointer");
+    MV_CHECK_ARG(N > 0 && H > 0 && W > 0 && C > 0 && R > 0 && S > 0 && sh > 0 && sw > 0 && ph >= 0 && pw >= 0 && dh > 0 && dw > 0,
+                 "dwconv2d: bad dims");
+    const long long Ho = (H + 2 * ph - dh * (R - 1) - 1) / sh + 1, Wo = (W + 2 * pw - dw * (S - 1) - 1) / sw + 1;
+    MV_CHECK_ARG(Ho > 0 && Wo > 0, "dwconv2d: empty output");
+    if (!mv_dwconv2d_supported(C, C, C, R, S, in_dtype, out_dtype)) {
+        set_error("dwconv2d: unsupported configuration C=%d %dx%d (ask mv_dwconv2d_supported first)", C, R, S);
+        return MV_E_UNSUPPORTED;
+    }
+    return dwconv_launch(x, w_rsc, scale, shift, y, N, H, W, C, R, S, sh, sw, ph, pw, dh, dw, act, (hipStream_t)stream);
+}
+
+}  // extern "C"

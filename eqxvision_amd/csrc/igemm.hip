@@ -22,6 +22,7 @@
 //    tile t+1 is issued before the MFMAs of tile t.
 //  * blockIdx -> tile mapping is XCD-aware: the 8 XCDs (private L2s) each take a contiguous chunk of
 //    the tile list, n-tiles fastest, so every n-tile of one pixel tile hits the same L2.
+#include "conv_launchers.h"
 #include "mfma_common.h"
 
 namespace mv {
@@ -347,7 +348,7 @@ int igemm_launch(const void* x, const void* w, const float* scale, const float* 
 // inside its tile's window, zeros elsewhere -- sixteen 4-channel groups become ONE 64 -> 64 convolution with a block-diagonal
 // weight tile, a 264-channel group a 64 x 320..576 slice.  The k-tile stays a full 128-byte line per pixel, every fragment load is
 // aligned (Cg % 8 == 0 or Cg | 64), and the padded MFMA work (win / Cg x) is far cheaper than the scalar kernel (0.9 TFLOP/s).
-int igemm_grouped64_supported(int C, int K, int R, int S, int groups, int in_dtype, int out_dtype) {
+static int igemm_grouped64_supported(int C, int K, int R, int S, int groups, int in_dtype, int out_dtype) {
     if (groups <= 1 || C != K || C % groups != 0) return 0;
     const int cg = C / groups;
     return in_dtype == MV_BF16 && (out_dtype == MV_BF16 || out_dtype == MV_F32) && C % 8 == 0 && (cg % 8 == 0 || 64 % cg == 0) &&
@@ -355,7 +356,7 @@ int igemm_grouped64_supported(int C, int K, int R, int S, int groups, int in_dty
 }
 
 // the widest per-tile input window, rounded up to a multiple of 64 (what the caller's expanded filters must be laid out for)
-int igemm_grouped64_window(int C, int groups) {
+static int igemm_grouped64_window(int C, int groups) {
     const int cg = C / groups;
     int w = 0;
     for (int n0 = 0; n0 < C; n0 += 64) {
@@ -366,9 +367,9 @@ int igemm_grouped64_window(int C, int groups) {
     return (w + 63) / 64 * 64;
 }
 
-int igemm_grouped64_launch(const void* x, const void* w64, const float* scale, const float* shift, const void* residual, void* y,
-                           int N, int H, int W, int C, int K, int R, int S, int sh, int sw, int ph, int pw, int dh, int dw, int groups,
-                           int act, int out_dtype, hipStream_t st) {
+static int igemm_grouped64_launch(const void* x, const void* w64, const float* scale, const float* shift, const void* residual,
+                                  void* y, int N, int H, int W, int C, int K, int R, int S, int sh, int sw, int ph, int pw, int dh, int dw,
+                                  int groups, int act, int out_dtype, hipStream_t st) {
     IgemmP p;
     p.x = (const bf16_t*)x; p.w = (const bf16_t*)w64; p.scale = scale; p.shift = shift; p.residual = residual; p.y = y;
     const ConvShape s = {N, H, W, C, K, R, S, sh, sw, ph, pw, dh, dw, groups, act, MV_BF16, out_dtype, residual != nullptr};
@@ -381,3 +382,35 @@ int igemm_grouped64_launch(const void* x, const void* w64, const float* scale, c
 }
 
 }  // namespace mv
+
+using namespace mv;
+
+extern "C" {
+
+int mv_conv2d_grouped64_supported(int C, int K, int R, int S, int groups, int in_dtype, int out_dtype) {
+    return !get_flag("force_generic") && !get_flag("no_grouped64") && igemm_grouped64_supported(C, K, R, S, groups, in_dtype, out_dtype);
+}
+
+int mv_conv2d_nhwc_grouped64_fwd(const void* x, const void* w64, const float* scale, const float* shift, const void* residual,
+                                 void* y, int N, int H, int W, int C, int K, int R, int S, int sh, int sw, int ph, int pw, int dh,
+                                 int dw, int groups, int act, int in_dtype, int out_dtype, mv_stream_t stream) {
+    MV_CHECK_FUSED_ACT(act, "conv2d_grouped64");
+    MV_CHECK_ARG(x && w64 && y, "conv2d_grouped64: NULL pointer");
+    MV_CHECK_ARG(N > 0 && H > 0 && W > 0 && C > 0 && K > 0 && R > 0 && S > 0 && sh > 0 && sw > 0 && ph >= 0 && pw >= 0 && dh > 0 &&
+                 dw > 0, "conv2d_grouped64: bad dims");
+    const long long Ho = (H + 2 * ph - dh * (R - 1) - 1) / sh + 1, Wo = (W + 2 * pw - dw * (S - 1) - 1) / sw + 1;
+    MV_CHECK_ARG(Ho > 0 && Wo > 0 && (long long)N * Ho * Wo < (1LL << 31) - 256, "conv2d_grouped64: bad output size");
+    if (!mv_conv2d_grouped64_supported(C, K, R, S, groups, in_dtype, out_dtype)) {
+        set_error("conv2d_grouped64: unsupported configuration C=%d K=%d groups=%d (ask mv_conv2d_grouped64_supported first)", C, K,
+                  groups);
+        return MV_E_UNSUPPORTED;
+    }
+    return igemm_grouped64_launch(x, w64, scale, shift, residual, y, N, H, W, C, K, R, S, sh, sw, ph, pw, dh, dw, groups, act, out_dtype,
+                                  (hipStream_t)stream);
+}
+
+int mv_conv2d_grouped64_window(int C, int groups) {
+    return (groups > 0 && C > 0 && C % groups == 0) ? igemm_grouped64_window(C, groups) : 0;
+}
+
+}  // extern "C"

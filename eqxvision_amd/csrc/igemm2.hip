@@ -15,6 +15,7 @@
 //          scheduled above it (cdna_hip_programming.md section 5.7).
 //  * vmcnt counts in issue order, so the residual / scale / shift prefetch issued before the ring is
 //    always older than any DMA and never disturbs the counts; there are no stores before the epilogue.
+#include "conv_launchers.h"
 #include "igemm_pipe.h"
 
 namespace mv {
@@ -430,7 +431,7 @@ int igemm2_dual_launch(const void* x, const void* x2, const void* w, const float
 }
 
 // block tile igemm2_launch picks for (M rows, K output channels) when it is not told one
-int igemm2_tile_shape(long long M, int K, int* bm, int* bn) {
+static int igemm2_tile_shape(long long M, int K, int* bm, int* bn) {
     const int tile = igemm2_tile_rule(M, K, get_flag("igemm2_tile"));
     *bm = 256;
     *bn = tile == 1 ? 64 : (tile == 3 ? 256 : 128);

@@ -271,7 +271,7 @@ __global__ __launch_bounds__(WAVES * 64) void ln_mlp96_kernel(const LnMlpP p) {
     }
 }
 
-int ln_mlp_supported(long long M, int C, int hidden, int x_dtype) {
+static int ln_mlp_supported(long long M, int C, int hidden, int x_dtype) {
     return C == lm::C && hidden == lm::H && (x_dtype == MV_F32 || x_dtype == MV_BF16) && M >= 1024 && M < (1ll << 31) - 64 &&
            !get_flag("no_ln_mlp");
 }
@@ -287,8 +287,8 @@ static int ln_mlp_go(const LnMlpP& p, hipStream_t st) {
     return MV_OK;
 }
 
-int ln_mlp_launch(const void* x, const void* w1, const float* b1, const void* w2, const float* b2, void* y, long long M,
-                  float eps, int x_dtype, hipStream_t st) {
+static int ln_mlp_launch(const void* x, const void* w1, const float* b1, const void* w2, const float* b2, void* y, long long M,
+                         float eps, int x_dtype, hipStream_t st) {
     LnMlpP p;
     p.x = x; p.res = nullptr; p.w1 = (const bf16_t*)w1; p.b1 = b1; p.w2 = (const bf16_t*)w2; p.b2 = b2; p.y = y;
     p.M = (int)M; p.tiles = (int)((M + 31) / 32); p.eps = eps;
@@ -303,8 +303,8 @@ int ln_mlp_launch(const void* x, const void* w1, const float* b1, const void* w2
     return wv == 16 ? ln_mlp_go<bf16_t, 16>(p, st) : wv == 8 ? ln_mlp_go<bf16_t, 8>(p, st) : ln_mlp_go<bf16_t, 12>(p, st);
 }
 
-int ln_mlp_res_launch(const void* x, const float* res, const void* w1, const float* b1, const void* w2, const float* b2, float* y,
-                      long long M, float eps, int x_dtype, hipStream_t st) {
+static int ln_mlp_res_launch(const void* x, const float* res, const void* w1, const float* b1, const void* w2, const float* b2,
+                             float* y, long long M, float eps, int x_dtype, hipStream_t st) {
     LnMlpP p;
     p.x = x; p.res = res; p.w1 = (const bf16_t*)w1; p.b1 = b1; p.w2 = (const bf16_t*)w2; p.b2 = b2; p.y = y;
     p.M = (int)M; p.tiles = (int)((M + 31) / 32); p.eps = eps;
@@ -317,3 +317,39 @@ int ln_mlp_res_launch(const void* x, const float* res, const void* w1, const flo
 }
 
 }  // namespace mv
+
+using namespace mv;
+
+extern "C" {
+
+int mv_ln_mlp_supported(int64_t M, int C, int hidden, int x_dtype) {
+    return !get_flag("force_generic") && ln_mlp_supported(M, C, hidden, x_dtype);
+}
+
+int mv_ln_mlp_fwd(const void* x, const void* w1, const float* b1, const void* w2, const float* b2, void* y, int64_t M, int C,
+                  int hidden, float eps, int x_dtype, mv_stream_t stream) {
+    MV_CHECK_ARG(x && w1 && b1 && w2 && b2 && y, "ln_mlp: NULL pointer");
+    MV_CHECK_ARG(x != y, "ln_mlp: in-place is not supported (rows are re-read for the residual add)");
+    if (!mv_ln_mlp_supported(M, C, hidden, x_dtype)) {
+        set_error("ln_mlp: unsupported configuration M=%lld C=%d hidden=%d (ask mv_ln_mlp_supported first)", (long long)M, C, hidden);
+        return MV_E_UNSUPPORTED;
+    }
+    return ln_mlp_launch(x, w1, b1, w2, b2, y, M, eps, x_dtype, (hipStream_t)stream);
+}
+
+int mv_ln_mlp_res_supported(int64_t M, int C, int hidden, int x_dtype) {
+    return mv_ln_mlp_supported(M, C, hidden, x_dtype);
+}
+
+int mv_ln_mlp_res_fwd(const void* x, const void* res, const void* w1, const float* b1, const void* w2, const float* b2, void* y,
+                      int64_t M, int C, int hidden, float eps, int x_dtype, mv_stream_t stream) {
+    MV_CHECK_ARG(x && res && w1 && b1 && w2 && b2 && y, "ln_mlp_res: NULL pointer");
+    MV_CHECK_ARG(x != y, "ln_mlp_res: x and y must not alias");
+    if (!mv_ln_mlp_res_supported(M, C, hidden, x_dtype)) {
+        set_error("ln_mlp_res: unsupported configuration M=%lld C=%d hidden=%d (ask mv_ln_mlp_res_supported first)", (long long)M, C, hidden);
+        return MV_E_UNSUPPORTED;
+    }
+    return ln_mlp_res_launch(x, (const float*)res, w1, b1, w2, b2, (float*)y, M, eps, x_dtype, (hipStream_t)stream);
+}
+
+}  // extern "C"

@@ -1,6 +1,6 @@
 // Which matrix-core kernel serves a convolution or a Linear: the whole rule as pure host code.  No HIP header: this file compiles
 // with a plain C++17 host compiler, so a stand-alone program can ask it about every shape of the model zoo without launching
-// anything (tests/test_route_host.py replays tests/data/routes.json through it).  The launchers (igemm.hip, generic.hip) compute
+// anything (tests/test_route_host.py replays tests/data/routes.json through it).  The launchers (igemm.hip, conv_fallback.hip) compute
 // a Route here and execute it; the kernels' files keep only what needs HIP.
 #pragma once
 #include <stddef.h>
@@ -144,7 +144,7 @@ inline int igemm2_dual_supported(long long M, int C1, int C2, int K, int dtype, 
            M < (1LL << 31) - 256 && !flag("no_dual");
 }
 
-// the fp32 matrix-core variants of the generic convolution (generic.hip: conv_generic_dispatch); aligned4 = every stride of x
+// the fp32 matrix-core variants of the generic convolution (conv_fallback.hip: conv_generic_dispatch); aligned4 = every stride of x
 // and w is a multiple of 4 elements and the channel stride is 1
 inline int generic_variant(bool all_f32, int groups, int C, int K, bool aligned4, long long M, FlagFn flag) {
     if (!all_f32 || groups != 1 || flag("no_f32_mfma") || flag("force_generic")) return 0;

@@ -7,6 +7,7 @@
 // both MFMA fragments (16 bytes = 8 reduction elements of one weight row / one input row) come straight from global
 // memory, eight k16-steps in flight; no LDS, no barrier; fp32 or bf16 output written from the accumulator layout
 // (a lane holds 4 consecutive channels of one row: 16-byte stores for fp32).
+#include "conv_launchers.h"
 #include "mfma_common.h"
 
 namespace mv {

@@ -13,6 +13,7 @@
 // Block = 4 waves; each wave owns 32 output pixels x 64 output channels (2 MFMA tiles); the block's
 // 64 x Kp weight slab sits in LDS (row pitch chosen so the 32-row ds_read_b128 fragments are
 // conflict-free) and is reused by every pixel tile the block walks (grid-stride over pixel tiles).
+#include "conv_launchers.h"
 #include "mfma_common.h"
 
 namespace mv {
@@ -693,7 +694,7 @@ int stem_supported(int C, int K, int R, int S, int x_dtype, int out_dtype) {
 }
 
 // fp32 result (the ViT token rows that START the fp32 residual stream): only the non-overlapping-patch GEMM writes it
-int stem_f32out_supported(int C, int H, int W, int K, int R, int S, int sh, int sw, int ph, int pw, int x_dtype) {
+static int stem_f32out_supported(int C, int H, int W, int K, int R, int S, int sh, int sw, int ph, int pw, int x_dtype) {
     return (x_dtype == MV_F32 || x_dtype == MV_BF16) && patch_v2_ok(C, H, W, K, R, S, sh, sw, ph, pw, x_dtype) && !get_flag("stem_v0") &&
            !get_flag("no_patch_f32out");
 }
@@ -750,3 +751,46 @@ int stem_launch(const void* x, const void* w, const float* scale, const float* s
 }
 
 }  // namespace mv
+
+using namespace mv;
+
+extern "C" {
+
+int mv_conv2d_nchw_f32out_supported(int C, int H, int W, int K, int R, int S, int sh, int sw, int ph, int pw, int x_dtype) {
+    return !get_flag("force_generic") && stem_supported(C, K, R, S, x_dtype, MV_BF16) &&
+           stem_f32out_supported(C, H, W, K, R, S, sh, sw, ph, pw, x_dtype);
+}
+
+int mv_conv2d_nchw_f32out_fwd(const void* x, const void* w, const float* scale, const float* shift, void* y, int N, int C,
+                              int H, int W, int K, int R, int S, int sh, int sw, int ph, int pw, int act, int x_dtype,
+                              int tok_stride, int tok_offset, const float* pos, mv_stream_t stream) {
+    MV_CHECK_ARG(act >= MV_ACT_NONE && act <= MV_ACT_SILU, "conv2d_nchw_f32out: unknown activation %d", act);
+    MV_CHECK_ARG(x && w && y, "conv2d_nchw_f32out: NULL pointer");
+    MV_CHECK_ARG(N > 0 && H > 0 && W > 0 && C > 0 && K > 0 && R > 0 && S > 0, "conv2d_nchw_f32out: non-positive dims");
+    if (!mv_conv2d_nchw_f32out_supported(C, H, W, K, R, S, sh, sw, ph, pw, x_dtype)) {
+        set_error("conv2d_nchw_f32out: unsupported configuration (ask mv_conv2d_nchw_f32out_supported first)");
+        return MV_E_UNSUPPORTED;
+    }
+    const int Ho = (H - R) / sh + 1, Wo = (W - S) / sw + 1;
+    MV_CHECK_ARG(tok_stride == 0 || tok_stride >= tok_offset + Ho * Wo, "conv2d_nchw_f32out: tok_stride too small");
+    return stem_launch(x, w, scale, shift, y, N, C, H, W, K, R, S, sh, sw, ph, pw, act, x_dtype, MV_F32, tok_stride, tok_offset, pos,
+                       (hipStream_t)stream);
+}
+
+int mv_conv2d_nchw_split_fwd(const void* x, const void* w_hi, const void* w_lo, const float* scale, const float* shift,
+                             void* y, int N, int C, int H, int W, int K, int R, int S, int sh, int sw, int ph, int pw, int act,
+                             int x_dtype, int out_dtype, mv_stream_t stream) {
+    MV_CHECK_FUSED_ACT(act, "conv2d_nchw_split");
+    MV_CHECK_ARG(x && w_hi && w_lo && y, "conv2d_nchw_split: NULL pointer");
+    MV_CHECK_ARG(N > 0 && H > 0 && W > 0 && C > 0 && K > 0 && R > 0 && S > 0 && sh > 0 && sw > 0 && ph >= 0 && pw >= 0,
+                 "conv2d_nchw_split: bad dims");
+    MV_CHECK_ARG((H + 2 * ph - R) / sh + 1 > 0 && (W + 2 * pw - S) / sw + 1 > 0, "conv2d_nchw_split: empty output");
+    if (get_flag("force_generic") || !stem_supported(C, K, R, S, x_dtype, out_dtype)) {
+        set_error("conv2d_nchw_split: unsupported configuration C=%d K=%d %dx%d", C, K, R, S);
+        return MV_E_UNSUPPORTED;
+    }
+    return stem_launch(x, w_hi, scale, shift, y, N, C, H, W, K, R, S, sh, sw, ph, pw, act, x_dtype, out_dtype, 0, 0, nullptr,
+                       (hipStream_t)stream, w_lo);
+}
+
+}  // extern "C"

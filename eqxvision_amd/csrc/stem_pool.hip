@@ -334,8 +334,8 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(WPE, WP
 }
 
 // the two entries this kernel is built for: ResNet (7x7 / 2, pad 3, pool pad 1) and AlexNet (11x11 / 4, pad 2, pool pad 0)
-int stem_pool_supported(int C, int K, int R, int S, int sh, int sw, int ph, int pw, int pk, int ps, int pp, int act,
-                        int x_dtype, int out_dtype, long long in_elems) {
+static int stem_pool_supported(int C, int K, int R, int S, int sh, int sw, int ph, int pw, int pk, int ps, int pp, int act,
+                               int x_dtype, int out_dtype, long long in_elems) {
     const bool resnet = R == 7 && sh == 2 && ph == 3 && pp == 1;
     const bool alexnet = R == 11 && sh == 4 && ph == 2 && pp == 0 && !get_flag("no_stem_pool11");
     return C == 3 && K == 64 && R == S && sh == sw && ph == pw && pk == 3 && ps == 2 && (resnet || alexnet) &&
@@ -377,8 +377,8 @@ static int stem_pool_go(StemPoolP p, int x_dtype, int blocks_per_cu, const char*
     return MV_OK;
 }
 
-int stem_pool_launch(const void* x, const void* w, const float* scale, const float* shift, void* y, int N, int H, int W,
-                     int R, int x_dtype, hipStream_t st) {
+static int stem_pool_launch(const void* x, const void* w, const float* scale, const float* shift, void* y, int N, int H, int W,
+                            int R, int x_dtype, hipStream_t st) {
     StemPoolP p;
     p.x = x; p.w = (const bf16_t*)w; p.scale = scale; p.shift = shift; p.y = (bf16_t*)y;
     p.N = N; p.H = H; p.W = W;
@@ -393,3 +393,31 @@ int stem_pool_launch(const void* x, const void* w, const float* scale, const flo
 }
 
 }  // namespace mv
+
+using namespace mv;
+
+extern "C" {
+
+int mv_stem_conv_pool_supported(int C, int K, int R, int S, int sh, int sw, int ph, int pw, int pool_k, int pool_s,
+                                int pool_p, int act, int x_dtype, int out_dtype, int64_t in_elems) {
+    return !get_flag("force_generic") && !get_flag("no_stem_pool") &&
+           stem_pool_supported(C, K, R, S, sh, sw, ph, pw, pool_k, pool_s, pool_p, act, x_dtype, out_dtype, in_elems);
+}
+
+int mv_stem_conv_pool_fwd(const void* x, const void* w, const float* scale, const float* shift, void* y, int N, int C,
+                          int H, int W, int K, int R, int S, int sh, int sw, int ph, int pw, int pool_k, int pool_s,
+                          int pool_p, int act, int x_dtype, int out_dtype, mv_stream_t stream) {
+    MV_CHECK_FUSED_ACT(act, "stem_conv_pool");
+    MV_CHECK_ARG(x && w && y, "stem_conv_pool: NULL pointer");
+    MV_CHECK_ARG(N > 0 && H > 0 && W > 0, "stem_conv_pool: non-positive dims");
+    if (!mv_stem_conv_pool_supported(C, K, R, S, sh, sw, ph, pw, pool_k, pool_s, pool_p, act, x_dtype, out_dtype,
+                                     (int64_t)N * C * H * W)) {
+        set_error("stem_conv_pool: unsupported configuration (ask mv_stem_conv_pool_supported first)");
+        return MV_E_UNSUPPORTED;
+    }
+    const int Ho = (H + 2 * ph - R) / sh + 1, Wo = (W + 2 * pw - S) / sw + 1;
+    MV_CHECK_ARG(Ho >= pool_k - pool_p && Wo >= pool_k - pool_p && Ho + 2 * pool_p >= pool_k && Wo + 2 * pool_p >= pool_k, "stem_conv_pool: image too small");
+    return stem_pool_launch(x, w, scale, shift, y, N, H, W, R, x_dtype, (hipStream_t)stream);
+}
+
+}  // extern "C"

@@ -312,7 +312,7 @@ static int stream_go(StreamP& p, int tiles_n, hipStream_t st) {
     return MV_OK;
 }
 
-int stream1x1_ln_supported(long long M, int C, int K, int x_dtype, int out_dtype) {
+static int stream1x1_ln_supported(long long M, int C, int K, int x_dtype, int out_dtype) {
     // K = 192 works (flag "ln_stream_192") but loses: only one 128-channel weight slab fits in LDS next to the epilogue patches,
     // so 5-6 blocks re-read AND re-normalise every row (measured 46 us vs 14 + 29.5 us for LayerNorm + Linear at 50 176 x 192 -> 576)
     const bool c_ok = C == 96 || (C == 192 && get_flag("ln_stream_192"));
@@ -321,8 +321,8 @@ int stream1x1_ln_supported(long long M, int C, int K, int x_dtype, int out_dtype
 }
 
 // y = act(w . n(x) + shift): rows normalised on the way in (LayerNorm with its affine folded into w / shift by the caller)
-int stream1x1_ln_launch(const void* x, const void* w, const float* shift, void* y, long long M, int C, int K, float eps, int act,
-                        int x_dtype, hipStream_t st) {
+static int stream1x1_ln_launch(const void* x, const void* w, const float* shift, void* y, long long M, int C, int K, float eps,
+                               int act, int x_dtype, hipStream_t st) {
     StreamP p;
     p.x = nullptr; p.xraw = x; p.eps = eps;
     p.w = (const bf16_t*)w; p.scale = nullptr; p.shift = shift; p.residual = nullptr; p.y = y;
@@ -402,3 +402,24 @@ int stream1x1_launch(const void* x, const void* w, const float* scale, const flo
 }
 
 }  // namespace mv
+
+using namespace mv;
+
+extern "C" {
+
+int mv_ln_linear_supported(int64_t M, int N, int K, int x_dtype, int out_dtype) {
+    return !get_flag("force_generic") && !get_flag("no_stream") && stream1x1_ln_supported(M, K, N, x_dtype, out_dtype);
+}
+
+int mv_ln_linear_fwd(const void* x, const void* w, const float* bias, void* y, int64_t M, int N, int K, float eps, int act,
+                     int x_dtype, int out_dtype, mv_stream_t stream) {
+    MV_CHECK_FUSED_ACT(act, "ln_linear");
+    MV_CHECK_ARG(x && w && y, "ln_linear: NULL pointer");
+    if (!mv_ln_linear_supported(M, N, K, x_dtype, out_dtype)) {
+        set_error("ln_linear: unsupported configuration M=%lld N=%d K=%d (ask mv_ln_linear_supported first)", (long long)M, N, K);
+        return MV_E_UNSUPPORTED;
+    }
+    return stream1x1_ln_launch(x, w, bias, y, M, K, N, eps, act, x_dtype, (hipStream_t)stream);
+}
+
+}  // extern "C"

@@ -14,6 +14,7 @@
 //     LDS once per block and re-used for all the windows the block walks.
 #include "mfma_common.h"
 #include "rng_common.h"
+#include "swin_geom.h"
 
 namespace mv {
 
@@ -299,3 +300,25 @@ int swin_mfma_launch(const void* qkv, const float* bias, void* out, int B, int H
 }
 
 }  // namespace mv
+
+using namespace mv;
+
+extern "C" {
+
+int mv_swin_window_attn_dropout_fwd(const void* qkv, const float* bias, void* out, const void* keys, float keep_prob, int B,
+                                    int Hf, int Wf, int C, int heads, int ws_h, int ws_w, int shift_h, int shift_w, int dtype,
+                                    mv_stream_t stream) {
+    MV_CHECK_ARG(qkv && bias && out && keys && B > 0 && Hf > 0 && Wf > 0 && C > 0 && heads > 0, "swin_attn_dropout: bad args");
+    WindowGeom g;
+    if (int rc = swin_check_geom("swin_attn_dropout", Hf, Wf, C, heads, ws_h, ws_w, shift_h, shift_w, g)) return rc;
+    MV_CHECK_ARG(keep_prob > 0.f && keep_prob <= 1.f, "swin_attn_dropout: keep_prob %g outside (0, 1]", (double)keep_prob);
+    if (!swin_mfma_supported(C, heads, ws_h, ws_w, dtype)) {
+        set_error("swin_attn_dropout: unsupported C=%d heads=%d window %dx%d dtype=%d (bf16, 32 channels per head, <= 64 tokens)", C,
+                  heads, ws_h, ws_w, dtype);
+        return MV_E_UNSUPPORTED;
+    }
+    return swin_mfma_launch(qkv, bias, out, B, Hf, Wf, C, heads, ws_h, ws_w, g.shh, g.shw, (const uint32_t*)keys, keep_prob,
+                            (hipStream_t)stream);
+}
+
+}  // extern "C"

@@ -71,8 +71,8 @@ __global__ __launch_bounds__(256) void swin_qk_rnorm_kernel(const T* __restrict_
         *(float4*)(dst + e) = make_float4(1.0f / sqrtf(acc[e]), 1.0f / sqrtf(acc[e + 1]), 1.0f / sqrtf(acc[e + 2]), 1.0f / sqrtf(acc[e + 3]));
 }
 
-int swin_qk_rnorm_launch(const void* qkv, float* rnorm, int B, int Hf, int Wf, int C, int ws_h, int ws_w, int shift_h, int shift_w,
-                         int dtype, hipStream_t st) {
+static int swin_qk_rnorm_launch(const void* qkv, float* rnorm, int B, int Hf, int Wf, int C, int ws_h, int ws_w, int shift_h,
+                                int shift_w, int dtype, hipStream_t st) {
     RnormP p;
     p.B = B; p.Hf = Hf; p.Wf = Wf; p.C = C; p.wsh = ws_h; p.wsw = ws_w; p.shh = shift_h; p.shw = shift_w;
     p.n = ws_h * ws_w;

@@ -11,6 +11,7 @@
 // Minimum slice: correctness first (one thread per output element, VALU); the matrix-core versions are future work.
 #include "common.h"
 #include "mfma_common.h"
+#include "swin_geom.h"
 
 namespace mv {
 
@@ -463,8 +464,8 @@ __global__ void adam_kernel(const float* __restrict__ g, float* __restrict__ m, 
 
 
 // Swin shifted-window attention backward (swin.py:123-250), one workgroup per (window, head, image), one thread per token.
-// qkv NHWC [B,Hf,Wf,3C] ([q|k|v][head][dh]); roll / partition / mask are the forward's index arithmetic (generic.hip:
-// swin_attn_generic_kernel).  With s = (q / sqrt(dh)) . k + bias + mask, p = softmax(s), o = p v:
+// qkv NHWC [B,Hf,Wf,3C] ([q|k|v][head][dh]); roll / partition / mask are the forward's index arithmetic (swin_geom.h, as
+// in attn_fallback.hip).  With s = (q / sqrt(dh)) . k + bias + mask, p = softmax(s), o = p v:
 //   g = p * (dp - sum_j dp p), dp = do . v^T;  dq = g k / sqrt(dh);  dk = g^T (q / sqrt(dh));  dv = p^T do;  dbias += g.
 // g is also written out per window ([B * windows][heads][n * n]) so that the bias gradient is a deterministic column sum.
 __global__ __launch_bounds__(64) void swin_attn_bwd_kernel(const float* __restrict__ qkv, const float* __restrict__ bias,
@@ -485,17 +486,12 @@ __global__ __launch_bounds__(64) void swin_attn_bwd_kernel(const float* __restri
     const int t = threadIdx.x;
     const float scale = rsqrtf((float)dh);
     const bool shifted = (shh + shw) > 0;
-    auto region = [&](int y, int x) {
-        const int rh = (y < Hf - wsh) ? 0 : (y < Hf - shh ? 1 : 2);
-        const int rw = (x < Wf - wsw) ? 0 : (x < Wf - shw ? 1 : 2);
-        return rh * 3 + rw;
-    };
+    const WindowGeom g = {Hf, Wf, wsh, wsw, shh, shw};
     long long pos = 0;
     int myreg = 0;
     if (t < n) {
-        const int ty = wy * wsh + t / wsw, tx = wx * wsw + t % wsw;          // rolled coordinates
-        myreg = region(ty, tx);
-        pos = ((long long)b * Hf + (ty + shh) % Hf) * Wf + (tx + shw) % Wf;
+        myreg = swin_tok_region(g, wy, wx, t);
+        pos = swin_tok_row(g, b, wy, wx, t);
         const float* r = qkv + pos * 3 * C + h * dh;
         for (int d = 0; d < dh; ++d) {
             q[t * dh + d] = r[d] * scale;

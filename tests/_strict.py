@@ -510,7 +510,7 @@ def emu_adaptive_avgpool(x, oh, ow, out, store_mode="rne", neighbour_count=False
 
 
 def wide_geometry(C):
-    """generic.hip, mv_adaptive_avgpool2d_nhwc_fwd: (cpb, pl, idle threads, channel blocks) of global_avgpool_wide_kernel."""
+    """pool.hip, mv_adaptive_avgpool2d_nhwc_fwd: (cpb, pl, idle threads, channel blocks) of global_avgpool_wide_kernel."""
     c8 = C // 8
     cpb = min(c8, 32)
     pl = 1024 // cpb
