@@ -21,6 +21,10 @@ reduction length: `ops_bound(ref, mag, n_ops, out) = n_ops 2^-23 mag + half_ulp_
 the kernel source next to each case.  The second half of this file holds the case data, the float64 references and a numpy/float32
 emulation of each kernel's contract (fp32 arithmetic in the kernel's order, then a round-to-nearest-even store); every emulation
 takes a switch for exactly one defect, which tests/test_strict_host.py turns on to prove that the instrument sees it.
+
+The last part does the same for the training backward kernels (csrc/train_bwd.hip; tests/test_strict_bwd_gpu.py, proofs in
+tests/test_strict_bwd_host.py): the conv shapes, float64 autograd references, and emulations of the input- and weight-gradient
+contracts, the column sum and the attention backward, again one defect switch each.
 """
 from __future__ import annotations
 
@@ -643,3 +647,422 @@ def bn_dz_coef64(s1, s2, s0, mean, var, scale, n, a, eps):
     A = -k * scale * s1 - B * (s0 / n)
     magA = np.abs(k * scale * s1) + (np.abs(B) + magB) * np.abs(s0 / n)
     return A, magA, B, magB
+
+
+# ================================================================================================ training backward kernels
+# Case data, float64 references and float32 emulations for tests/test_strict_bwd_gpu.py and tests/test_strict_bwd_host.py
+# (csrc/train_bwd.hip; every kernel there is fp32).
+def int_nz(rng, shape, lim):
+    """Integers in [-lim, lim] without 0, as float32 (a depthwise filter has one channel: a zero tap would be an unused index)."""
+    return (rng.integers(1, lim + 1, shape) * rng.choice(np.array([-1, 1]), shape)).astype(F32)
+
+
+def eighths(rng, shape):
+    """Multiples of 1/8 in [0, 1]: stand-ins for probabilities whose products with small integers are exact in fp32."""
+    return (rng.integers(0, 9, shape) / 8.0).astype(F32)
+
+
+def _pair(v):
+    return (int(v[0]), int(v[1])) if isinstance(v, (tuple, list)) else (int(v), int(v))
+
+
+class ConvGeom:
+    """One conv shape (N, H, W, C, K, (R, S), stride, pad, dil, groups); stride / pad / dil one int or an (h, w) pair."""
+
+    def __init__(self, N, H, W, C, K, RS, stride, pad, dil, groups):
+        self.N, self.H, self.W, self.C, self.K, self.groups = N, H, W, C, K, groups
+        (self.R, self.S), (self.sh, self.sw), (self.ph, self.pw), (self.dh, self.dw) = _pair(RS), _pair(stride), _pair(pad), _pair(dil)
+        self.Ho = (H + 2 * self.ph - self.dh * (self.R - 1) - 1) // self.sh + 1
+        self.Wo = (W + 2 * self.pw - self.dw * (self.S - 1) - 1) // self.sw + 1
+        self.Cg, self.Kg, self.P = C // groups, K // groups, N * self.Ho * self.Wo
+        self.out_elems = K * self.R * self.S * self.Cg
+        self.tag = f"{N}x{H}x{W}_C{C}_K{K}_{self.R}x{self.S}_s{self.sh}{self.sw}_p{self.ph}{self.pw}_d{self.dh}{self.dw}_g{groups}"
+
+    def args(self):
+        """The entries' argument tail: N, H, W, C, K, R, S, sh, sw, ph, pw, dh, dw, groups."""
+        return (self.N, self.H, self.W, self.C, self.K, self.R, self.S, self.sh, self.sw, self.ph, self.pw, self.dh, self.dw, self.groups)
+
+    def wgrad_split(self, offer_bytes=None):
+        """mv_conv2d_wgrad_nhwc_f32's arithmetic as its comment states it: tiles x position chunks ~ 4096 waves, at least 128
+        positions per chunk, at most 1024 chunks; (split the entry wants, split it runs with an offer of `offer_bytes`)."""
+        tiles = self.groups * -(-self.Kg // 32) * -(-self.Cg // 32) * self.R * self.S
+        want = 1 if tiles >= 2048 else -(-4096 // tiles)
+        want = min(want, (self.P + 127) // 128, 1024)
+        if want <= 1:
+            return want, 1
+        have = max((offer_bytes or 0) - 4096, 0)
+        fit = have // (self.out_elems * 4)
+        return want, (1 if fit < 2 else min(want, fit))
+
+
+# the issue's ten shapes; the eleventh is the one whose own split exceeds 2 (P = 396: four chunks), which none of the ten reaches
+CONV_BWD_SHAPES = [ConvGeom(*s) for s in [
+    (1, 9, 11, 40, 21, (1, 1), 1, 0, 1, 1),           # scalar-k loop, odd K, ragged second channel tile, M = 99 < 128
+    (2, 7, 9, 24, 12, (3, 3), 2, 1, 1, 1),            # float4 loop with K % 8 == 4 (P = 2 * 4 * 5 is even: odd P comes from 99 and 9)
+    (1, 8, 8, 16, 6, (3, 3), 1, 2, 2, 1),             # K % 4 == 2, dilation
+    (1, 9, 12, 8, 8, (1, 7), (2, 1), (0, 3), 1, 1),   # R != S, sh != sw, ph != pw; C = 8: the MFMA gate's edge
+    (1, 9, 12, 7, 8, (1, 7), (2, 1), (0, 3), 1, 1),   # C = 7: the VALU kernel serves it
+    (3, 5, 3, 16, 40, (3, 3), 1, 0, 1, 1),            # Wo = 1 (P = 9, odd), two k tiles, the second ragged
+    (2, 6, 4, 16, 8, (3, 3), 1, 0, 1, 1),             # Wo = 2
+    (2, 7, 7, 12, 12, (3, 3), 2, 1, 1, 12),           # depthwise
+    (2, 6, 6, 12, 20, (3, 3), 1, 1, 1, 4),            # Kg = 5, Cg = 3
+    (1, 12, 11, 72, 8, (3, 3), 1, 1, 1, 1),           # M = 132: two blocks, three channel tiles; split = 2
+    (3, 12, 11, 40, 21, (3, 3), 1, 1, 1, 1),          # P = 396: the entry wants split = 4 (the clamp cases)
+]]
+CONV_BWD_CLAMP = CONV_BWD_SHAPES[-1]
+
+
+def conv_bwd_data(g, kind, seed=60):
+    """(x NHWC, w KRSC, dy NHWK) float32: kind "int" -> integers in [-2, 2] (w and dy without zeros), "gauss" -> Gaussian, the
+    filter scaled by 1 / sqrt(fan-in)."""
+    rng = rng_of(seed + (0 if kind == "int" else 1))
+    xs, ws, ys = (g.N, g.H, g.W, g.C), (g.K, g.R, g.S, g.Cg), (g.N, g.Ho, g.Wo, g.K)
+    if kind == "int":
+        return int_tensor(rng, xs, 2), int_nz(rng, ws, 2), int_nz(rng, ys, 2)
+    return (rng.standard_normal(xs).astype(F32), (rng.standard_normal(ws) / np.sqrt(g.Cg * g.R * g.S)).astype(F32),
+            rng.standard_normal(ys).astype(F32))
+
+
+def conv_bwd64(x_nhwc, w_krsc, dy_nhwk, g):
+    """(dx NHWC, dw KRSC) of sum(conv2d(x, w) * dy): float64 torch.autograd of F.conv2d on double tensors."""
+    x = _t(x_nhwc).permute(0, 3, 1, 2).contiguous().requires_grad_(True)
+    w = _t(w_krsc).permute(0, 3, 1, 2).contiguous().requires_grad_(True)
+    y = torch.nn.functional.conv2d(x, w, None, (g.sh, g.sw), (g.ph, g.pw), (g.dh, g.dw), g.groups)
+    gx, gw = torch.autograd.grad(y, (x, w), _t(dy_nhwk).permute(0, 3, 1, 2).contiguous())
+    return gx.permute(0, 2, 3, 1).contiguous().numpy(), gw.permute(0, 2, 3, 1).contiguous().numpy()
+
+
+def conv_bwd_ref(x, w, dy, g):
+    """(dx, mag of dx, dw, mag of dw): the references and the same contractions on absolute values."""
+    dx, dw = conv_bwd64(x, w, dy, g)
+    mx, mw = conv_bwd64(np.abs(x), np.abs(w), np.abs(dy), g)
+    return dx, mx, dw, mw
+
+
+def conv_bwd_weights(x, w, dy, g):
+    """The (rows, reduction) matrices prove_exact looks at: per group the filters as (channel, (k, r, s)) for the input gradient;
+    dy as (k, position) and x as (channel, pixel) for the weight gradient."""
+    per_group = [w[i * g.Kg:(i + 1) * g.Kg].transpose(3, 0, 1, 2).reshape(g.Cg, -1) for i in range(g.groups)]
+    return per_group, [dy.reshape(-1, g.K).T, x.reshape(-1, g.C).T]
+
+
+def _mm32(a, b):
+    return np.asarray(a, F32) @ np.asarray(b, F32)
+
+
+def emu_conv_dgrad(dy, w, g, defect=None):
+    """The input-gradient contract in float32: dx[pos][c] = sum over the taps (r, s) whose stride divides of dy[out(pos, r, s)] . w[:, r, s, c]
+    (conv_dgrad_mfma_kernel; one fp32 matrix product per tap).  Defects, one each:
+      "drop_last_odd_k"   the scalar-k loop's last step is lost when K is odd (k = K - 1 sits alone in its pair)
+      "read_past_k"       the float4 loop keeps the upper half-wave's four k when K % 8 == 4: it reads dy[pos][K .. K + 3] -- the next
+                          position's first four values, the sentinel behind the last -- against four filters past the end (sentinel)
+      "stride_any"        a tap is accepted where the stride does not divide (ho = th / sh without the remainder test)"""
+    dy, w = np.asarray(dy, F32), np.asarray(w, F32)
+    K = g.K
+    dyf = dy.reshape(-1, K)
+    if defect == "drop_last_odd_k" and K % 2:
+        dyf = dyf.copy()
+        dyf[:, K - 1] = 0
+    if defect == "read_past_k" and K % 8 == 4:
+        assert g.groups == 1
+        flat = np.concatenate([dyf.reshape(-1), np.full(4, SENTINEL, F32)])
+        idx = np.arange(dyf.shape[0])[:, None] * K + np.arange(K + 4)[None, :]
+        dyf = flat[idx]
+        w = np.concatenate([w, np.full((4,) + w.shape[1:], SENTINEL, F32)])
+        K = K + 4
+    Kg = K // g.groups
+    dx = np.zeros((g.N * g.H * g.W, g.C), F32)
+    m = np.arange(g.N * g.H * g.W)
+    wi, hi, n = m % g.W, (m // g.W) % g.H, m // (g.W * g.H)
+    for r in range(g.R):
+        th = hi + g.ph - r * g.dh
+        ho = np.floor_divide(th, g.sh)
+        hok = (th >= 0) & (ho < g.Ho) & ((th % g.sh == 0) | (defect == "stride_any"))
+        for s in range(g.S):
+            tw = wi + g.pw - s * g.dw
+            wo = np.floor_divide(tw, g.sw)
+            ok = hok & (tw >= 0) & (wo < g.Wo) & ((tw % g.sw == 0) | (defect == "stride_any"))
+            rows = dyf[np.where(ok, (n * g.Ho + ho) * g.Wo + wo, 0)] * ok[:, None].astype(F32)
+            for gi in range(g.groups):
+                dx[:, gi * g.Cg:(gi + 1) * g.Cg] += _mm32(rows[:, gi * Kg:(gi + 1) * Kg], w[gi * Kg:(gi + 1) * Kg, r, s, :])
+    return dx.reshape(g.N, g.H, g.W, g.C)
+
+
+def emu_conv_wgrad(x, dy, g, split=1, defect=None):
+    """The weight-gradient contract in float32 (conv_wgrad_mfma_kernel + sum_parts_kernel): the positions p = (n, ho, wo) are cut
+    into `split` chunks of an even length; each half-wave walks its chunk two positions at a time, carrying (n, ho, wo) along; the
+    chunks' partial filters are added in chunk order.  Defects, one each:
+      "drop_last_odd_p"   the last position of an odd P (the lower half-wave alone in its pair) is lost
+      "wrap_once"         the walk's `while (wo >= Wo)` is an `if`: at Wo = 1 a step of two wraps once only and wo stays out of range
+      "chunk_twice"       a chunk also takes the first position of the next one"""
+    x, dy = np.asarray(x, F32), np.asarray(dy, F32)
+    P = g.P
+    chunk = (-(-P // split) + 1) & ~1
+    dyf = dy.reshape(P, g.K)
+    total = np.zeros((g.K, g.R, g.S, g.Cg), F32)
+    for ci in range(split):
+        p0, p1 = ci * chunk, min(ci * chunk + chunk, P)
+        ps, ns, hos, wos = [], [], [], []
+        for fh in (0, 1):
+            p = p0 + fh
+            n, rem = divmod(p, g.Ho * g.Wo)
+            ho, wo = divmod(rem, g.Wo)
+            last = p1 + (1 if defect == "chunk_twice" and p1 < P else 0)
+            while p - fh < last:
+                if p < last and not (defect == "drop_last_odd_p" and P % 2 and p == P - 1):
+                    ps.append(p), ns.append(n), hos.append(ho), wos.append(wo)
+                p += 2
+                wo += 2
+                while wo >= g.Wo:
+                    wo -= g.Wo
+                    ho += 1
+                    if ho >= g.Ho:
+                        ho, n = 0, n + 1
+                    if defect == "wrap_once":
+                        break
+        part = np.zeros_like(total)
+        if ps:
+            ps, ns, hos, wos = (np.asarray(v) for v in (ps, ns, hos, wos))
+            for r in range(g.R):
+                hi = hos * g.sh - g.ph + r * g.dh
+                for s in range(g.S):
+                    wi = wos * g.sw - g.pw + s * g.dw
+                    ok = (hi >= 0) & (hi < g.H) & (wi >= 0) & (wi < g.W) & (ns < g.N)
+                    xr = x[np.where(ok, ns, 0), np.where(ok, hi, 0), np.where(ok, wi, 0)] * ok[:, None].astype(F32)
+                    for gi in range(g.groups):
+                        part[gi * g.Kg:(gi + 1) * g.Kg, r, s, :] = _mm32(dyf[ps][:, gi * g.Kg:(gi + 1) * g.Kg].T, xr[:, gi * g.Cg:(gi + 1) * g.Cg])
+        total = total + part
+    return total
+
+
+def colsum_ref(a, b):
+    a = np.asarray(a, F64)
+    bb = 1.0 if b is None else np.asarray(b, F64)
+    return (a * bb).sum(0), (np.abs(a) * np.abs(bb)).sum(0)
+
+
+def colsum_split(M):
+    """mv_colsum_f32's arithmetic: (parts, rows per part) with scratch on offer; one part below 512 rows."""
+    split = min((M + 255) // 256, 512) if M >= 512 else 1
+    return split, -(-M // split)
+
+
+def colsum_n_ops(M, split):
+    """Roundings on the longest path of one column sum, counted from colsum_kernel / colsum_part_kernel / sum_parts_kernel: the
+    product, ceil(rows / 4) adds in a row group, two adds across the four groups, and `split` adds over the parts."""
+    rows = -(-M // split)
+    return 1 + -(-rows // 4) + 2 + (split if split > 1 else 0)
+
+
+def emu_colsum(a, b=None, split=1, drop_tail_rows=False):
+    """colsum_kernel (split = 1) / colsum_part_kernel + sum_parts_kernel in float32: four row groups (m = rg, rg + 4, ...) summed in
+    order, (g0 + g1) + (g2 + g3), the parts added in order.  drop_tail_rows: the rows m >= 4 (M / 4) of a part are lost (a loop over
+    whole groups of four)."""
+    a = np.asarray(a, F32)
+    v = a if b is None else a * np.asarray(b, F32)
+    M, C = v.shape
+    chunk = -(-M // split)
+    out = np.zeros(C, F32)
+    for ci in range(split):
+        blk = v[ci * chunk:min((ci + 1) * chunk, M)]
+        n4 = blk.shape[0] // 4
+        acc = np.zeros((4, C), F32)
+        for i in range(n4):
+            acc += blk[4 * i:4 * i + 4]
+        tail = blk[4 * n4:]
+        if tail.shape[0] and not drop_tail_rows:
+            acc[:tail.shape[0]] += tail
+        part = (acc[0] + acc[1]) + (acc[2] + acc[3])
+        out = part if split == 1 else out + part
+    return out
+
+
+def softmax_bwd_ref(p, dp, scale):
+    """ds = scale p (dp - sum_j dp p) in float64 and its magnitude |scale p| (|dp| + sum_j |dp p|)."""
+    p, dp = np.asarray(p, F64), np.asarray(dp, F64)
+    ref = scale * p * (dp - (p * dp).sum(-1, keepdims=True))
+    mag = np.abs(scale * p) * (np.abs(dp) + np.abs(p * dp).sum(-1, keepdims=True))
+    return ref, mag
+
+
+def mha_bwd_data(B, N, H, dh, kind, seed=70):
+    """(qkv [B, N, 3 D], probs [B, H, N, N], dout [B, N, D]) float32.  "int": integers in [-2, 2] and probabilities that are
+    multiples of 1/8, independent of qkv (the kernel reads them from a buffer); "gauss": Gaussian, rows of probs a float32 softmax."""
+    rng = rng_of(seed + N + (0 if kind == "int" else 1))
+    D = H * dh
+    if kind == "int":
+        return int_tensor(rng, (B, N, 3 * D), 2), eighths(rng, (B, H, N, N)), int_tensor(rng, (B, N, D), 2)
+    s = rng.standard_normal((B, H, N, N))
+    e = np.exp(s - s.max(-1, keepdims=True))
+    return rng.standard_normal((B, N, 3 * D)).astype(F32), (e / e.sum(-1, keepdims=True)).astype(F32), rng.standard_normal((B, N, D)).astype(F32)
+
+
+def _heads(a, H, dh):
+    """[B, N, H dh] -> [B, H, N, dh]"""
+    return a.reshape(a.shape[0], a.shape[1], H, dh).transpose(0, 2, 1, 3)
+
+
+def mha_bwd_ref(qkv, probs, dout, scale, H, dh):
+    """The four float64 contractions of train_bwd.hip's attention-backward comment: dP = dO V^T, dS = scale P (dP - sum_j P dP),
+    dQ = dS K, dK = dS^T Q, dV = P^T dO; with them the magnitudes (the contractions on absolute values, dS's own magnitude carried
+    through) and the operation counts of S.ops_bound, counted from mha_bwd_q_kernel / mha_bwd_kv_kernel:
+      dP      dh fma
+      t       its lane's ceil(N / 64) fma and 6 shuffle adds, on top of dP's
+      dS      the difference and two products on top: n_ds = dh + ceil(N / 64) + 9
+      dQ, dK  N fma on the stored dS: n_ds + N;   dV  N fma.
+    Returns {"ds": (ref, mag, n_ops), "dqkv": (ref, mag, n_ops)}."""
+    qkv, P, dout = np.asarray(qkv, F64), np.asarray(probs, F64), np.asarray(dout, F64)
+    B, N, D3 = qkv.shape
+    D = D3 // 3
+    q, k, v = (_heads(qkv[:, :, i * D:(i + 1) * D], H, dh) for i in range(3))
+    go = _heads(dout, H, dh)
+    dP = go @ v.transpose(0, 1, 3, 2)
+    mdP = np.abs(go) @ np.abs(v).transpose(0, 1, 3, 2)
+    t = (P * dP).sum(-1, keepdims=True)
+    mt = (P * mdP).sum(-1, keepdims=True)
+    dS = scale * P * (dP - t)
+    mdS = np.abs(scale * P) * (mdP + mt)
+    n_ds = dh + -(-N // 64) + 9
+    outs = [(dS @ k, mdS @ np.abs(k), n_ds + N), (dS.transpose(0, 1, 3, 2) @ q, mdS.transpose(0, 1, 3, 2) @ np.abs(q), n_ds + N),
+            (P.transpose(0, 1, 3, 2) @ go, P.transpose(0, 1, 3, 2) @ np.abs(go), N)]
+
+    def rows(a):
+        return a.transpose(0, 2, 1, 3).reshape(B, N, D)
+    ref = np.concatenate([rows(o[0]) for o in outs], -1)
+    mag = np.concatenate([rows(o[1]) for o in outs], -1)
+    n_ops = np.concatenate([np.full((B, N, D), float(o[2])) for o in outs], -1)
+    return {"ds": (dS, mdS, float(n_ds)), "dqkv": (ref, mag, n_ops)}
+
+
+def emu_mha_bwd(qkv, probs, dout, scale, H, dh, drop_j_tail=False):
+    """mha_bwd_q_kernel + mha_bwd_kv_kernel in float32 -> (ds, dqkv).  drop_j_tail: the lane loops `for (j = lane; j < N; j += 64)`
+    make one trip only: the keys j >= 64 miss from the row sum, their dS is never written (the sentinel stays) and dQ does not see
+    them."""
+    qkv, P, dout = np.asarray(qkv, F32), np.asarray(probs, F32), np.asarray(dout, F32)
+    B, N, D3 = qkv.shape
+    D = D3 // 3
+    q, k, v = (_heads(qkv[:, :, i * D:(i + 1) * D], H, dh) for i in range(3))
+    go = _heads(dout, H, dh)
+    J = min(N, 64) if drop_j_tail else N
+    dP = go @ v.transpose(0, 1, 3, 2)
+    t = (P[..., :J] * dP[..., :J]).sum(-1, keepdims=True, dtype=F32)
+    ds = np.full(P.shape, SENTINEL, F32)
+    ds[..., :J] = F32(scale) * P[..., :J] * (dP[..., :J] - t)
+    dq = ds[..., :J] @ k[:, :, :J]
+    dk = ds.transpose(0, 1, 3, 2) @ q
+    dv = P.transpose(0, 1, 3, 2) @ go
+
+    def rows(a):
+        return a.transpose(0, 2, 1, 3).reshape(B, N, D)
+    return ds, np.concatenate([rows(dq), rows(dk), rows(dv)], -1).astype(F32)
+
+
+def maxpool_bwd64(x, dy, k, s, p):
+    """float64 autograd of max_pool2d: dx NHWC for x NHWC, dy NHWC (no ties in x: the gradient is defined)."""
+    xt = _t(x).permute(0, 3, 1, 2).contiguous().requires_grad_(True)
+    y = torch.nn.functional.max_pool2d(xt, k, s, p)
+    (gx,) = torch.autograd.grad(y, (xt,), _t(dy).permute(0, 3, 1, 2).contiguous())
+    return gx.permute(0, 2, 3, 1).contiguous().numpy()
+
+
+def distinct_ints(rng, shape):
+    """x (N, H, W, C): per channel a random permutation of 0 .. N H W - 1, centred: no two values of a channel are equal."""
+    N, H, W, C = shape
+    n = N * H * W
+    x = np.stack([rng.permutation(n) for _ in range(C)], -1).astype(F32) - F32(n // 2)
+    return x.reshape(N, H, W, C)
+
+
+def patch_merge_bwd_ref(dy, H, W):
+    """The adjoint of mv_patch_merge_gather_nhwc, whose blocks are (0::2, 0::2) | (1::2, 0::2) | (0::2, 1::2) | (1::2, 1::2) of the
+    map padded with zeros to even sizes: dx[b, hi, wi, c] = dy[b, hi / 2, wi / 2, ((hi & 1) + 2 (wi & 1)) C + c]; what dy holds for
+    the padded taps reaches no input element."""
+    dy = np.asarray(dy, F64)
+    B, Ho, Wo, C4 = dy.shape
+    C = C4 // 4
+    full = np.zeros((B, 2 * Ho, 2 * Wo, C))
+    full[:, 0::2, 0::2], full[:, 1::2, 0::2] = dy[..., 0:C], dy[..., C:2 * C]
+    full[:, 0::2, 1::2], full[:, 1::2, 1::2] = dy[..., 2 * C:3 * C], dy[..., 3 * C:]
+    return full[:, :H, :W]
+
+
+def act_grad64(x, act):
+    """d act64 / dx in float64.  At the corners of the piecewise functions the value act_bwd_kernel's comparisons choose:
+      relu          v > 0 ? 1 : 0                      -> 0 at 0 (the left derivative)
+      hard_sigmoid  -3 < v < 3 ? 1/6 : 0               -> 0 at -3 and at 3 (the outer side)
+      hard_swish    v <= -3 ? 0 : v >= 3 ? 1 : (2 v + 3) / 6  -> 0 at -3 (left; the right derivative is -1/2), 1 at 3 (right; the left
+                    derivative is 3/2)"""
+    x = np.asarray(x, F64)
+    if act in (None, "none"):
+        return np.ones_like(x)
+    if act == "relu":
+        return (x > 0).astype(F64)
+    if act == "hard_sigmoid":
+        return np.where((x > -3.0) & (x < 3.0), 1.0 / 6.0, 0.0)
+    if act == "hard_swish":
+        return np.where(x <= -3.0, 0.0, np.where(x >= 3.0, 1.0, (2.0 * x + 3.0) / 6.0))
+    sg = 1.0 / (1.0 + np.exp(-x))
+    if act == "sigmoid":
+        return sg * (1.0 - sg)
+    if act == "silu":
+        return sg * (1.0 + x * (1.0 - sg))
+    if act == "gelu_tanh":                               # y = x s(2 u): y' = s + x s (1 - s) 2 u'
+        c = np.sqrt(2.0 / np.pi)
+        u = c * (x + 0.044715 * x ** 3)
+        s2 = 1.0 / (1.0 + np.exp(-2.0 * u))
+        return s2 + x * s2 * (1.0 - s2) * 2.0 * c * (1.0 + 3.0 * 0.044715 * x * x)
+    raise ValueError(act)
+
+
+def layernorm_bwd64(x, gamma, dy, eps):
+    """(dx, dy xhat) of y = xhat gamma + beta in float64: dx = rstd (g - mean(g) - xhat mean(g xhat)), g = gamma dy."""
+    x, dy = np.asarray(x, F64), np.asarray(dy, F64)
+    mean = x.mean(-1, keepdims=True)
+    rstd = 1.0 / np.sqrt(((x - mean) ** 2).mean(-1, keepdims=True) + eps)
+    xh = (x - mean) * rstd
+    g = dy * (1.0 if gamma is None else np.asarray(gamma, F64))
+    return rstd * (g - g.mean(-1, keepdims=True) - xh * (g * xh).mean(-1, keepdims=True)), dy * xh
+
+
+def xent64(logits, target):
+    """optax.softmax_cross_entropy(logits, target) per row, its mean, and the mean's gradient, in float64; the rows of `target` need
+    not sum to 1: loss_b = ts_b lse_b - sum_k t l, dlogits = (ts softmax - t) / B."""
+    l, t = np.asarray(logits, F64), np.asarray(target, F64)
+    mx = l.max(-1, keepdims=True)
+    lse = mx + np.log(np.exp(l - mx).sum(-1, keepdims=True))
+    ts = t.sum(-1, keepdims=True)
+    rows = (ts * lse - (t * l).sum(-1, keepdims=True))[:, 0]
+    return rows, rows.mean(), (ts * np.exp(l - lse) - t) / l.shape[0]
+
+
+def swin_bwd64(qkv, bias, dout, heads, ws, shift):
+    """float64 autograd of the shifted-window attention core (tests/_cases.py: swin_bwd_case's `core`) for a rectangular map and
+    window: roll, partition, q / sqrt(dh) . k + bias, the -100 mask between regions, softmax, reverse.  The shift of an axis whose
+    window covers the map is dropped.  Returns (dqkv [B, Hf, Wf, 3 C], g [B nW, heads, n, n] = the gradient of the logits)."""
+    B, Hf, Wf, C3 = qkv.shape
+    C, (wh, ww) = C3 // 3, ws
+    sh = [0 if wh >= Hf else shift[0], 0 if ww >= Wf else shift[1]]
+    n, dh, nW = wh * ww, C // heads, (Hf // wh) * (Wf // ww)
+    t = _t(qkv).requires_grad_(True)
+    x = torch.roll(t, (-sh[0], -sh[1]), (1, 2)) if sum(sh) > 0 else t
+    x = x.view(B, Hf // wh, wh, Wf // ww, ww, 3 * C).permute(0, 1, 3, 2, 4, 5).reshape(B * nW, n, 3, heads, dh).permute(2, 0, 3, 1, 4)
+    q, k, v = x[0] * dh ** -0.5, x[1], x[2]
+    attn = q @ k.transpose(-2, -1) + _t(bias)[None]
+    if sum(sh) > 0:
+        m = torch.zeros((Hf, Wf), dtype=torch.float64)
+        c = 0
+        for hh in ((0, -wh), (-wh, -sh[0]), (-sh[0], None)):
+            for wl in ((0, -ww), (-ww, -sh[1]), (-sh[1], None)):
+                m[hh[0]:hh[1], wl[0]:wl[1]] = c
+                c += 1
+        m = m.view(Hf // wh, wh, Wf // ww, ww).permute(0, 2, 1, 3).reshape(nW, n)
+        m = m.unsqueeze(1) - m.unsqueeze(2)
+        m = m.masked_fill(m != 0, -100.0)
+        attn = (attn.view(B, nW, heads, n, n) + m[None, :, None]).view(-1, heads, n, n)
+    attn.retain_grad()
+    y = (attn.softmax(-1) @ v).transpose(1, 2).reshape(B * nW, n, C)
+    y = y.view(B, Hf // wh, Wf // ww, wh, ww, C).permute(0, 1, 3, 2, 4, 5).reshape(B, Hf, Wf, C)
+    if sum(sh) > 0:
+        y = torch.roll(y, (sh[0], sh[1]), (1, 2))
+    y.backward(_t(dout))
+    return t.grad.numpy(), attn.grad.numpy()

@@ -14,8 +14,11 @@ Bound instrument (`S.ops_bound`, n_ops counted from the kernel source next to ea
 and >= 4096 reference elements have |ref| >= 2^-6, decided from the reference): the six activations, add, channel scale, channel
 affine with and without residual, the adaptive / global / plain average pools, resize at ragged ratios, and the fp32 backward
 kernels mv_channel_scale_bwd_f32, mv_avgpool_global_bwd_nhwc_f32, mv_bn_dgamma_f32, mv_bn_train_dz_coef_f32.
-Still under `_cases._cmp` only: mv_se_scale_fwd, the moments kernels, mv_maxpool2d_bwd_nhwc_f32, mv_act_bwd_f32, mv_colsum_f32, the
-LayerNorm / softmax / attention and dropout / PRNG kernels.  mv_maxpool2d_out_nhwc_fwd is exact in test_squeezenet_gpu.py.
+Still under `_cases._cmp` only: mv_se_scale_fwd, the moments kernels, the forward LayerNorm kernels and the dropout / PRNG kernels.
+mv_maxpool2d_out_nhwc_fwd is exact in test_squeezenet_gpu.py.  The training backward kernels (conv dgrad / wgrad,
+mv_maxpool2d_bwd_nhwc_f32, mv_colsum_f32, the softmax / attention backward, the gathers' adjoints: exact and bounded;
+mv_act_bwd_f32, the LayerNorm backward, the cross-entropy, the Swin window backward: float64 reference at edge shapes) are in
+test_strict_bwd_gpu.py, the forward attention kernels in test_strict_attn_gpu.py.
 
 Worst fp32-output ratios |got - ref| / bound of the activations that use v_exp_f32 / v_rcp_f32 (bound: S.act_n_ops, which rests on
 the ISA's stated 1-ulp accuracy of both), measured on an MI355X, kernels eltwise_x8 / eltwise:
