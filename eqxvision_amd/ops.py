@@ -64,11 +64,53 @@ def _bn_training(bn) -> bool:
     return bn is not None and not bn.inference
 
 
-def _bn_id(bn):
-    """Cache-key part for weights prepared WITH a BatchNorm folded in: identity + the version of its running statistics (the
-    StateIndex is shared by every copy of the module, e.g. tree_inference's; a training-mode update bumps it, so an inference
-    call afterwards refolds)."""
-    return None if bn is None else (id(bn), bn.state_index.version)
+def _prepared(mod, tag, deps, build):
+    """The operands `build()` prepares for `mod`, made once and kept in the module's cache under `tag` (a hashable: the static variant --
+    layout, dtype, form).  `deps`: the foreign objects the operands are made from -- parameter leaves, sibling modules, BatchNorms
+    (None where absent).  The entry holds them, and a later call is a hit only if it passes the very same objects (`is`; an id()
+    alone could be a recycled one: tree_at shares untouched sub-modules between trees); another set of objects under the same tag
+    gets an entry of its own.  A BatchNorm among them also has to be at the version of its running statistics the operands were
+    folded with (the StateIndex is shared by every copy of the module, e.g. tree_inference's; a training-mode update bumps it):
+    otherwise the entry is rebuilt in place, so the stale device tensors go."""
+    entries = mod._cache().setdefault(tag, [])
+    vers = [d.state_index.version for d in deps if hasattr(d, "state_index")]
+    for e in entries:
+        if len(e[0]) == len(deps) and all(a is b for a, b in zip(e[0], deps)):
+            if e[1] != vers:
+                e[1], e[2] = vers, build()
+            return e[2]
+    entries.append([tuple(deps), vers, build()])
+    return entries[-1][2]
+
+
+def _bias(m) -> Optional[np.ndarray]:
+    """A module's bias as a flat fp32 vector, None where it has none."""
+    return None if m.bias is None else np.asarray(m.bias, np.float32).reshape(-1)
+
+
+def _dev_bias(m) -> Optional[torch.Tensor]:
+    b = _bias(m)
+    return None if b is None else _dev(b, torch.float32)
+
+
+def _conv_fold(conv, bn):
+    """fp32 (scale, shift) of a convolution's bias + BatchNorm(inference) epilogue; None for a part there is nothing to apply for."""
+    bias = _bias(conv)
+    if bn is None:
+        return None, bias
+    scale, shift = bn_fold(bn)
+    return scale, shift if bias is None else shift + bias * scale
+
+
+def _ln_fold(lin, ln, wide: bool = False):
+    """A LayerNorm's affine folded into the Linear behind it, fp32: (W . diag(gamma), b + W . beta); `wide`: b + W . beta is formed
+    in float64 and rounded once."""
+    w = np.asarray(lin.weight, np.float32)
+    g, beta = np.asarray(ln.weight, np.float32).reshape(-1), np.asarray(ln.bias, np.float32).reshape(-1)
+    b = np.zeros(w.shape[0], np.float32) if lin.bias is None else _bias(lin)
+    if wide:
+        return w * g[None, :], (b.astype(np.float64) + w.astype(np.float64) @ beta.astype(np.float64)).astype(np.float32)
+    return w * g[None, :], b + w @ beta
 
 
 def bn_train_update(bn, y: Act):
@@ -133,7 +175,7 @@ def bn_train_update(bn, y: Act):
     # normalised with (running' = a * batch + (1 - a) * running), the row count of the data-parallel batch and whether the column
     # sums have to be summed over ranks
     sidx._last_update = dict(a=1.0 if first else 1.0 - float(bn.momentum), rows=float(rows), cnt=cnt, reduce=reduce_ranks)
-    sidx.device_updated(run)               # bumps the version: every fold prepared with the old statistics is stale (_bn_id)
+    sidx.device_updated(run)               # bumps the version: every fold prepared with the old statistics is stale (_prepared)
     on_replay(lambda s=sidx, r=run: s.device_updated(r))     # ... and again after every replay of a recorded step
     return scale, shift
 
@@ -152,69 +194,37 @@ def _bn_affine(y: Act, scale: torch.Tensor, shift: torch.Tensor, act=None, resid
 
 
 def prep_conv(conv, bn, layout: str, dtype: str):
-    key = ("conv", layout, dtype, _bn_id(bn))
-    cache = conv._cache()
-    hit = cache.get(key)
-    if hit is not None:
-        return hit
-    w = np.asarray(conv.weight, np.float32)                      # (O, I/g, kh, kw)
-    if layout == "krsc":
-        w = np.ascontiguousarray(w.transpose(0, 2, 3, 1))
-    bias = None if conv.bias is None else np.asarray(conv.bias, np.float32).reshape(-1)
-    scale = shift = None
-    if bn is not None:
-        scale, shift = bn_fold(bn)
-        if bias is not None:
-            shift = shift + bias * scale
-    elif bias is not None:
-        shift = bias
-    out = (_dev(w, TORCH_DT[dtype]),
-           None if scale is None else _dev(scale, torch.float32),
-           None if shift is None else _dev(shift, torch.float32))
-    cache[key] = out
-    return out
+    def build():
+        w = np.asarray(conv.weight, np.float32)                      # (O, I/g, kh, kw)
+        if layout == "krsc":
+            w = np.ascontiguousarray(w.transpose(0, 2, 3, 1))
+        scale, shift = _conv_fold(conv, bn)
+        return (_dev(w, TORCH_DT[dtype]),
+                None if scale is None else _dev(scale, torch.float32),
+                None if shift is None else _dev(shift, torch.float32))
+    return _prepared(conv, ("conv", layout, dtype), (bn,), build)
 
 
 def prep_conv_grouped64(conv, bn):
     """Grouped filters (O, I/g, kh, kw) expanded to the per-tile input windows: [O][kh][kw][win] (the layout
     mv_conv2d_nhwc_grouped64_fwd documents; block-diagonal 64 x 64 tiles when the group width divides 64), bf16; BN folded to
     fp32 scale / shift as in prep_conv."""
-    key = ("conv_g64", _bn_id(bn))
-    cache = conv._cache()
-    hit = cache.get(key)
-    if hit is not None:
-        return hit
-    w = np.asarray(conv.weight, np.float32)                      # (O, Cg, kh, kw)
-    O_, cg, kh, kw = w.shape
-    win = int(_lib.load().mv_conv2d_grouped64_window(O_, conv.groups))
-    w64 = np.zeros((O_, kh, kw, win), np.float32)
-    for k in range(O_):
-        off = (k // cg) * cg - ((k // 64 * 64) // cg) * cg       # my group's first channel inside my tile's window
-        w64[k, :, :, off:off + cg] = w[k].transpose(1, 2, 0)
-    bias = None if conv.bias is None else np.asarray(conv.bias, np.float32).reshape(-1)
-    scale = shift = None
-    if bn is not None:
-        scale, shift = bn_fold(bn)
-        if bias is not None:
-            shift = shift + bias * scale
-    elif bias is not None:
-        shift = bias
-    hit = (_dev(w64, torch.bfloat16), None if scale is None else _dev(scale, torch.float32),
-           None if shift is None else _dev(shift, torch.float32))
-    cache[key] = hit
-    return hit
+    def build():
+        w = np.asarray(conv.weight, np.float32)                      # (O, Cg, kh, kw)
+        O_, cg, kh, kw = w.shape
+        win = int(_lib.load().mv_conv2d_grouped64_window(O_, conv.groups))
+        w64 = np.zeros((O_, kh, kw, win), np.float32)
+        for k in range(O_):
+            off = (k // cg) * cg - ((k // 64 * 64) // cg) * cg       # my group's first channel inside my tile's window
+            w64[k, :, :, off:off + cg] = w[k].transpose(1, 2, 0)
+        scale, shift = _conv_fold(conv, bn)
+        return (_dev(w64, torch.bfloat16), None if scale is None else _dev(scale, torch.float32),
+                None if shift is None else _dev(shift, torch.float32))
+    return _prepared(conv, "conv_g64", (bn,), build)
 
 
 def prep_linear(lin, dtype: str):
-    key = ("lin", dtype)
-    cache = lin._cache()
-    hit = cache.get(key)
-    if hit is not None:
-        return hit
-    w = _dev(np.asarray(lin.weight, np.float32), TORCH_DT[dtype])
-    b = None if lin.bias is None else _dev(np.asarray(lin.bias, np.float32).reshape(-1), torch.float32)
-    cache[key] = (w, b)
-    return w, b
+    return _prepared(lin, ("lin", dtype), (), lambda: (_dev(np.asarray(lin.weight, np.float32), TORCH_DT[dtype]), _dev_bias(lin)))
 
 
 def _bf16_split(w: np.ndarray):
@@ -227,40 +237,26 @@ def _bf16_split(w: np.ndarray):
 
 def prep_linear_split(lin):
     """[N][2K] = [hi row | lo row] bf16 + fp32 bias (cached)."""
-    cache = lin._cache()
-    hit = cache.get("lin_split")
-    if hit is None:
+    def build():
         hi, lo = _bf16_split(np.asarray(lin.weight, np.float32))
-        w = torch.cat([hi, lo], dim=1).contiguous().to(device())
-        b = None if lin.bias is None else _dev(np.asarray(lin.bias, np.float32).reshape(-1), torch.float32)
-        hit = (w, b)
-        cache["lin_split"] = hit
-    return hit
+        return torch.cat([hi, lo], dim=1).contiguous().to(device()), _dev_bias(lin)
+    return _prepared(lin, "lin_split", (), build)
 
 
 def prep_conv_split(conv):
     """OIHW weights as (hi, lo) bf16 + fp32 bias (cached); no BatchNorm on these call sites."""
-    cache = conv._cache()
-    hit = cache.get("conv_split")
-    if hit is None:
+    def build():
         hi, lo = _bf16_split(np.asarray(conv.weight, np.float32))
-        b = None if conv.bias is None else _dev(np.asarray(conv.bias, np.float32).reshape(-1), torch.float32)
-        hit = (hi.to(device()), lo.to(device()), b)
-        cache["conv_split"] = hit
-    return hit
+        return hi.to(device()), lo.to(device()), _dev_bias(conv)
+    return _prepared(conv, "conv_split", (), build)
 
 
 def prep_f32(mod, name: str, arr) -> Optional[torch.Tensor]:
     if arr is None:
         return None
-    cache = mod._cache()
-    key = ("f32", name)
-    hit = cache.get(key)
-    if hit is None:
-        from ._module import DevArray
-        hit = arr.dev.reshape(-1) if isinstance(arr, DevArray) else _dev(np.asarray(arr, np.float32), torch.float32)
-        cache[key] = hit
-    return hit
+    from ._module import DevArray
+    return _prepared(mod, ("f32", name), (),
+                     lambda: arr.dev.reshape(-1) if isinstance(arr, DevArray) else _dev(np.asarray(arr, np.float32), torch.float32))
 
 
 # ------------------------------------------------------------------ layout plumbing
@@ -371,13 +367,7 @@ def conv2d(x: Act, conv, bn=None, act=None, residual: Optional[Act] = None) -> A
 
     if conv.groups > 1 and dt == "bf16" and residual is None and \
             _lib.load().mv_dwconv2d_supported(C, K, conv.groups, kh, kw, _lib.BF16, _lib.BF16):
-        cache = conv._cache()
-        hit = cache.get(("dw", _bn_id(bn)))
-        if hit is None:
-            _, scale, shift = prep_conv(conv, bn, "oihw", dt)
-            wr = np.ascontiguousarray(np.asarray(conv.weight, np.float32)[:, 0].transpose(1, 2, 0))     # (C,1,R,S) -> [R][S][C]
-            hit = (_dev(wr, torch.bfloat16), scale, shift)
-            cache[("dw", _bn_id(bn))] = hit
+        hit = prep_dw(conv, bn)
         y = empty((B, Ho, Wo, K), torch.bfloat16)
         _lib.call("mv_dwconv2d_nhwc_fwd", _ptr(x.t), _ptr(hit[0]), _ptr(hit[1]), _ptr(hit[2]), _ptr(y), B, H, W, C, kh, kw, sh, sw,
                   ph, pw, dh, dw, ACT[act], _lib.BF16, _lib.BF16, stream_ptr())
@@ -406,15 +396,13 @@ def _conv2d_padded_k(x: Act, conv, bn, act, prep, dims) -> Act:
     B, H, W, C, Ho, Wo = dims
     K = conv.out_channels
     Kp = (K + 7) // 8 * 8
-    cache = conv._cache()
-    key = ("kpad", _bn_id(bn))
-    hit = cache.get(key)
-    if hit is None:
+
+    def build():
         wp = torch.zeros((Kp,) + tuple(w.shape[1:]), dtype=w.dtype, device=w.device)
         wp[:K] = w
         pad1 = lambda v, fill: None if v is None else torch.cat([v, torch.full((Kp - K,), fill, dtype=v.dtype, device=v.device)])
-        hit = (wp, pad1(scale, 1.0), pad1(shift, 0.0))
-        cache[key] = hit
+        return wp, pad1(scale, 1.0), pad1(shift, 0.0)
+    hit = _prepared(conv, "kpad", (bn,), build)
     kh, kw = conv.kernel_size
     sh, sw = conv.stride
     ph, pw = conv.padding
@@ -471,7 +459,7 @@ def conv1x1_chain(x: Act, conv3, bn3, residual: Act, conv1n, bn1n, sub: int = 0)
     # a width mv_conv1x1_chain_supported refuses) where they have the shape
     for sb in ((2, 0) if sub == 2 else (0,)):
         if lib.mv_conv1x1_chain_res_supported(B, H, W, C, K, N2, sb, DT[dt]):
-            wf, shf, _ = chain_acc_operands(conv3, [[(conv3, bn3)]], conv1n, bn1n)
+            wf, shf = chain_acc_operands(conv3, [[(conv3, bn3)]], conv1n, bn1n)
             y = empty((B, H // 2, W // 2, K) if sb else (B, H, W, K), torch.bfloat16)
             t1 = empty((B, H, W, N2), torch.bfloat16)
             _lib.call("mv_conv1x1_chain_res_fwd", _ptr(x.t), _ptr(residual.t), _ptr(wf), _ptr(shf), _ptr(y), _ptr(t1), B, H, W, C, K, N2,
@@ -509,24 +497,21 @@ def _rc_shift_rows(*vecs) -> np.ndarray:
 
 
 def chain_acc_operands(cache_on, y_blocks, conv1n, bn1n):
-    """The (fragments, shift rows, kept modules) of the accumulator-layout chain kernels (csrc/chain_acc.h; header:
+    """The (fragments, shift rows) of the accumulator-layout chain kernels (csrc/chain_acc.h; header:
     mv_conv1x1_chain_rc_fwd, _chain_rc0_fwd, _chain_res_fwd, _dual_chain_res_fwd), cached on `cache_on`.  `y_blocks` lists the
     pointwise (conv, bn) groups that produce y, in the order of the kernel's reduction: the groups of ONE inner list add into the
     same accumulation, so their shifts are summed into one block of shift rows; every inner list has a block of its own.  Per
     32-channel chunk of y: the k-step fragments of the groups' scaled weight rows side by side, then the next conv1's
     (_res_fragments); shift rows: one block per inner list, then the next conv1's (_rc_shift_rows)."""
-    cache = cache_on._cache()
-    key = ("chain_acc", tuple(tuple((id(c), _bn_id(b)) for c, b in blk) for blk in y_blocks), id(conv1n), _bn_id(bn1n))
-    hit = cache.get(key)
-    if hit is None:
+    def build():
         blocks = [[_scaled_rows(c, b) for c, b in blk] for blk in y_blocks]
         wy = np.concatenate([w for blk in blocks for w, _ in blk], axis=1)
         w1n, hn = _scaled_rows(conv1n, bn1n)
         sh = _rc_shift_rows(*[np.add.reduce([h for _, h in blk]) for blk in blocks], hn)
-        others = tuple(c for blk in y_blocks for c, _ in blk if c is not cache_on) + (conv1n,)   # keeps the id()s in the key alive
-        hit = (_dev(_res_fragments(wy, w1n).reshape(-1), torch.bfloat16), torch.from_numpy(sh.view(np.int32)).to(device()), others)
-        cache[key] = hit
-    return hit
+        return _dev(_res_fragments(wy, w1n).reshape(-1), torch.bfloat16), torch.from_numpy(sh.view(np.int32)).to(device())
+    # (the block sizes are part of the variant: the same modules grouped differently are different operands)
+    return _prepared(cache_on, ("chain_acc",) + tuple(len(blk) for blk in y_blocks),
+                     [m for blk in y_blocks for pair in blk for m in pair] + [conv1n, bn1n], build)
 
 
 def _res_fragments(w3, w1n) -> np.ndarray:
@@ -569,7 +554,7 @@ def conv1x1_chain_rc(t2: Act, t2_prev: Act, x0: Act, conv3_0, bn3_0, ds_conv, ds
     if not _lib.load().mv_conv1x1_chain_rc_supported(M, C, K, N2, DT[dt]):
         return None
     # y0's two sources share an accumulation (one shift block, shift3_0 + shift_d); conv3_1 continues from bf16(y0) with its own
-    wf, tab, _ = chain_acc_operands(conv3_1, [[(conv3_0, bn3_0), (ds_conv, ds_bn)], [(conv3_1, bn3_1)]], conv1n, bn1n)
+    wf, tab = chain_acc_operands(conv3_1, [[(conv3_0, bn3_0), (ds_conv, ds_bn)], [(conv3_1, bn3_1)]], conv1n, bn1n)
     y = empty((B, H, W, K), torch.bfloat16)
     t1 = empty((B, H, W, N2), torch.bfloat16)
     _lib.call("mv_conv1x1_chain_rc_fwd", _ptr(t2.t), _ptr(t2_prev.t), _ptr(x0.t), _ptr(wf), _ptr(tab), _ptr(y), _ptr(t1), M, C, K, N2,
@@ -580,22 +565,14 @@ def conv1x1_chain_rc(t2: Act, t2_prev: Act, x0: Act, conv3_0, bn3_0, ds_conv, ds
 def _fold(conv, bn):
     """fp32 (scale, shift) of a convolution's bias + BatchNorm(inference) epilogue (ones / zeros where absent)."""
     K = conv.out_channels
-    bias = None if conv.bias is None else np.asarray(conv.bias, np.float32).reshape(-1)
-    if bn is not None:
-        scale, shift = bn_fold(bn)
-        if bias is not None:
-            shift = shift + bias * scale
-        return scale, shift
-    return np.ones(K, np.float32), (np.zeros(K, np.float32) if bias is None else bias)
+    scale, shift = _conv_fold(conv, bn)
+    return (np.ones(K, np.float32) if scale is None else scale), (np.zeros(K, np.float32) if shift is None else shift)
 
 
 def prep_bneck_tail(conv2, bn2, conv3, bn3):
     """Weights of a bottleneck's 3x3 and expansion convolutions in the FRAGMENT ORDER of mv_bottleneck_tail_fwd (header): a wave
     owns 32 output channels and fetches each k16-step of them as one contiguous 1 KB piece (cached on conv2)."""
-    key = ("bneck_tail", _bn_id(bn2), id(conv3), _bn_id(bn3))
-    cache = conv2._cache()
-    hit = cache.get(key)
-    if hit is None:
+    def build():
         w2 = np.ascontiguousarray(np.asarray(conv2.weight, np.float32).transpose(0, 2, 3, 1))     # [K][R][S][C]
         K, R, S, C = w2.shape
         w2f = w2.reshape(K // 32, 32, R * S, C // 16, 2, 8).transpose(0, 2, 3, 4, 1, 5)            # (wave, tap, j, h, m, e)
@@ -603,10 +580,9 @@ def prep_bneck_tail(conv2, bn2, conv3, bn3):
         w3f = w3.reshape(conv3.out_channels // 256, 8, 32, C // 16, 2, 8).transpose(0, 1, 3, 4, 2, 5)   # (chunk, wave, j, h, m, e)
         s2, h2 = _fold(conv2, bn2)
         s3, h3 = _fold(conv3, bn3)
-        hit = (_dev(w2f, torch.bfloat16), _dev(s2, torch.float32), _dev(h2, torch.float32),
-               _dev(w3f, torch.bfloat16), _dev(s3, torch.float32), _dev(h3, torch.float32), conv3)   # conv3: keeps the id() in the key alive
-        cache[key] = hit
-    return hit
+        return (_dev(w2f, torch.bfloat16), _dev(s2, torch.float32), _dev(h2, torch.float32),
+                _dev(w3f, torch.bfloat16), _dev(s3, torch.float32), _dev(h3, torch.float32))
+    return _prepared(conv2, "bneck_tail", (bn2, conv3, bn3), build)
 
 
 def bottleneck_tail(t1: Act, conv2, bn2, conv3, bn3, identity: Act) -> Optional[Act]:
@@ -627,7 +603,7 @@ def bottleneck_tail(t1: Act, conv2, bn2, conv3, bn3, identity: Act) -> Optional[
         return None
     if not _lib.load().mv_bottleneck_tail_supported(H, W, C, K, DT[dt]):
         return None
-    w2f, s2, h2, w3f, s3, h3, _ = prep_bneck_tail(conv2, bn2, conv3, bn3)
+    w2f, s2, h2, w3f, s3, h3 = prep_bneck_tail(conv2, bn2, conv3, bn3)
     y = empty((B, H, W, K), torch.bfloat16)
     _lib.call("mv_bottleneck_tail_fwd", _ptr(t1.t), _ptr(w2f), _ptr(s2), _ptr(h2), _ptr(w3f), _ptr(s3), _ptr(h3),
               _ptr(identity.t), _ptr(y), B, H, W, C, K, DT[dt], stream_ptr())
@@ -643,15 +619,11 @@ def _scaled_rows(conv, bn) -> Tuple[np.ndarray, np.ndarray]:
 
 def _dual_weights(conv3, bn3, ds_conv, ds_bn):
     """[scale3 * W3 | scale_d * W_d] as bf16 rows and shift3 + shift_d (cached on conv3)."""
-    cache = conv3._cache()
-    key = ("dual", _bn_id(bn3), id(ds_conv), _bn_id(ds_bn))
-    hit = cache.get(key)
-    if hit is None:
+    def build():
         w3, h3 = _scaled_rows(conv3, bn3)
         wd, hd = _scaled_rows(ds_conv, ds_bn)
-        hit = (_dev(np.concatenate([w3, wd], axis=1), torch.bfloat16), _dev((h3 + hd).astype(np.float32), torch.float32))
-        cache[key] = hit
-    return hit
+        return _dev(np.concatenate([w3, wd], axis=1), torch.bfloat16), _dev((h3 + hd).astype(np.float32), torch.float32)
+    return _prepared(conv3, "dual", (bn3, ds_conv, ds_bn), build)
 
 
 def conv1x1_dual(x: Act, conv3, bn3, xin: Act, ds_conv, ds_bn, act="relu") -> Optional[Act]:
@@ -738,7 +710,7 @@ def conv1x1_dual_chain(x: Act, conv3, bn3, xin: Act, ds_conv, ds_bn, conv1n, bn1
     if store_y and (ds_stride == (1, 1) or (xin.sub is not None and ds_stride == (xin.sub, xin.sub))) \
             and _lib.load().mv_conv1x1_dual_chain_res_supported(M, C1, C2, K, N2, DT[dt]):
         # C = 128 / K = 512 (layer 2 entry): y stored, weights streamed (csrc/chain_l2.hip); xin is the map the downsample branch reads
-        wf, tab, _ = chain_acc_operands(conv3, [[(conv3, bn3), (ds_conv, ds_bn)]], conv1n, bn1n)
+        wf, tab = chain_acc_operands(conv3, [[(conv3, bn3), (ds_conv, ds_bn)]], conv1n, bn1n)
         y = empty((B, H, W, K), torch.bfloat16)
         t1 = empty((B, H, W, N2), torch.bfloat16)
         _lib.call("mv_conv1x1_dual_chain_res_fwd", _ptr(x.t), _ptr(xin.t), _ptr(wf), _ptr(tab), _ptr(y), _ptr(t1), M, C1, C2, K, N2,
@@ -747,7 +719,7 @@ def conv1x1_dual_chain(x: Act, conv3, bn3, xin: Act, ds_conv, ds_bn, conv1n, bn1
     if not _pointwise(ds_conv) or not _lib.load().mv_conv1x1_dual_chain_supported(M, C1, C2, K, N2, DT[dt]):
         return None
     if not store_y and not _lib.get_flag("no_chain_rc0") and _lib.load().mv_conv1x1_chain_rc_supported(M, C1, K, N2, DT[dt]):
-        wf, tab, _ = chain_acc_operands(conv3, [[(conv3, bn3), (ds_conv, ds_bn)]], conv1n, bn1n)   # the same function without its output map
+        wf, tab = chain_acc_operands(conv3, [[(conv3, bn3), (ds_conv, ds_bn)]], conv1n, bn1n)   # the same function without its output map
         t1 = empty((B, H, W, N2), torch.bfloat16)
         _lib.call("mv_conv1x1_chain_rc0_fwd", _ptr(x.t), _ptr(xin.t), _ptr(wf), _ptr(tab), _ptr(t1), M, C1, K, N2, DT[dt], stream_ptr())
         return Act(t1, "map", x.batched)
@@ -818,7 +790,7 @@ def linear(x: Act, lin, act=None, residual: Optional[Act] = None, out_fp32: bool
         # split-K over the CUs, fixed-order reduction (csrc/fc_stream.hip)
         # (decided BEFORE prep_linear: the row-major bf16 copy of a 9216 x 4096 weight would only double the device memory)
         wf = fc_fragments(lin)
-        b = prep_f32(lin, "bias", None if lin.bias is None else np.asarray(lin.bias, np.float32).reshape(-1))
+        b = prep_f32(lin, "bias", _bias(lin))
         nbytes = int(_lib.load().mv_fc_stream_workspace(M, N, K))
         ws = _fc_workspace(nbytes)
         _lib.call("mv_fc_stream_fwd", _ptr(x.t), _ptr(wf), _ptr(b), _ptr(y), _ptr(ws), nbytes, M, N, K, ACT[act], DT[dt], odc, stream_ptr())
@@ -877,18 +849,15 @@ def _splitk_scratch(M: int, N: int, kred: int):
 def fc_fragments(lin) -> torch.Tensor:
     """Linear weight [N][K] in MFMA fragment order for csrc/fc_stream.hip: [N / 32 tiles][K / 16 steps][64 lanes][8] bf16, lane
     (n = l % 32, h = l / 32) holds W[32 tile + n][16 step + 8 h .. + 7]; N is padded to a multiple of 32 with zero rows (cached)."""
-    cache = lin._cache()
-    hit = cache.get("fc_frag")
-    if hit is None:
+    def build():
         w = torch.from_numpy(np.ascontiguousarray(np.asarray(lin.weight, np.float32))).to(torch.bfloat16)
         N, K = w.shape
         NT = (N + 31) // 32
         if NT * 32 != N:
             w = torch.cat([w, torch.zeros((NT * 32 - N, K), dtype=torch.bfloat16)], dim=0)
         # [NT][32 n][K/16][2 h][8] -> [NT][K/16][2 h][32 n][8]
-        hit = w.view(NT, 32, K // 16, 2, 8).permute(0, 2, 3, 1, 4).contiguous().to(device())
-        cache["fc_frag"] = hit
-    return hit
+        return w.view(NT, 32, K // 16, 2, 8).permute(0, 2, 3, 1, 4).contiguous().to(device())
+    return _prepared(lin, "fc_frag", (), build)
 
 
 def linear_head(x: Act, lin) -> Act:
@@ -1042,34 +1011,21 @@ def layernorm(x: Act, ln, out_fp32: bool = False) -> Act:
 
 def _ln_folded(lin, ln):
     """(W . diag(gamma) as bf16, b + W . beta as fp32) on the device, cached on the Linear."""
-    cache = lin._cache()
-    key = ("ln_fold", id(ln.weight), id(ln.bias))
-    hit = cache.get(key)
-    if hit is None:
-        w = np.asarray(lin.weight, np.float32)
-        g, b = np.asarray(ln.weight, np.float32).reshape(-1), np.asarray(ln.bias, np.float32).reshape(-1)
-        b0 = np.zeros(w.shape[0], np.float32) if lin.bias is None else np.asarray(lin.bias, np.float32).reshape(-1)
-        hit = (_dev(w * g[None, :], torch.bfloat16), _dev(b0 + w @ b, torch.float32), ln)      # ln: keeps the ids alive
-        cache[key] = hit
-    return hit
+    def build():
+        w, b = _ln_fold(lin, ln)
+        return _dev(w, torch.bfloat16), _dev(b, torch.float32)
+    return _prepared(lin, "ln_fold", (ln.weight, ln.bias), build)
 
 
 def _ln_folded_cs(lin, ln):
     """For mv_linear_lnin_fwd: (W' = bf16(W . diag(gamma)), colsum[n] = sum_k W'[n][k] of the ROUNDED values, b' = b + W . beta),
     on the device, cached on the Linear."""
-    cache = lin._cache()
-    key = ("ln_fold_cs", id(ln.weight), id(ln.bias))
-    hit = cache.get(key)
-    if hit is None:
-        w = np.asarray(lin.weight, np.float32)
-        g, b = np.asarray(ln.weight, np.float32).reshape(-1), np.asarray(ln.bias, np.float32).reshape(-1)
-        b0 = np.zeros(w.shape[0], np.float32) if lin.bias is None else np.asarray(lin.bias, np.float32).reshape(-1)
-        wf = torch.from_numpy(np.ascontiguousarray(w * g[None, :])).to(torch.bfloat16)
+    def build():
+        w, bf = _ln_fold(lin, ln, wide=True)
+        wf = torch.from_numpy(np.ascontiguousarray(w)).to(torch.bfloat16)
         cs = wf.to(torch.float64).sum(dim=1).to(torch.float32).numpy()
-        bf = (b0.astype(np.float64) + w.astype(np.float64) @ b.astype(np.float64)).astype(np.float32)
-        hit = (wf.to(device()), _dev(cs, torch.float32), _dev(bf, torch.float32), ln)      # ln: keeps the ids alive
-        cache[key] = hit
-    return hit
+        return wf.to(device()), _dev(cs, torch.float32), _dev(bf, torch.float32)
+    return _prepared(lin, "ln_fold_cs", (ln.weight, ln.bias), build)
 
 
 def _ln_foldable(ln, C: int) -> bool:
@@ -1138,7 +1094,7 @@ def linear_lnin(x: Act, ln, lin, act=None, heads: int = 0):
     hi, st = x.t, x.ln[1]
     N, K = lin.out_features, lin.in_features
     M = hi.numel() // K
-    w, cs, b = _ln_folded_cs(lin, ln)[:3]
+    w, cs, b = _ln_folded_cs(lin, ln)
     if heads:
         B, T, D = hi.shape
         y = empty((B, 3 * heads, T, D // heads), torch.bfloat16)
@@ -1165,7 +1121,7 @@ def ln_linear(x: Act, ln, lin, act=None) -> Act:
         ok = bool(_lib.load().mv_ln_linear_supported(M, lin.out_features, C, xdt, _lib.BF16))
     if not ok:
         return linear(layernorm(x, ln), lin, act=act)
-    w, b = _ln_folded(lin, ln)[:2]
+    w, b = _ln_folded(lin, ln)
     y = empty(tuple(x.t.shape[:-1]) + (lin.out_features,), torch.bfloat16)
     _lib.call("mv_ln_linear_fwd", _ptr(x.t), _ptr(w), _ptr(b), _ptr(y), M, lin.out_features, C, float(ln.eps), ACT[act], xdt,
               _lib.BF16, stream_ptr())
@@ -1194,17 +1150,12 @@ def ln_mlp(x: Act, ln, mlp) -> Optional[Act]:
         if _lib.load().mv_ln_mlp_stream_supported(M, C, Hd, xdt):
             return _ln_mlp_stream(x, ln, mlp, M, C, Hd, xdt)
         return None
-    cache = mlp._cache()
-    key = ("ln_mlp", id(ln.weight), id(ln.bias))
-    hit = cache.get(key)
-    if hit is None:
-        w1 = np.asarray(fc1.weight, np.float32)
-        g, b = np.asarray(ln.weight, np.float32).reshape(-1), np.asarray(ln.bias, np.float32).reshape(-1)
-        hit = (_dev(w1 * g[None, :], torch.bfloat16),
-               _dev(np.asarray(fc1.bias, np.float32).reshape(-1) + w1 @ b, torch.float32),
-               _dev(np.asarray(fc2.weight, np.float32), torch.bfloat16),
-               _dev(np.asarray(fc2.bias, np.float32).reshape(-1), torch.float32), ln)        # ln: keeps the ids alive
-        cache[key] = hit
+
+    def build():
+        w1, b1 = _ln_fold(fc1, ln)
+        return (_dev(w1, torch.bfloat16), _dev(b1, torch.float32), _dev(np.asarray(fc2.weight, np.float32), torch.bfloat16),
+                _dev_bias(fc2))
+    hit = _prepared(mlp, "ln_mlp", (ln.weight, ln.bias), build)
     y = empty(tuple(x.t.shape), x.t.dtype)
     _lib.call("mv_ln_mlp_fwd", _ptr(x.t), _ptr(hit[0]), _ptr(hit[1]), _ptr(hit[2]), _ptr(hit[3]), _ptr(y), M, C, Hd,
               float(ln.eps), xdt, stream_ptr())
@@ -1222,16 +1173,12 @@ def ln_mlp_fragments(w1: np.ndarray, w2: np.ndarray):
 def _ln_mlp_stream(x: Act, ln, mlp, M, C, Hd, xdt) -> Act:
     """ln_mlp's wide-row variant: weights streamed from L2 in fragment order (LayerNorm affine folded into fc1 on the host)."""
     fc1, fc2 = mlp.fc1, mlp.fc2
-    cache = mlp._cache()
-    key = ("ln_mlp_stream", id(ln.weight), id(ln.bias))
-    hit = cache.get(key)
-    if hit is None:
-        w1 = np.asarray(fc1.weight, np.float32)
-        g, b = np.asarray(ln.weight, np.float32).reshape(-1), np.asarray(ln.bias, np.float32).reshape(-1)
-        w1f, w2f = ln_mlp_fragments(w1 * g[None, :], np.asarray(fc2.weight, np.float32))
-        hit = (_dev(w1f, torch.bfloat16), _dev(np.asarray(fc1.bias, np.float32).reshape(-1) + w1 @ b, torch.float32),
-               _dev(w2f, torch.bfloat16), _dev(np.asarray(fc2.bias, np.float32).reshape(-1), torch.float32), ln)
-        cache[key] = hit
+
+    def build():
+        w1, b1 = _ln_fold(fc1, ln)
+        w1f, w2f = ln_mlp_fragments(w1, np.asarray(fc2.weight, np.float32))
+        return _dev(w1f, torch.bfloat16), _dev(b1, torch.float32), _dev(w2f, torch.bfloat16), _dev_bias(fc2)
+    hit = _prepared(mlp, "ln_mlp_stream", (ln.weight, ln.bias), build)
     y = empty(tuple(x.t.shape), x.t.dtype)
     _lib.call("mv_ln_mlp_stream_fwd", _ptr(x.t), _ptr(hit[0]), _ptr(hit[1]), _ptr(hit[2]), _ptr(hit[3]), _ptr(y), M, C, Hd,
               float(ln.eps), xdt, stream_ptr())
@@ -1270,12 +1217,7 @@ def batchnorm(x: Act, bn, act=None) -> Act:
     if _bn_training(bn):
         sc, sh = bn_train_update(bn, x)
         return _bn_affine(x, sc, sh, act)
-    cache = bn._cache()
-    hit = cache.get(("fold", bn.state_index.version))
-    if hit is None:
-        s, h = bn_fold(bn)
-        hit = (_dev(s, torch.float32), _dev(h, torch.float32))
-        cache[("fold", bn.state_index.version)] = hit
+    hit = _prepared(bn, "fold", (bn,), lambda: tuple(_dev(v, torch.float32) for v in bn_fold(bn)))
     C = x.t.shape[-1]
     y = empty(tuple(x.t.shape), x.t.dtype)
     _lib.call("mv_channel_affine_fwd", _ptr(x.t), _ptr(hit[0]), _ptr(hit[1]), _ptr(y), x.t.numel() // C, C,
@@ -1402,12 +1344,7 @@ def qkv_attention(x: Act, lin, heads: int, scale: float, need_probs: bool, drop=
 def swin_rel_bias(attn) -> torch.Tensor:
     """The relative-position bias [heads][n][n] of a _ShiftedWindowAttention on the device: table[index] gathered on the host
     (swin.py:34-43), cached on the module."""
-    cache = attn._cache()
-    b = cache.get("bias")
-    if b is None:
-        b = _dev(attn.get_relative_position_bias(), torch.float32)
-        cache["bias"] = b
-    return b
+    return _prepared(attn, "bias", (), lambda: _dev(attn.get_relative_position_bias(), torch.float32))
 
 
 def swin_window_attention(qkv: Act, bias: torch.Tensor, heads: int, window, shift, drop=None) -> Act:
@@ -1465,20 +1402,18 @@ def swin_block_attention(x: Act, norm, attn) -> Optional[Act]:
         sh[1] = 0
     if attn.qkv.in_features != C or not _lib.load().mv_swin_block_attn_supported(Hf, Wf, C, attn.num_heads, ws[0], ws[1], _lib.F32):
         return None
-    cache = attn._cache()
-    key = ("block_attn", id(norm.weight), id(norm.bias))
-    hit = cache.get(key)
-    if hit is None:
-        wq = np.asarray(attn.qkv.weight, np.float32)
-        g, b = np.asarray(norm.weight, np.float32).reshape(-1), np.asarray(norm.bias, np.float32).reshape(-1)
-        frags = swin_block_attn_fragments(wq * g[None, :], np.asarray(attn.qkv.bias, np.float32).reshape(-1) + wq @ b,
-                                          np.asarray(attn.proj.weight, np.float32), attn.get_relative_position_bias())
+
+    def build():
+        frags = swin_block_attn_fragments(*_ln_fold(attn.qkv, norm), np.asarray(attn.proj.weight, np.float32),
+                                          attn.get_relative_position_bias())
         if frags is None:
             return None
         wf, bq, wpf, b64 = frags
-        hit = (_dev(wf, torch.bfloat16), _dev(bq, torch.float32), _dev(wpf, torch.bfloat16),
-               _dev(np.asarray(attn.proj.bias, np.float32).reshape(-1), torch.float32), _dev(b64, torch.float32), norm)
-        cache[key] = hit
+        return (_dev(wf, torch.bfloat16), _dev(bq, torch.float32), _dev(wpf, torch.bfloat16), _dev_bias(attn.proj),
+                _dev(b64, torch.float32))
+    hit = _prepared(attn, "block_attn", (norm.weight, norm.bias), build)
+    if hit is None:
+        return None
     y = empty(tuple(x.t.shape), torch.float32)
     _lib.call("mv_swin_block_attn_fwd", _ptr(x.t), _ptr(hit[0]), _ptr(hit[1]), _ptr(hit[2]), _ptr(hit[3]), _ptr(hit[4]), _ptr(y),
               B, Hf, Wf, C, attn.num_heads, ws[0], ws[1], sh[0], sh[1], float(norm.eps), _lib.F32, stream_ptr())
@@ -1532,17 +1467,14 @@ def swin_v2_operands(attn):
     LayerNorm folding of swin_block_attention -- cached on the module, keyed by the identities of the leaves they are made of."""
     l1, l2 = _cpb_linears(attn)
     leaves = (l1.weight, l1.bias, l2.weight, attn.logit_scale, attn.relative_position_index, attn.relative_position_bias_table)
-    key = ("v2_operands",) + tuple(id(a) for a in leaves)
-    cache = attn._cache()
-    hit = cache.get(key)
-    if hit is None:
+
+    def build():
         bias = swin_v2_rel_bias_host(attn.relative_position_bias_table, attn.relative_position_index, l1.weight, l1.bias, l2.weight,
                                      attn.num_heads, attn.window_size)
         ls = np.asarray(attn.logit_scale, np.float32).reshape(-1)
         mul = np.exp(np.minimum(ls, np.float32(np.log(100.0)))).astype(np.float32)       # reference :165-167
-        hit = (_dev(bias, torch.float32), _dev(mul, torch.float32), leaves)              # leaves: keeps the ids alive
-        cache[key] = hit
-    return hit[0], hit[1]
+        return _dev(bias, torch.float32), _dev(mul, torch.float32)
+    return _prepared(attn, "v2_operands", leaves, build)
 
 
 def swin_v2_rel_bias(attn) -> torch.Tensor:
@@ -1556,17 +1488,14 @@ def swin_v2_qkv(attn):
     lin = attn.qkv
     if lin.bias is None:
         return lin
-    key = ("v2_qkv", id(lin.weight), id(lin.bias))
-    cache = attn._cache()
-    hit = cache.get(key)
-    if hit is None:
+
+    def build():
         from ._module import tree_at
         b = np.array(np.asarray(lin.bias, np.float32))
         n = b.size // 3
         b.reshape(-1)[n:2 * n] = 0
-        hit = (tree_at(lambda l: l.bias, lin, b), lin.weight, lin.bias)
-        cache[key] = hit
-    return hit[0]
+        return tree_at(lambda l: l.bias, lin, b)
+    return _prepared(attn, "v2_qkv", (lin.weight, lin.bias), build)
 
 
 def swin_qk_rnorm(qkv: Act, window, shift) -> torch.Tensor:
@@ -1677,14 +1606,9 @@ def se_scale(x: Act, fc1, fc2, act1, act2) -> Optional[Act]:
             or fc2.out_channels != C or act1 not in ACT or act2 not in ACT or not _lib.load().mv_se_scale_supported(C, S, _lib.BF16)):
         return None
     w1, _, b1 = prep_conv(fc1, None, "krsc", "bf16")
-    cache = fc2._cache()
-    hit = cache.get("se_w2t")
-    if hit is None:                     # [S][C]: the kernel's threads read consecutive channels of a row
-        w = np.asarray(fc2.weight, np.float32).reshape(C, S)
-        hit = (_dev(np.ascontiguousarray(w.T), torch.bfloat16),
-               None if fc2.bias is None else _dev(np.asarray(fc2.bias, np.float32).reshape(-1), torch.float32))
-        cache["se_w2t"] = hit
-    w2, b2 = hit
+    # [S][C]: the kernel's threads read consecutive channels of a row
+    w2, b2 = _prepared(fc2, "se_w2t", (), lambda: (
+        _dev(np.ascontiguousarray(np.asarray(fc2.weight, np.float32).reshape(C, S).T), torch.bfloat16), _dev_bias(fc2)))
     s = empty((B, C), torch.bfloat16)
     _lib.call("mv_se_scale_fwd", _ptr(x.t), _ptr(w1), _ptr(b1), _ptr(w2), _ptr(b2), _ptr(s), B, H * W, C, S, ACT[act1], ACT[act2],
               _lib.BF16, stream_ptr())
@@ -1819,14 +1743,11 @@ def patch_merge_gather(x: Act) -> Act:
 # ------------------------------------------------------------------ ConvNeXt block (models/classification/convnext.py)
 def prep_dw(conv, bn=None):
     """Depthwise filters (C, 1, R, S) re-laid to [R][S][C] bf16 + folded scale / shift (cached: the "dw" entry conv2d uses)."""
-    cache = conv._cache()
-    hit = cache.get(("dw", _bn_id(bn)))
-    if hit is None:
+    def build():
         _, scale, shift = prep_conv(conv, bn, "oihw", "bf16")
         wr = np.ascontiguousarray(np.asarray(conv.weight, np.float32)[:, 0].transpose(1, 2, 0))     # (C,1,R,S) -> [R][S][C]
-        hit = (_dev(wr, torch.bfloat16), scale, shift)
-        cache[("dw", _bn_id(bn))] = hit
-    return hit
+        return _dev(wr, torch.bfloat16), scale, shift
+    return _prepared(conv, "dw", (bn,), build)
 
 
 def _cnblock_layers(blk):
@@ -1850,22 +1771,14 @@ def _cnblock_layers(blk):
 def _cnblock_mlp(blk, ln, fc1, fc2, form: str):
     """The block's MLP with the LayerNorm affine folded into fc1 (W1 diag(g), b1 + W1 beta) and layer_scale into fc2 (diag(ls) W2 in
     fp32, then one bf16 rounding; ls * b2).  form "lds" / "lin": row-major; "stream": mv_ln_mlp_stream_fwd's fragment order."""
-    ls = np.asarray(blk.layer_scale, np.float32).reshape(-1)
-    key = ("cnb_mlp", form) + tuple(id(a) for a in (ln.weight, ln.bias, fc1.weight, fc1.bias, fc2.weight, fc2.bias, blk.layer_scale))
-    cache = blk._cache()
-    hit = cache.get(key)
-    if hit is None:
-        w1 = np.asarray(fc1.weight, np.float32)
-        g, b = np.asarray(ln.weight, np.float32).reshape(-1), np.asarray(ln.bias, np.float32).reshape(-1)
-        w1f = w1 * g[None, :]
+    def build():
+        ls = np.asarray(blk.layer_scale, np.float32).reshape(-1)
+        w1f, b1 = _ln_fold(fc1, ln)
         w2f = np.asarray(fc2.weight, np.float32) * ls[:, None]
         if form == "stream":
             w1f, w2f = ln_mlp_fragments(w1f, w2f)
-        hit = (_dev(w1f, torch.bfloat16), _dev(np.asarray(fc1.bias, np.float32).reshape(-1) + w1 @ b, torch.float32),
-               _dev(w2f, torch.bfloat16), _dev(np.asarray(fc2.bias, np.float32).reshape(-1) * ls, torch.float32),
-               (ln.weight, ln.bias, fc1.weight, fc1.bias, fc2.weight, fc2.bias, blk.layer_scale))      # keeps the ids alive
-        cache[key] = hit
-    return hit
+        return _dev(w1f, torch.bfloat16), _dev(b1, torch.float32), _dev(w2f, torch.bfloat16), _dev(_bias(fc2) * ls, torch.float32)
+    return _prepared(blk, ("cnb_mlp", form), (ln.weight, ln.bias, fc1.weight, fc1.bias, fc2.weight, fc2.bias, blk.layer_scale), build)
 
 
 def _cnblock_dw(x: Act, dw, ln, normalize: int, y_dt: str) -> Act:
@@ -1887,19 +1800,17 @@ def convnext_downsample(x: Act, ln, conv) -> Act:
     if H % 2 or W % 2 or x.t.dtype != torch.float32 or tuple(conv.kernel_size) != (2, 2) or tuple(conv.stride) != (2, 2) \
             or tuple(conv.padding) != (0, 0) or conv.groups != 1:
         return cast(conv2d(n, conv), "fp32") if x.t.dtype == torch.float32 else conv2d(n, conv)
-    cache = conv._cache()
-    lin = cache.get("patch_linear")
-    if lin is None:
+
+    def build():
         from . import nn
         K = conv.out_channels
         lin = nn.Linear.__new__(nn.Linear)
         w = np.asarray(conv.weight, np.float32)                  # (K, C, dh, dw) -> [K][dw][dh][C]: the gather's (dh, dw) order
-        for f, v in (("weight", np.ascontiguousarray(w.transpose(0, 3, 2, 1).reshape(K, 4 * C))),
-                     ("bias", None if conv.bias is None else np.asarray(conv.bias, np.float32).reshape(-1)),
+        for f, v in (("weight", np.ascontiguousarray(w.transpose(0, 3, 2, 1).reshape(K, 4 * C))), ("bias", _bias(conv)),
                      ("in_features", 4 * C), ("out_features", K), ("use_bias", conv.bias is not None)):
             object.__setattr__(lin, f, v)
-        cache["patch_linear"] = lin
-    return linear_split(patch_merge_gather(n), lin, out_fp32=True)
+        return lin
+    return linear_split(patch_merge_gather(n), _prepared(conv, "patch_linear", (), build), out_fp32=True)
 
 
 def cnblock(x: Act, blk, drop=None) -> Act:
@@ -1917,7 +1828,7 @@ def cnblock(x: Act, blk, drop=None) -> Act:
         if x.t.dtype == torch.float32 and lib.mv_ln_mlp_res_supported(M, C, Hd, _lib.BF16) and \
                 lib.mv_cnblock_dw_supported(C, H, W, x.dt, _lib.BF16, 0):
             d = _cnblock_dw(x, dw, ln, 0, "bf16")
-            w1, b1, w2, b2, _ = _cnblock_mlp(blk, ln, fc1, fc2, "lds")
+            w1, b1, w2, b2 = _cnblock_mlp(blk, ln, fc1, fc2, "lds")
             y = empty((B, H, W, C), torch.float32)
             _lib.call("mv_ln_mlp_res_fwd", _ptr(d.t), _ptr(x.t), _ptr(w1), _ptr(b1), _ptr(w2), _ptr(b2), _ptr(y), M, C, Hd,
                       float(ln.eps), _lib.BF16, stream_ptr())
@@ -1927,14 +1838,14 @@ def cnblock(x: Act, blk, drop=None) -> Act:
             # the stream kernel reads fp32 rows: d is written in fp32 (+8 B per element of d against bf16, in exchange for keeping
             # the 577-line kernel single-typed)
             d = _cnblock_dw(x, dw, ln, 0, "fp32")
-            w1, b1, w2, b2, _ = _cnblock_mlp(blk, ln, fc1, fc2, "stream")
+            w1, b1, w2, b2 = _cnblock_mlp(blk, ln, fc1, fc2, "stream")
             y = empty((B, H, W, C), torch.float32)
             _lib.call("mv_ln_mlp_stream_res_fwd", _ptr(d.t), _ptr(x.t), _ptr(w1), _ptr(b1), _ptr(w2), _ptr(b2), _ptr(y), M, C, Hd,
                       float(ln.eps), _lib.F32, stream_ptr())
             return Act(y, "map", x.batched)
         if lib.mv_cnblock_dw_supported(C, H, W, x.dt, _lib.BF16, 1):
             n = _cnblock_dw(x, dw, ln, 1, "bf16")
-            w1, b1, w2, b2, _ = _cnblock_mlp(blk, ln, fc1, fc2, "lin")
+            w1, b1, w2, b2 = _cnblock_mlp(blk, ln, fc1, fc2, "lin")
             h = empty((B, H, W, Hd), torch.bfloat16)
             _splitk_scratch(M, Hd, C)
             _lib.call("mv_linear_fwd", _ptr(n.t), _ptr(w1), None, _ptr(b1), None, _ptr(h), M, Hd, C, _lib.ACT_GELU_TANH, _lib.BF16,
@@ -2129,12 +2040,7 @@ def channel_gather(x: Act, idx: torch.Tensor) -> Act:
 
 
 def _gather_index(mod, name, idx: np.ndarray) -> torch.Tensor:
-    cache = mod._cache()
-    hit = cache.get(("gather", name))
-    if hit is None:
-        hit = _dev(np.asarray(idx, np.int32), torch.int32)
-        cache[("gather", name)] = hit
-    return hit
+    return _prepared(mod, ("gather", name), (), lambda: _dev(np.asarray(idx, np.int32), torch.int32))
 
 
 def _channel_slice(x: Act, c0: int, c1: int) -> Act:
@@ -2163,21 +2069,19 @@ def _shuffle_operands(unit, layout_in, C_in: int):
     parts = _shuffle_parts(unit)
     if parts is None:
         return None
-    bns = tuple(_bn_id(m) for br in parts if br is not None for m in br[1::2])
-    key = ("shuffle_fold", layout_in, C_in, bns)
-    cache = unit._cache()
-    if key in cache:
-        return cache[key]
-    F = shuffle_fold_unit(unit, layout_in, C_in)
-    if F is not None:
+
+    def build():
+        F = shuffle_fold_unit(unit, layout_in, C_in)
+        if F is None:
+            return None
+
         def tail(T):
             return (_dev(T[0], torch.bfloat16), _dev(T[1], torch.float32), _dev(T[2], torch.float32),
                     _dev(dwpw_fragments(T[3]), torch.bfloat16), _dev(T[4], torch.float32), _dev(T[5], torch.float32))
         w1, s1, h1 = F["pw1"]
-        F = dict(F, pw1=(_dev(w1, torch.bfloat16), _dev(s1, torch.float32), _dev(h1, torch.float32)), tail2=tail(F["tail2"]),
-                 tail1=None if F["tail1"] is None else tail(F["tail1"]))
-    cache[key] = F
-    return F
+        return dict(F, pw1=(_dev(w1, torch.bfloat16), _dev(s1, torch.float32), _dev(h1, torch.float32)), tail2=tail(F["tail2"]),
+                    tail1=None if F["tail1"] is None else tail(F["tail1"]))
+    return _prepared(unit, ("shuffle_fold", layout_in, C_in), [m for br in parts if br is not None for m in br[1::2]], build)
 
 
 def _conv1x1_folded(x: Act, w: torch.Tensor, scale: torch.Tensor, shift: torch.Tensor, K: int) -> Act:
@@ -2239,13 +2143,11 @@ def shuffle_head(x: Act, conv, bn, layout_in) -> Act:
         return conv2d(x, conv, bn, "relu")
     if compute_dtype() != "bf16" or _bn_training(bn) or not _pointwise(conv) or conv.out_channels % 8:
         return conv2d(shuffle_unfold(x, layout_in, conv), conv, bn, "relu")
-    cache = conv._cache()
-    key = ("shuffle_head", layout_in, _bn_id(bn))
-    hit = cache.get(key)
-    if hit is None:
+
+    def build():
         w, s, h = shuffle_fold_head(conv, bn, layout_in)
-        hit = (_dev(w, torch.bfloat16), _dev(s, torch.float32), _dev(h, torch.float32))
-        cache[key] = hit
+        return _dev(w, torch.bfloat16), _dev(s, torch.float32), _dev(h, torch.float32)
+    hit = _prepared(conv, ("shuffle_head", layout_in), (bn,), build)
     return _conv1x1_folded(as_map(x), *hit, conv.out_channels)
 
 
@@ -2309,14 +2211,9 @@ def fire(x: Act, mod) -> Act:
         # measured: 64 -> 256 + 256 on 27 x 27 maps at 256 images is the one Fire of both networks where the
         # composition beats the fused launch (by 5 - 8 %); it stays on the composition
         return fire_literal(x, mod)
-    cache = mod._cache()
-    ops_ = cache.get("fire_expand")
-    if ops_ is None:
-        def bias(conv):
-            return None if conv.bias is None else _dev(np.asarray(conv.bias, np.float32).reshape(-1), torch.float32)
-        ops_ = (_dev(fire_fragments(np.asarray(mod.expand1x1.weight, np.float32)), torch.bfloat16), bias(mod.expand1x1),
-                _dev(fire_fragments(np.asarray(mod.expand3x3.weight, np.float32)), torch.bfloat16), bias(mod.expand3x3))
-        cache["fire_expand"] = ops_
+    ops_ = _prepared(mod, "fire_expand", (), lambda: (
+        _dev(fire_fragments(np.asarray(mod.expand1x1.weight, np.float32)), torch.bfloat16), _dev_bias(mod.expand1x1),
+        _dev(fire_fragments(np.asarray(mod.expand3x3.weight, np.float32)), torch.bfloat16), _dev_bias(mod.expand3x3)))
     t = conv2d(x, mod.squeeze, None, "relu")
     y = empty((B, H, W, E1 + E3), torch.bfloat16)
     _lib.call("mv_fire_expand_fwd", _ptr(t.t), _ptr(ops_[0]), _ptr(ops_[1]), _ptr(ops_[2]), _ptr(ops_[3]), _ptr(y), B, H, W, S, E1, E3,
@@ -2423,18 +2320,16 @@ def inception(x: Act, mod) -> Act:
         return inception_literal(x, mod)
     if (C, H) in INCEPTION_LITERAL_SHAPES and H == W and not _lib.get_flag("inception_always"):
         return inception_literal(x, mod)
-    cache = mod._cache()
-    key = ("inception", tuple(_bn_id(u.bn) for u in units))
-    hit = cache.get(key)
-    if hit is None:
+
+    def build():
         f = [(np.asarray(u.conv.weight, np.float32),) + bn_fold(u.bn) for u in units]
         wm, sm, hm, _ = inception_stack([f[0], f[1], f[3]])
         d32 = lambda a: _dev(a, torch.float32)
-        hit = dict(merged=(_dev(wm, torch.bfloat16), d32(sm), d32(hm)),
-                   proj=(_dev(f[5][0].reshape(cp, C), torch.bfloat16), d32(f[5][1]), d32(f[5][2])),
-                   w3=(_dev(inception_fragments(f[2][0]), torch.bfloat16), d32(f[2][1]), d32(f[2][2])),
-                   w5=(_dev(inception_fragments(f[4][0], c5p), torch.bfloat16), d32(f[4][1]), d32(f[4][2])))
-        cache[key] = hit
+        return dict(merged=(_dev(wm, torch.bfloat16), d32(sm), d32(hm)),
+                    proj=(_dev(f[5][0].reshape(cp, C), torch.bfloat16), d32(f[5][1]), d32(f[5][2])),
+                    w3=(_dev(inception_fragments(f[2][0]), torch.bfloat16), d32(f[2][1]), d32(f[2][2])),
+                    w5=(_dev(inception_fragments(f[4][0], c5p), torch.bfloat16), d32(f[4][1]), d32(f[4][2])))
+    hit = _prepared(mod, "inception", [u.bn for u in units], build)
     M, st = B * H * W, stream_ptr()
     y = empty((B, H, W, Ct), torch.bfloat16)
     t = empty((B, H, W, lt), torch.bfloat16)
@@ -2552,18 +2447,14 @@ def dense_block_plan(block, C0: int, H: int, W: int):
 
 
 def _dense_layer_operands(layer):
-    cache = layer._cache()
-    key = ("dense_layer", _bn_id(layer.norm1), _bn_id(layer.norm2))
-    hit = cache.get(key)
-    if hit is None:
+    def build():
         s1, h1 = bn_fold(layer.norm1)
         s2, h2 = bn_fold(layer.norm2)
         w1 = np.asarray(layer.conv1.weight, np.float32)
         d32 = lambda a: _dev(a, torch.float32)
-        hit = (d32(s1), d32(h1), _dev(w1.reshape(w1.shape[0], w1.shape[1]), torch.bfloat16), d32(s2), d32(h2),
-               _dev(inception_fragments(np.asarray(layer.conv2.weight, np.float32)), torch.bfloat16))
-        cache[key] = hit
-    return hit
+        return (d32(s1), d32(h1), _dev(w1.reshape(w1.shape[0], w1.shape[1]), torch.bfloat16), d32(s2), d32(h2),
+                _dev(inception_fragments(np.asarray(layer.conv2.weight, np.float32)), torch.bfloat16))
+    return _prepared(layer, "dense_layer", (layer.norm1, layer.norm2), build)
 
 
 def dense_block(x: Act, block, filled: Optional[int] = None, key=None) -> Act:
@@ -2616,13 +2507,8 @@ def dense_transition(x: Act, trans, next_ld: int = 0, key=None) -> Act:
               and bool(_lib.load().mv_preact_conv1x1_supported(C, N, C, ld, 0, 2, _lib.BF16, _lib.BF16)))
     if not ok:
         return dense_transition_literal(x, trans, key)
-    cache = trans._cache()
-    ck = ("dense_transition", _bn_id(bn))
-    hit = cache.get(ck)
-    if hit is None:
-        s1, h1 = bn_fold(bn)
-        hit = (_dev(s1, torch.float32), _dev(h1, torch.float32), _dev(np.asarray(conv.weight, np.float32).reshape(N, C), torch.bfloat16))
-        cache[ck] = hit
+    hit = _prepared(trans, "dense_transition", (bn,), lambda: tuple(_dev(v, torch.float32) for v in bn_fold(bn)) + (
+        _dev(np.asarray(conv.weight, np.float32).reshape(N, C), torch.bfloat16),))
     y = empty((B, H // 2, W // 2, ld), torch.bfloat16)
     _lib.call("mv_preact_conv1x1_fwd", _ptr(x.t), C, _ptr(hit[0]), _ptr(hit[1]), _ptr(hit[2]), None, None, _ptr(y), ld, 0, B, H, W, C, N, 2,
               _lib.BF16, _lib.BF16, stream_ptr())

@@ -99,12 +99,7 @@ def test_two_restatements_agree():
     np.testing.assert_allclose(n, t, rtol=0, atol=1e-6 * max(1.0, np.abs(t).max()))
 
 
-def _launch_list(monkeypatch, *a, **kw):
-    """tests/test_host.py's recorder; the few-row Linears of the composition path (fc_stream) also get a CPU workspace."""
-    import torch
-    from eqxvision_amd import ops
-    monkeypatch.setattr(ops, "_fc_workspace", lambda nbytes: torch.zeros(nbytes, dtype=torch.uint8))
-    return _host_launch_list(monkeypatch, *a, **kw)
+_launch_list = _host_launch_list        # tests/test_host.py's recorder
 
 
 NEW = ("mv_cnblock_dw_fwd", "mv_ln_mlp_res_fwd", "mv_ln_mlp_stream_res_fwd")

@@ -13,6 +13,7 @@ from eqxvision_amd import nn, ops, utils
 from oracle import np_ops as O
 from oracle import state as S
 from tests import _densenet_ref as R
+from tests._cpu_ops import cpu_ops
 from tests.test_host import _launch_list
 
 NEW = ("mv_preact_conv1x1_fwd", "mv_conv3x3_slice_fwd")
@@ -189,23 +190,6 @@ def test_argument_errors_do_not_need_a_gpu(built_lib):
     assert a(1, 2, 1, 1, 4, 8, 2, 2, 2, 2, 1, None) == -1 and b"empty output" in err()
 
 
-def _cpu_ops(monkeypatch):
-    """Every launch replaced by a recorder and every device allocation by a CPU tensor (tests/test_host.py: _launch_list)."""
-    import torch
-    from eqxvision_amd import _act, _lib
-    calls = []
-    monkeypatch.setattr(_lib, "call", lambda name, *a: calls.append((name, a)) or 0)
-    monkeypatch.setattr(_act, "device", lambda: torch.device("cpu"))
-    monkeypatch.setattr(ops, "device", lambda: torch.device("cpu"))
-    monkeypatch.setattr(ops, "empty", lambda shape, dtype: torch.zeros(shape, dtype=dtype))
-    monkeypatch.setattr(_act, "empty", lambda shape, dtype: torch.zeros(shape, dtype=dtype))
-    monkeypatch.setattr(ops, "stream_ptr", lambda: 0)
-    monkeypatch.setattr(ops, "_dev", lambda a, dt: torch.from_numpy(np.ascontiguousarray(a)).to(dt))
-    monkeypatch.setattr(ops, "_splitk_scratch", lambda *a, **k: None)
-    monkeypatch.setattr(ops, "_fc_workspace", lambda nbytes: torch.zeros(1))
-    return calls
-
-
 def _block_and_transition():
     D = _mod()
     blk = D._DenseBlock(3, 48, bn_size=2, growth_rate=16, drop_rate=0.0, key=eqv.random.PRNGKey(1))
@@ -219,7 +203,7 @@ def test_launch_list_of_a_block_and_a_transition(monkeypatch, built_lib):
     import torch
     from eqxvision_amd import _lib
     from eqxvision_amd._act import Act
-    calls = _cpu_ops(monkeypatch)
+    calls = cpu_ops(monkeypatch)
     blk, tr = _block_and_transition()
     x = Act(torch.zeros(2, 5, 7, 48, dtype=torch.bfloat16), "map", True)
     with eqv.precision("bf16"):
@@ -285,7 +269,7 @@ def test_dropout_key_schedule(monkeypatch):
     handed element l of the split of element p of the split of the sample's key over the len(features) layers."""
     import torch
     D = _mod()
-    calls = _cpu_ops(monkeypatch)
+    calls = cpu_ops(monkeypatch)
     seen = []
 
     def fake_dropout(x, p, key, per_row=False):
@@ -319,7 +303,7 @@ def test_avgpool2d_output_sizes(monkeypatch):
     assert nn.AvgPool2d(3, 2).output_size(7, 8) == (3, 3) and nn.AvgPool2d((2, 3), 1).output_size(5, 5) == (4, 3)
     with pytest.raises(NotImplementedError):
         nn.AvgPool2d(2, 2, padding=1)
-    calls = _cpu_ops(monkeypatch)
+    calls = cpu_ops(monkeypatch)
     y = p(Act(torch.zeros(2, 5, 7, 24, dtype=torch.bfloat16), "map", True))
     assert tuple(y.t.shape) == (2, 2, 3, 24) and calls[-1][0] == "mv_avgpool2d_nhwc_fwd" and calls[-1][1][2:10] == (2, 5, 7, 24, 2, 2, 2, 2)
     with pytest.raises(ValueError):

@@ -14,6 +14,7 @@ from eqxvision_amd import nn, ops, utils
 from oracle import np_ops as O
 from oracle import state as S
 from tests import _googlenet_ref as R
+from tests._cpu_ops import cpu_ops
 from tests.test_host import _launch_list
 
 # read off the reference file (class annotations, in order)
@@ -136,23 +137,12 @@ def test_dropout_key_schedule(monkeypatch):
     """The main Dropout is handed element 13 of the 14-way split of the sample's key (the reference indexes 15, jax clamps), an
     auxiliary head's Dropout element 1 of the 2-way split of elements 7 (aux1) / 11 (aux2)."""
     import torch
-    from eqxvision_amd import _act, _lib
-    from eqxvision_amd._act import Act
     seen = []
 
     def fake_dropout(x, p, key, per_row=False):
         seen.append((p, np.asarray(key, np.uint32).copy()))
         return x
-    names = []
-    monkeypatch.setattr(_lib, "call", lambda name, *a: names.append(name) or 0)
-    monkeypatch.setattr(_act, "device", lambda: torch.device("cpu"))
-    monkeypatch.setattr(ops, "device", lambda: torch.device("cpu"))
-    monkeypatch.setattr(ops, "empty", lambda shape, dtype: torch.zeros(shape, dtype=dtype))
-    monkeypatch.setattr(_act, "empty", lambda shape, dtype: torch.zeros(shape, dtype=dtype))
-    monkeypatch.setattr(ops, "stream_ptr", lambda: 0)
-    monkeypatch.setattr(ops, "_dev", lambda a, dt: torch.from_numpy(np.ascontiguousarray(a)).to(dt))
-    monkeypatch.setattr(ops, "_splitk_scratch", lambda *a, **k: None)
-    monkeypatch.setattr(ops, "_fc_workspace", lambda nbytes: torch.zeros(1))
+    calls = cpu_ops(monkeypatch)
     monkeypatch.setattr(ops, "dropout", fake_dropout)
     monkeypatch.setattr(ops, "bn_train_update", lambda bn, y: (torch.ones(bn.input_size), torch.zeros(bn.input_size)))
     m = eqv.models.googlenet(aux_logits=True, num_classes=8)          # training mode: the Dropouts are live
@@ -169,6 +159,7 @@ def test_dropout_key_schedule(monkeypatch):
         np.testing.assert_array_equal(seen[1][1][b], eqv.random.split(ks[11], 2)[1])
     masks = R.dropout_masks(keys)
     np.testing.assert_array_equal(masks["main"][1], O.jax_bernoulli(eqv.random.split(keys[1], 14)[13], 0.8, (1024,)))
+    names = [c[0] for c in calls]
     assert "mv_copy_rows" in names and "mv_conv3x3_pair_fwd" not in names          # training mode is the literal composition
 
 

@@ -579,20 +579,9 @@ def _launch_list(monkeypatch, factory, sd_fn, B, size=224, flags=()):
     `_supported` entries, which need no device)."""
     import torch
     import eqxvision_amd as eqv
-    from eqxvision_amd import _act, _lib, ops
-    names = []
-
-    def fake_call(name, *a):
-        names.append(name)
-        return 0
-    monkeypatch.setattr(_lib, "call", fake_call)
-    monkeypatch.setattr(_act, "device", lambda: torch.device("cpu"))
-    monkeypatch.setattr(ops, "device", lambda: torch.device("cpu"))
-    monkeypatch.setattr(ops, "empty", lambda shape, dtype: torch.zeros(shape, dtype=dtype))
-    monkeypatch.setattr(_act, "empty", lambda shape, dtype: torch.zeros(shape, dtype=dtype))
-    monkeypatch.setattr(ops, "stream_ptr", lambda: 0)
-    monkeypatch.setattr(ops, "_dev", lambda a, dt: torch.from_numpy(np.ascontiguousarray(a)).to(dt))
-    monkeypatch.setattr(ops, "_splitk_scratch", lambda *a, **k: None)
+    from eqxvision_amd import _lib
+    from tests._cpu_ops import cpu_ops
+    calls = cpu_ops(monkeypatch)
     for f in flags:                                      # (the real entry: _lib.call is the recorder now)
         _lib.load().mv_set_flag(f.encode(), 1)
     try:
@@ -607,7 +596,7 @@ def _launch_list(monkeypatch, factory, sd_fn, B, size=224, flags=()):
     finally:
         for f in flags:
             _lib.load().mv_set_flag(f.encode(), 0)
-    return [n for n in names if n != "mv_set_scratch"]
+    return [n for n, _ in calls if n != "mv_set_scratch"]
 
 
 def test_resnet50_layer1_plan_launch_list(monkeypatch, built_lib):

@@ -4,6 +4,7 @@ import numpy as np
 import pytest
 
 from oracle import state as S
+from tests._cpu_ops import cpu_ops
 from tests.test_host import _launch_list
 
 NEW_ENTRY = "mv_conv1x1_dual_chain_res_fwd"
@@ -69,8 +70,7 @@ def test_rc_operands_from_modules(monkeypatch, bias):
     import torch
     from eqxvision_amd import ops
     from tests._cases import _rc_fragments, _rc_shifts
-    monkeypatch.setattr(ops, "device", lambda: torch.device("cpu"))
-    monkeypatch.setattr(ops, "_dev", lambda a, dt: torch.from_numpy(np.ascontiguousarray(a)).to(dt))
+    cpu_ops(monkeypatch)
     rng = np.random.default_rng(5)
     C, K, N2 = 64, 256, 64
     c30, b30, w30, h30 = _conv_bn(rng, C, K, bias)
@@ -81,12 +81,12 @@ def test_rc_operands_from_modules(monkeypatch, bias):
     ref_f = _rc_fragments(np.concatenate([w30, wd], axis=1), w31, w1n).reshape(K // 32, 16, 64 * 8)
     ref_s = _rc_shifts(h30 + hd, h31, h1n)
 
-    wf, sh, _ = ops.chain_acc_operands(c31, [[(c30, b30), (cd, bd)], [(c31, b31)]], c1n, b1n)
+    wf, sh = ops.chain_acc_operands(c31, [[(c30, b30), (cd, bd)], [(c31, b31)]], c1n, b1n)
     assert wf.dtype == torch.bfloat16 and sh.dtype == torch.int32 and tuple(sh.shape) == (18, 64)
     np.testing.assert_array_equal(wf.view(torch.int16).numpy().reshape(K // 32, 16, 64 * 8), bits(ref_f))
     np.testing.assert_array_equal(sh.numpy().view(np.uint32), ref_s)
 
-    wf0, sh0, _ = ops.chain_acc_operands(c30, [[(c30, b30), (cd, bd)]], c1n, b1n)
+    wf0, sh0 = ops.chain_acc_operands(c30, [[(c30, b30), (cd, bd)]], c1n, b1n)
     assert tuple(sh0.shape) == (10, 64)
     np.testing.assert_array_equal(wf0.view(torch.int16).numpy().reshape(K // 32, 12, 64 * 8),
                                   bits(np.concatenate([ref_f[:, :8], ref_f[:, 12:]], axis=1)))
