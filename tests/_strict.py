@@ -128,23 +128,27 @@ def gemm_ref(x, w, scale, shift, res, act):
 
 
 # ------------------------------------------------------------------------------------------------ instrument 1
-def prove_exact(name, ref, mag, weights, stored=(), hidden=(), out="bf16", min_nonzero=0.10):
+def prove_exact(name, ref, mag, weights, stored=(), hidden=(), out="bf16", min_nonzero=0.10, frac_bits=0, hidden_max=BF16_INT_MAX):
     """The exact-integer preconditions, asserted on the CPU before a launch (the float64 arrays hold integers far below 2^53, so the
     conversion to int64 is itself exact and checked):
       (a) `mag` (sum |x||w| * |scale| + |shift| + |res|) <= 256 for a bf16 output, and every operand in `stored` / intermediate in
           `hidden` is an integer of magnitude <= 256; mag < 2^24 for the fp32 accumulators;
       (b) every reduction index of every matrix in `weights` ((rows, reduction) layout) has a non-zero weight in some row, and every
           row has a non-zero weight;
-      (c) fewer than 90 % of the reference outputs are zero."""
+      (c) fewer than 90 % of the reference outputs are zero.
+    `frac_bits` = f: "integer" reads "multiple of 2^-f" and the limits apply to the value times 2^f (dyadic operands: an average over
+    4 or 16 pixels, bilinear taps at ratio 2); `hidden_max` replaces the bf16 limit of `stored` / `hidden` where nothing is stored
+    as bf16 (the fp32 gradient path: tests/_rule_grad.py)."""
     for what, a in [("ref", ref), ("mag", mag)] + [(f"stored[{i}]", s) for i, s in enumerate(stored)] + \
                    [(f"hidden[{i}]", h) for i, h in enumerate(hidden)]:
-        a = np.asarray(a, F64)
+        a = np.ldexp(np.asarray(a, F64), frac_bits)
         ai = np.rint(a).astype(np.int64)
         assert np.array_equal(ai.astype(F64), a), f"{name}: {what} is not integer-valued"
         top = int(np.abs(ai).max()) if ai.size else 0
         assert top < ACC_INT_MAX, f"{name}: {what} reaches {top} >= 2^24 (fp32 accumulator not exact)"
         if out == "bf16" or what not in ("ref", "mag"):
-            assert top <= BF16_INT_MAX, f"{name}: {what} reaches {top} > 256 (not exact in bf16)"
+            lim = BF16_INT_MAX if what in ("ref", "mag") else hidden_max
+            assert top <= lim, f"{name}: {what} reaches {top} > {lim} (not exact in bf16)"
     for i, w in enumerate(weights):
         w2 = np.asarray(w).reshape(w.shape[0], -1) != 0
         assert w2.any(axis=0).all(), f"{name}: weights[{i}] leaves {int((~w2.any(axis=0)).sum())} reduction indices unused"
