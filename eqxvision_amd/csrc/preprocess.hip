@@ -3,6 +3,9 @@
 // The filter lives in two tap tables the host builds in float64 (eqxvision_amd/preprocess.py: axis_table); the kernel only
 // applies them, so the same entry serves the antialiased ImageNet preset and plain two-tap up-sampling.  HBM-bound gather, no
 // matrix work: every input byte a tile needs is read once into LDS, both passes run out of LDS, every output is stored once.
+// Two entries share the tile body: one image size per launch (mv_preprocess_u8_fwd), or one record per image for a packed batch
+// of any sizes (mv_preprocess_u8_ragged_fwd).  A launch has ONE tile and ONE LDS size; the ragged entry sizes them for the largest
+// spans and pitches of its batch, so one steeply down-sampled image lowers the occupancy of the whole launch (accepted).
 #include "common.h"
 
 namespace mv {
@@ -24,6 +27,15 @@ struct PrepP {
     int rows_cap, cols_cap, pitch; // staged input rectangle the LDS was sized for; bytes per staged line (multiple of 16)
 };
 
+// mv_preprocess_u8_ragged_fwd: one record per image (blockIdx.z) instead of one geometry per launch.  In `p`, x is the packed
+// buffer, tab_h the packed table buffer, mh / mw / rows_cap / cols_cap / pitch the largest any image of the batch needs (what the
+// LDS was sized for); Hin, Win and tab_w are not used.
+struct PrepRaggedP {
+    PrepP p;
+    const mv_preprocess_image* rec;
+    long long x_bytes, tab_words;
+};
+
 __device__ __forceinline__ int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
 
 // One workgroup = one TH x TW tile of the cropped output of one image, all three channels.
@@ -37,11 +49,12 @@ __device__ __forceinline__ int clampi(int v, int lo, int hi) { return v < lo ? l
 // >= 0 and <= the result, so the rounding error is bounded by (taps + 1) 2^-24 of the result itself whatever the image; and a
 // constant neighbourhood comes out as that constant exactly, however the fp32 weights happen to round (a flat image gives
 // fma(v, a, b) bit for bit, borders included).  Nothing is shared between workgroups: two runs give the same bits.
+// `img`: the first byte of image `b`, whose geometry and tables are p's; the output goes to image b of p.y.
 template <bool CHW_IN, bool NHWC_OUT, bool BF16_OUT>
-__global__ __launch_bounds__(256) void preprocess_u8_kernel(const PrepP p) {
+__device__ __forceinline__ void preprocess_tile(const PrepP& p, const uint8_t* img, const int b) {
     extern __shared__ uint4 smem4[];
     const int tid = threadIdx.x;
-    const int y0 = blockIdx.y * p.TH, x0 = blockIdx.x * p.TW, b = blockIdx.z;
+    const int y0 = blockIdx.y * p.TH, x0 = blockIdx.x * p.TW;
     const int th = min(p.TH, p.Hout - y0), tw = min(p.TW, p.Wout - x0);
     constexpr int PIX = CHW_IN ? 1 : 3;                      // bytes from one pixel of a channel to the next
     const int lines_cap = CHW_IN ? 3 * p.rows_cap : p.rows_cap;
@@ -98,7 +111,6 @@ __global__ __launch_bounds__(256) void preprocess_u8_kernel(const PrepP p) {
 
     // 2. input rectangle
     const size_t img_bytes = (size_t)p.Hin * p.Win * 3;
-    const uint8_t* img = p.x + (size_t)b * img_bytes;
     const uintptr_t img_lo = (uintptr_t)img, img_hi = img_lo + img_bytes;
     const int lines = CHW_IN ? 3 * nrows : nrows;
     const int len = ncols * PIX;
@@ -171,6 +183,36 @@ __global__ __launch_bounds__(256) void preprocess_u8_kernel(const PrepP p) {
     }
 }
 
+template <bool CHW_IN, bool NHWC_OUT, bool BF16_OUT>
+__global__ __launch_bounds__(256) void preprocess_u8_kernel(const PrepP p) {
+    const int b = blockIdx.z;
+    preprocess_tile<CHW_IN, NHWC_OUT, BF16_OUT>(p, p.x + (size_t)b * ((size_t)p.Hin * p.Win * 3), b);
+}
+
+// The record is device data like the tables: the host validated its own copy, the kernel trusts neither.  A record whose image
+// or tables would leave their buffers, or whose table pitch exceeds what the LDS was sized for, forms no address at all: its
+// tiles store nothing and set bit 2.  (Uniform over the workgroup, before any barrier.)  A record that passes describes memory
+// inside the two buffers, and the tile body cuts everything else -- rectangle, taps -- as it does for the tables.
+template <bool CHW_IN, bool NHWC_OUT, bool BF16_OUT>
+__global__ __launch_bounds__(256) void preprocess_u8_ragged_kernel(const PrepRaggedP r) {
+    const int b = blockIdx.z;
+    const mv_preprocess_image g = r.rec[b];
+    PrepP p = r.p;
+    const long long img_bytes = (long long)g.Hin * g.Win * 3;
+    const bool ok = g.Hin >= 1 && g.Win >= 1 && img_bytes < (1LL << 31) && g.offset >= 0 && g.offset <= r.x_bytes - img_bytes &&
+                    g.mh >= 1 && g.mh <= p.mh && g.mw >= 1 && g.mw <= p.mw && g.tab_h >= 0 && g.tab_w >= 0 &&
+                    (long long)g.tab_h + (long long)p.Hout * (2 + g.mh) <= r.tab_words &&
+                    (long long)g.tab_w + (long long)p.Wout * (2 + g.mw) <= r.tab_words;
+    if (!ok) {
+        if (threadIdx.x == 0) atomicOr(p.status, 4u);
+        return;
+    }
+    p.Hin = g.Hin; p.Win = g.Win; p.mh = g.mh; p.mw = g.mw;
+    p.tab_w = p.tab_h + g.tab_w;
+    p.tab_h = p.tab_h + g.tab_h;
+    preprocess_tile<CHW_IN, NHWC_OUT, BF16_OUT>(p, p.x + g.offset, b);
+}
+
 // input samples a run of T outputs can touch on one axis: (T - 1) * ratio between the first and the last centre, the support on
 // both sides, one for the inclusive end, one for rounding
 int span_cap(int T, int in, int out_full) {
@@ -191,6 +233,38 @@ size_t lds_bytes(int TH, int TW, int rows_cap, int cols_cap, int in_chw, int mh,
     const size_t lines = in_chw ? 3 * (size_t)rows_cap : rows_cap;
     return lines * *pitch + (size_t)rows_cap * 3 * TW * 4 + (size_t)(2 * TH + 2 * TW + TH * mh + TW * mw) * 4;
 }
+
+// Tile: the largest of these whose staged rectangle fits 64 KiB of LDS.  The ImageNet preset on a 500 x 375 image (ratio
+// 1.46) takes 32 x 32: 51 input rows x 51 columns staged = 51 x 176 B of uint8 + 51 x 3 x 32 fp32 of horizontal sums + 1.3 KiB
+// of tables = 29.9 KiB -> 5 workgroups of 4 waves per CU = 5 waves per SIMD, 49 tiles per image.  Smaller tiles keep steep
+// down-sampling (up to 11.5x, 24 taps) inside the budget; their stores are shorter runs, which such a reduction can afford.
+// caps(TH, TW, &rows, &cols): the input rectangle a TH x TW tile can need.  p.mh / p.mw are read; TH, TW, rows_cap, cols_cap and
+// pitch of the chosen tile (or of the smallest, if none fits) are left in p, its LDS size in *lds.
+template <class F> bool pick_tile(PrepP& p, int in_chw, size_t* lds, F&& caps) {
+    static const int tiles[][2] = {{32, 32}, {16, 32}, {16, 16}, {8, 16}, {4, 8}};
+    for (const auto& t : tiles) {
+        p.TH = t[0];
+        p.TW = t[1];
+        caps(p.TH, p.TW, &p.rows_cap, &p.cols_cap);
+        *lds = lds_bytes(p.TH, p.TW, p.rows_cap, p.cols_cap, in_chw, p.mh, p.mw, &p.pitch);
+        if (*lds <= 64 * 1024) return true;
+    }
+    return false;
+}
+
+// launches KERNEL<in_chw, out_nhwc, out_dtype == MV_BF16> with ARG on (grid, 256 threads, lds, st) of the calling entry
+#define PREPROCESS_GO(KERNEL, ARG, CHW, NHWC, BF) hipLaunchKernelGGL((KERNEL<CHW, NHWC, BF>), grid, dim3(256), lds, st, ARG)
+#define PREPROCESS_LAUNCH(KERNEL, ARG)                                                                                        \
+    do {                                                                                                                      \
+        const bool bf = out_dtype == MV_BF16;                                                                                 \
+        if (in_chw) {                                                                                                         \
+            if (out_nhwc) { if (bf) PREPROCESS_GO(KERNEL, ARG, true, true, true); else PREPROCESS_GO(KERNEL, ARG, true, true, false); }      \
+            else { if (bf) PREPROCESS_GO(KERNEL, ARG, true, false, true); else PREPROCESS_GO(KERNEL, ARG, true, false, false); }             \
+        } else {                                                                                                              \
+            if (out_nhwc) { if (bf) PREPROCESS_GO(KERNEL, ARG, false, true, true); else PREPROCESS_GO(KERNEL, ARG, false, true, false); }    \
+            else { if (bf) PREPROCESS_GO(KERNEL, ARG, false, false, true); else PREPROCESS_GO(KERNEL, ARG, false, false, false); }           \
+        }                                                                                                                     \
+    } while (0)
 
 }  // namespace
 
@@ -232,45 +306,100 @@ int mv_preprocess_u8_fwd(const void* x, void* y, const void* tab_h, const void* 
     unsigned* status = device_status_word();
     MV_CHECK_ARG(status != nullptr, "preprocess_u8: the device status word is not available");
 
-    // Tile: the largest of these whose staged rectangle fits 64 KiB of LDS.  The ImageNet preset on a 500 x 375 image (ratio
-    // 1.46) takes 32 x 32: 51 input rows x 51 columns staged = 51 x 176 B of uint8 + 51 x 3 x 32 fp32 of horizontal sums + 1.3 KiB
-    // of tables = 29.9 KiB -> 5 workgroups of 4 waves per CU = 5 waves per SIMD, 49 tiles per image.  Smaller tiles keep steep
-    // down-sampling (up to 11.5x, 24 taps) inside the budget; their stores are shorter runs, which such a reduction can afford.
-    static const int tiles[][2] = {{32, 32}, {16, 32}, {16, 16}, {8, 16}, {4, 8}};
     PrepP p;
+    p.x = (const uint8_t*)x; p.y = y; p.tab_h = (const int*)tab_h; p.tab_w = (const int*)tab_w; p.a = a; p.b = b; p.status = status;
+    p.Hin = Hin; p.Win = Win; p.Hout = Hout; p.Wout = Wout; p.mh = taps_h; p.mw = taps_w;
     size_t lds = 0;
-    bool fits = false;
-    for (const auto& t : tiles) {
-        p.TH = t[0];
-        p.TW = t[1];
-        p.rows_cap = span_cap(p.TH, Hin, Hr);
-        p.cols_cap = span_cap(p.TW, Win, Wr);
-        lds = lds_bytes(p.TH, p.TW, p.rows_cap, p.cols_cap, in_chw, taps_h, taps_w, &p.pitch);
-        if (lds <= 64 * 1024) {
-            fits = true;
-            break;
-        }
-    }
-    if (!fits) {
+    if (!pick_tile(p, in_chw, &lds, [&](int TH, int TW, int* rows, int* cols) {
+            *rows = span_cap(TH, Hin, Hr);
+            *cols = span_cap(TW, Win, Wr);
+        })) {
         set_error("preprocess_u8: %dx%d -> %dx%d does not fit the LDS tile (%zu bytes for the smallest tile)", Hin, Win, Hr, Wr, lds);
         return MV_E_UNSUPPORTED;
     }
-    p.x = (const uint8_t*)x; p.y = y; p.tab_h = (const int*)tab_h; p.tab_w = (const int*)tab_w; p.a = a; p.b = b; p.status = status;
-    p.Hin = Hin; p.Win = Win; p.Hout = Hout; p.Wout = Wout; p.mh = taps_h; p.mw = taps_w;
     const dim3 grid((Wout + p.TW - 1) / p.TW, (Hout + p.TH - 1) / p.TH, B);
     MV_CHECK_ARG(grid.y <= 65535, "preprocess_u8: %d output rows are too many tiles", Hout);
     hipStream_t st = (hipStream_t)stream;
     set_kernel_name("preprocess_u8");
-#define GO(CHW, NHWC, BF) hipLaunchKernelGGL((preprocess_u8_kernel<CHW, NHWC, BF>), grid, dim3(256), lds, st, p)
-    const bool bf = out_dtype == MV_BF16;
-    if (in_chw) {
-        if (out_nhwc) { if (bf) GO(true, true, true); else GO(true, true, false); }
-        else { if (bf) GO(true, false, true); else GO(true, false, false); }
-    } else {
-        if (out_nhwc) { if (bf) GO(false, true, true); else GO(false, true, false); }
-        else { if (bf) GO(false, false, true); else GO(false, false, false); }
+    PREPROCESS_LAUNCH(preprocess_u8_kernel, p);
+    MV_LAUNCH_CHECK();
+    return MV_OK;
+}
+
+int mv_preprocess_u8_ragged_fwd(const void* x, int64_t x_bytes, void* y, const mv_preprocess_image* rec_host,
+                                const mv_preprocess_image* rec_dev, const void* tab, int64_t tab_words, const float* a,
+                                const float* b, int B, int Hout, int Wout, int in_chw, int out_dtype, int out_nhwc,
+                                mv_stream_t stream) {
+    MV_CHECK_ARG(B > 0 && Hout > 0 && Wout > 0 && x_bytes > 0 && tab_words > 0, "preprocess_u8_ragged: bad sizes");
+    MV_CHECK_ARG(out_dtype == MV_F32 || out_dtype == MV_BF16, "preprocess_u8_ragged: out_dtype must be MV_F32 or MV_BF16");
+    MV_CHECK_ARG(B <= 65535, "preprocess_u8_ragged: batch %d too large", B);
+    if (!x || !y || !rec_host || !rec_dev || !tab || !a || !b) {
+        set_error("preprocess_u8_ragged: null buffer");
+        return MV_E_UNSUPPORTED;
     }
-#undef GO
+    int mh = 0, mw = 0;
+    for (int i = 0; i < B; ++i) {
+        const mv_preprocess_image& g = rec_host[i];
+        MV_CHECK_ARG(g.Hin > 0 && g.Win > 0 && g.Hr > 0 && g.Wr > 0 && g.mh > 0 && g.mw > 0, "preprocess_u8_ragged: image %d: bad sizes", i);
+        const long long img_bytes = (long long)g.Hin * g.Win * 3;
+        MV_CHECK_ARG(img_bytes < (1LL << 31), "preprocess_u8_ragged: image %d: %dx%d too large", i, g.Hin, g.Win);
+        MV_CHECK_ARG(g.offset >= 0 && g.offset <= x_bytes - img_bytes,
+                     "preprocess_u8_ragged: image %d: %lld bytes at offset %lld do not lie inside the buffer of %lld bytes", i, img_bytes,
+                     (long long)g.offset, (long long)x_bytes);
+        if (g.top < 0 || g.left < 0 || (long long)g.top + Hout > g.Hr || (long long)g.left + Wout > g.Wr) {
+            set_error("preprocess_u8_ragged: image %d: crop %dx%d at (%d, %d) does not lie inside the resized image %dx%d", i, Hout, Wout,
+                      g.top, g.left, g.Hr, g.Wr);
+            return MV_E_UNSUPPORTED;
+        }
+        const int need_h = taps_needed(g.Hin, g.Hr), need_w = taps_needed(g.Win, g.Wr);
+        if (g.mh > MV_PREPROCESS_MAX_TAPS || g.mw > MV_PREPROCESS_MAX_TAPS || need_h > MV_PREPROCESS_MAX_TAPS ||
+            need_w > MV_PREPROCESS_MAX_TAPS) {
+            set_error("preprocess_u8_ragged: image %d: %dx%d -> %dx%d needs up to %d x %d taps (tables of %d x %d); at most %d per axis "
+                      "(down-sampling by up to %.1f)", i, g.Hin, g.Win, g.Hr, g.Wr, need_h, need_w, g.mh, g.mw, MV_PREPROCESS_MAX_TAPS,
+                      (MV_PREPROCESS_MAX_TAPS - 1) / 2.0);
+            return MV_E_UNSUPPORTED;
+        }
+        MV_CHECK_ARG(g.tab_h >= 0 && g.tab_w >= 0 && (long long)g.tab_h + (long long)Hout * (2 + g.mh) <= tab_words &&
+                         (long long)g.tab_w + (long long)Wout * (2 + g.mw) <= tab_words,
+                     "preprocess_u8_ragged: image %d: tables at words %d and %d do not lie inside the table buffer of %lld words", i,
+                     g.tab_h, g.tab_w, (long long)tab_words);
+        mh = g.mh > mh ? g.mh : mh;
+        mw = g.mw > mw ? g.mw : mw;
+    }
+    const size_t out_bytes = (size_t)B * 3 * Hout * Wout * dsize(out_dtype);
+    const uintptr_t xa = (uintptr_t)x, ya = (uintptr_t)y;
+    if (xa < ya + out_bytes && ya < xa + (size_t)x_bytes) {
+        set_error("preprocess_u8_ragged: input and output overlap");
+        return MV_E_UNSUPPORTED;
+    }
+    unsigned* status = device_status_word();
+    MV_CHECK_ARG(status != nullptr, "preprocess_u8_ragged: the device status word is not available");
+
+    // One tile and one LDS size per launch: the rectangle and the table pitches are the largest any image of the batch needs, per
+    // axis, so one steeply down-sampled image shrinks the tile (and the occupancy) of the whole launch.  Accepted: the result of an
+    // image does not depend on the tile it was computed in.
+    PrepRaggedP r;
+    PrepP& p = r.p;
+    p.x = (const uint8_t*)x; p.y = y; p.tab_h = (const int*)tab; p.tab_w = nullptr; p.a = a; p.b = b; p.status = status;
+    p.Hin = 0; p.Win = 0; p.Hout = Hout; p.Wout = Wout; p.mh = mh; p.mw = mw;
+    r.rec = rec_dev; r.x_bytes = x_bytes; r.tab_words = tab_words;
+    size_t lds = 0;
+    if (!pick_tile(p, in_chw, &lds, [&](int TH, int TW, int* rows, int* cols) {
+            *rows = *cols = 0;
+            for (int i = 0; i < B; ++i) {
+                const mv_preprocess_image& g = rec_host[i];
+                *rows = std::max(*rows, span_cap(TH, g.Hin, g.Hr));
+                *cols = std::max(*cols, span_cap(TW, g.Win, g.Wr));
+            }
+        })) {
+        set_error("preprocess_u8_ragged: the batch does not fit the LDS tile (%zu bytes for the smallest tile)", lds);
+        return MV_E_UNSUPPORTED;
+    }
+    const dim3 grid((Wout + p.TW - 1) / p.TW, (Hout + p.TH - 1) / p.TH, B);
+    MV_CHECK_ARG(grid.y <= 65535, "preprocess_u8_ragged: %d output rows are too many tiles", Hout);
+    hipStream_t st = (hipStream_t)stream;
+    set_kernel_name("preprocess_u8_ragged");
+    PREPROCESS_LAUNCH(preprocess_u8_ragged_kernel, r);
     MV_LAUNCH_CHECK();
     return MV_OK;
 }

@@ -9,11 +9,19 @@ and the crop offsets follow torchvision's rounding, the filter is `torch.nn.func
 normalised over the taps inside the image).  The host builds the filter as one tap table per axis in float64, rounds the weights
 to fp32, uploads them once per geometry and keeps them; the kernel only applies them.
 
+    x = eqv.preprocess.imagenet_eval([img0, img1, ...])    # images of different sizes, still one launch
+
+A list of images takes `mv_preprocess_u8_ragged_fwd`: the images packed tightly into one uint8 buffer, every table into one int32
+buffer, one record per image (`RECORD`) that says where they lie.  The geometry belongs to that call, so nothing is kept on the
+device and only the per-axis tables are cached, on the host and bounded (`AXIS_CACHE`).
+
 Outputs: NCHW in fp32 or bf16 are what the models' entry kernels read without a conversion launch (`_act.wrap` takes a [B, 3, H, W]
 tensor as the image batch; the entry convolutions read fp32 or bf16).  The models have no NHWC entry, so `imagenet_eval` does not
 offer one; `resize_crop_normalize(layout="nhwc")` returns a plain tensor for other consumers.
 """
 from __future__ import annotations
+
+import functools
 
 import numpy as np
 import torch
@@ -83,23 +91,27 @@ _tables = {}        # (device, Hin, Win, Hr, Wr, top, left, Hout, Wout) -> (tab_
 _affines = {}       # (device, mean, std) -> (a, b) on the device
 
 
-def _geometry(hin, win, resized_hw, crop_box):
+def _geometry(hin, win, resized_hw, crop_box, who="preprocess"):
     hr, wr = int(resized_hw[0]), int(resized_hw[1])
     top, left, hout, wout = (int(v) for v in crop_box)
     if hr < 1 or wr < 1 or hout < 1 or wout < 1:
-        raise ValueError(f"preprocess: resized size {(hr, wr)} and crop {(hout, wout)} must be positive")
+        raise ValueError(f"{who}: resized size {(hr, wr)} and crop {(hout, wout)} must be positive")
     if top < 0 or left < 0 or top + hout > hr or left + wout > wr:
-        raise ValueError(f"preprocess: crop {hout}x{wout} at ({top}, {left}) does not lie inside the resized image {hr}x{wr}")
+        raise ValueError(f"{who}: crop {hout}x{wout} at ({top}, {left}) does not lie inside the resized image {hr}x{wr}")
     return hr, wr, top, left, hout, wout
+
+
+def _check_taps(hin, win, hr, wr, who="preprocess"):
+    for n_in, n_out in ((hin, hr), (win, wr)):               # refused on the host, before the device is touched
+        need = min(n_in, int(2.0 * max(1.0, n_in / n_out) + 1.0))
+        if need > MAX_TAPS:
+            raise ValueError(f"{who}: {hin}x{win} -> {hr}x{wr} needs {need} filter taps on an axis, at most {MAX_TAPS} "
+                             f"(down-sampling by up to {(MAX_TAPS - 1) / 2})")
 
 
 def _device_tables(hin, win, hr, wr, top, left, hout, wout):
     geo = (hin, win, hr, wr, top, left, hout, wout)
-    for n_in, n_out in ((hin, hr), (win, wr)):               # refused on the host, before the device is touched
-        need = min(n_in, int(2.0 * max(1.0, n_in / n_out) + 1.0))
-        if need > MAX_TAPS:
-            raise ValueError(f"preprocess: {hin}x{win} -> {hr}x{wr} needs {need} filter taps on an axis, at most {MAX_TAPS} "
-                             f"(down-sampling by up to {(MAX_TAPS - 1) / 2})")
+    _check_taps(hin, win, hr, wr)
     key = (str(device()),) + geo
     hit = _tables.get(key)
     if hit is None:
@@ -119,15 +131,15 @@ def _device_affine(mean, std):
     return hit
 
 
-def _check_input(images_u8, channels_last):
+def _check_input(images_u8, channels_last, who="preprocess"):
     """-> (array, batched, chw, Hin, Win); raises ValueError before anything touches the device."""
     x = images_u8
     if not isinstance(x, (np.ndarray, torch.Tensor)):
-        raise ValueError(f"preprocess: images must be a uint8 numpy array or torch tensor, got {type(x).__name__}")
+        raise ValueError(f"{who}: images must be a uint8 numpy array or torch tensor, got {type(x).__name__}")
     if x.dtype != (torch.uint8 if isinstance(x, torch.Tensor) else np.uint8):
-        raise ValueError(f"preprocess: images must be uint8 (decoded pixels 0..255), got {x.dtype}")
+        raise ValueError(f"{who}: images must be uint8 (decoded pixels 0..255), got {x.dtype}")
     if x.ndim not in (3, 4):
-        raise ValueError(f"preprocess: images must be [H, W, 3] / [3, H, W] or a batch of them, got shape {tuple(x.shape)}")
+        raise ValueError(f"{who}: images must be [H, W, 3] / [3, H, W] or a batch of them, got shape {tuple(x.shape)}")
     batched = x.ndim == 4
     s = tuple(int(v) for v in x.shape[-3:])
     if channels_last is None:
@@ -136,15 +148,151 @@ def _check_input(images_u8, channels_last):
         elif s[0] == 3:
             chw = True
         else:
-            raise ValueError(f"preprocess: images must have 3 channels first or last, got shape {tuple(x.shape)}")
+            raise ValueError(f"{who}: images must have 3 channels first or last, got shape {tuple(x.shape)}")
     else:
         chw = not channels_last
         if s[0 if chw else 2] != 3:
-            raise ValueError(f"preprocess: images must have 3 channels, got shape {tuple(x.shape)} with channels_last={channels_last}")
+            raise ValueError(f"{who}: images must have 3 channels, got shape {tuple(x.shape)} with channels_last={channels_last}")
     hin, win = (s[1], s[2]) if chw else (s[0], s[1])
     if hin < 1 or win < 1:
-        raise ValueError(f"preprocess: empty image, shape {tuple(x.shape)}")
+        raise ValueError(f"{who}: empty image, shape {tuple(x.shape)}")
     return x, batched, chw, hin, win
+
+
+def _check_output(dtype, layout):
+    if dtype not in DT:
+        raise ValueError(f"preprocess: dtype must be 'fp32' or 'bf16', got {dtype!r}")
+    if layout not in ("nchw", "nhwc"):
+        raise ValueError(f"preprocess: layout must be 'nchw' or 'nhwc', got {layout!r}")
+
+
+# ---- batches of differently sized images: a list of images -> mv_preprocess_u8_ragged_fwd, one launch ----------------------------
+
+# `mv_preprocess_image` of include/eqxvision_amd.h, 48 bytes
+RECORD = np.dtype([("offset", "<i8"), ("Hin", "<i4"), ("Win", "<i4"), ("Hr", "<i4"), ("Wr", "<i4"), ("top", "<i4"), ("left", "<i4"),
+                   ("tab_h", "<i4"), ("tab_w", "<i4"), ("mh", "<i4"), ("mw", "<i4")])
+AXIS_CACHE = 4096      # tables kept on the HOST, per axis; a ragged call keeps nothing on the device
+
+
+@functools.lru_cache(maxsize=AXIS_CACHE)
+def _axis_words(n_in, n_out, start, count):
+    """(`pack_table(*axis_table(...))`, read-only; its pitch).  ImageNet's validation set has a few hundred distinct (size, resized
+    size) pairs per axis, so a warm cache leaves a call the concatenation only."""
+    first, taps, w = axis_table(n_in, n_out, start, count)
+    words = pack_table(first, taps, w)
+    words.setflags(write=False)
+    return words, w.shape[1]
+
+
+def _is_device_tensor(im):
+    return isinstance(im, torch.Tensor) and im.device.type != "cpu"
+
+
+def _check_list(images, channels_last):
+    """-> (chw, [(Hin, Win), ...]); every refusal names the image."""
+    if len(images) == 0:
+        raise ValueError("preprocess: the list of images is empty")
+    for i, im in enumerate(images):
+        _check_input(im, channels_last, f"preprocess: image {i}")
+        if im.ndim != 3:
+            raise ValueError(f"preprocess: image {i}: a list holds single images [H, W, 3] / [3, H, W], got shape {tuple(im.shape)}")
+    if channels_last is None:                                # read off the images that leave no doubt; [3, W, 3] follows them
+        chw, decided_by = False, None
+        for i, im in enumerate(images):
+            first, last = int(im.shape[0]) == 3, int(im.shape[2]) == 3
+            if first != last:
+                if decided_by is not None and chw != first:
+                    raise ValueError(f"preprocess: image {i}: mixed layouts, shape {tuple(im.shape)} has its channels "
+                                     f"{'first' if first else 'last'} and image {decided_by}, shape {tuple(images[decided_by].shape)}, "
+                                     "has not; give every image of a list in the same layout")
+                if decided_by is None:
+                    chw, decided_by = first, i
+    else:
+        chw = not channels_last
+    sizes = []
+    for i, im in enumerate(images):
+        s = tuple(int(v) for v in im.shape)
+        if s[0 if chw else 2] != 3:
+            raise ValueError(f"preprocess: image {i}: mixed layouts, shape {s} has no 3 channels "
+                             f"{'first' if chw else 'last'} like the rest of the list")
+        sizes.append((s[1], s[2]) if chw else (s[0], s[1]))
+    return chw, sizes
+
+
+def _per_image(value, B, width, what):
+    """`value`: one geometry (`width` numbers) for all images or a list of B of them -> a list of B."""
+    if len(value) == width and all(isinstance(v, (int, np.integer)) for v in value):
+        return [value] * B
+    if len(value) != B:
+        raise ValueError(f"preprocess: {what} must be {width} numbers or one such entry per image ({B}), got {len(value)} entries")
+    return list(value)
+
+
+def ragged_plan(sizes, resized_hw, crop_box):
+    """Host half of a ragged call, no device involved.  `sizes`: [(Hin, Win)] per image; `resized_hw`, `crop_box`: one geometry or
+    one per image.  Returns (records, tables, (Hout, Wout)): `records` a RECORD array [B] for tightly packed images in list
+    order, `tables` the int32 buffer its tab_h / tab_w offsets point into (each image's row table, then its column table)."""
+    B = len(sizes)
+    resized, boxes = _per_image(resized_hw, B, 2, "resized_hw"), _per_image(crop_box, B, 4, "crop_box")
+    rec = np.zeros(B, RECORD)
+    parts, offset, word, crop = [], 0, 0, None
+    for i, (hin, win) in enumerate(sizes):
+        who = f"preprocess: image {i}"
+        hr, wr, top, left, hout, wout = _geometry(hin, win, resized[i], boxes[i], who)
+        crop = crop or (hout, wout)
+        if (hout, wout) != crop:
+            raise ValueError(f"{who}: mixed crop sizes, {hout}x{wout} here and {crop[0]}x{crop[1]} for image 0; the images of one "
+                             "call share the output size")
+        _check_taps(hin, win, hr, wr, who)
+        (th, mh), (tw, mw) = _axis_words(hin, hr, top, hout), _axis_words(win, wr, left, wout)
+        rec[i] = (offset, hin, win, hr, wr, top, left, word, word + th.size, mh, mw)
+        parts += [th, tw]
+        offset += hin * win * 3
+        word += th.size + tw.size
+    if word >= 2 ** 31:
+        raise ValueError(f"preprocess: the tables of {B} images take {word} words, more than an int32 offset reaches")
+    return rec, np.concatenate(parts), crop
+
+
+def pack_images(images) -> torch.Tensor:
+    """The images as one tightly packed uint8 buffer on the device, in list order.  Host images are concatenated in one staging
+    array and cross in one copy; device images are joined by one device concatenation."""
+    host = [i for i, im in enumerate(images) if not _is_device_tensor(im)]
+    up = None
+    if host:
+        flat = [np.ascontiguousarray(images[i].numpy() if isinstance(images[i], torch.Tensor) else images[i]).reshape(-1) for i in host]
+        up = torch.from_numpy(np.concatenate(flat)).to(device(), non_blocking=True)
+        if len(host) == len(images):
+            return up
+    pieces, at = [], 0
+    for im in images:
+        if _is_device_tensor(im):
+            pieces.append(im.to(device()).reshape(-1))
+        else:
+            n = int(np.prod(im.shape))
+            pieces.append(up[at:at + n])
+            at += n
+    return torch.cat(pieces)
+
+
+def _ragged(images, resized_hw, crop_box, mean, std, dtype, layout, channels_last):
+    if getattr(_act_tls, "keep", None) is not None:
+        raise ValueError("preprocess: a list of differently sized images cannot be recorded by filter_jit: its sizes and offsets "
+                         "belong to this one call, and a replay would apply them to other images; preprocess outside the "
+                         "recorded function, or give one array of equally sized images")
+    chw, sizes = _check_list(images, channels_last)
+    _check_output(dtype, layout)
+    rec, tables, (hout, wout) = ragged_plan(sizes, resized_hw, crop_box)
+    affine(mean, std)                                        # validates before the device is touched
+    a, b = _device_affine(mean, std)
+    x = pack_images(images)
+    tab, rec_dev = torch.from_numpy(tables).to(device()), torch.from_numpy(rec.view(np.uint8)).to(device())
+    B = len(images)
+    y = empty((B, 3, hout, wout) if layout == "nchw" else (B, hout, wout, 3), TORCH_DT[dtype])
+    _lib.call("mv_preprocess_u8_ragged_fwd", x.data_ptr(), x.numel(), y.data_ptr(), rec.ctypes.data, rec_dev.data_ptr(),
+              tab.data_ptr(), tab.numel(), a.data_ptr(), b.data_ptr(), B, hout, wout, int(chw), DT[dtype], int(layout == "nhwc"),
+              stream_ptr())
+    return y
 
 
 def resize_crop_normalize(images_u8, resized_hw, crop_box, mean=IMAGENET_MEAN, std=IMAGENET_STD, dtype="fp32", layout="nchw",
@@ -153,12 +301,15 @@ def resize_crop_normalize(images_u8, resized_hw, crop_box, mean=IMAGENET_MEAN, s
     image, return (x / 255 - mean) / std as a device tensor [B, 3, height, width] (`layout="nchw"`) or [B, height, width, 3], fp32
     or bf16.  `images_u8`: [B, H, W, 3] or [B, 3, H, W] (or one image without the batch axis), numpy or torch, host or device; the
     layout is read off which axis is 3 unless `channels_last` says so.  One launch on the current stream; recorded by `filter_jit`
-    like any other (a device-resident input is then read in place, a host array is staged as uint8 once per call)."""
+    like any other (a device-resident input is then read in place, a host array is staged as uint8 once per call).
+    A list or tuple of images [H_i, W_i, 3] (or all [3, H_i, W_i]) of DIFFERENT sizes is one launch too: `resized_hw` and
+    `crop_box` are then one geometry for all images or lists with one entry per image, the crop's height and width the same for
+    all.  The images are packed tightly into one buffer (one upload for host images), tables and records are built per call from
+    a bounded host-side cache; such a call cannot be recorded by `filter_jit`."""
+    if isinstance(images_u8, (list, tuple)):
+        return _ragged(images_u8, resized_hw, crop_box, mean, std, dtype, layout, channels_last)
     x, batched, chw, hin, win = _check_input(images_u8, channels_last)
-    if dtype not in DT:
-        raise ValueError(f"preprocess: dtype must be 'fp32' or 'bf16', got {dtype!r}")
-    if layout not in ("nchw", "nhwc"):
-        raise ValueError(f"preprocess: layout must be 'nchw' or 'nhwc', got {layout!r}")
+    _check_output(dtype, layout)
     hr, wr, top, left, hout, wout = _geometry(hin, win, resized_hw, crop_box)
     affine(mean, std)                                        # validates before the device is touched
     tab_h, tab_w, mh, mw = _device_tables(hin, win, hr, wr, top, left, hout, wout)
@@ -178,10 +329,16 @@ def resize_crop_normalize(images_u8, resized_hw, crop_box, mean=IMAGENET_MEAN, s
 def imagenet_eval(images_u8, resize=256, crop=224, mean=IMAGENET_MEAN, std=IMAGENET_STD, dtype="fp32", layout="nchw",
                   channels_last=None) -> torch.Tensor:
     """torchvision's ImageNet evaluation preset on the device: shorter side to `resize` (antialiased bilinear), centre crop `crop`,
-    scale by 1 / 255, subtract `mean`, divide by `std`.  Returns [B, 3, crop, crop], fp32 or bf16: what `eqv.vmap(net)` reads."""
+    scale by 1 / 255, subtract `mean`, divide by `std`.  Returns [B, 3, crop, crop], fp32 or bf16: what `eqv.vmap(net)` reads.
+    A list of images of different sizes (decoded photographs) gets the preset's geometry per image, in one launch."""
     if layout != "nchw":
         raise ValueError(f"preprocess.imagenet_eval: the models read NCHW images; layout={layout!r} is not one of their entries "
                          "(resize_crop_normalize offers NHWC for other consumers)")
+    if isinstance(images_u8, (list, tuple)):
+        _, sizes = _check_list(images_u8, channels_last)
+        resized = [resized_size(h, w, resize) for h, w in sizes]
+        boxes = [center_crop_box(hr, wr, crop) for hr, wr in resized]
+        return resize_crop_normalize(images_u8, resized, boxes, mean, std, dtype, layout, channels_last)
     _, _, _, hin, win = _check_input(images_u8, channels_last)
     hr, wr = resized_size(hin, win, resize)
     return resize_crop_normalize(images_u8, (hr, wr), center_crop_box(hr, wr, crop), mean, std, dtype, layout, channels_last)

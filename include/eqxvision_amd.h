@@ -77,7 +77,7 @@ int mv_flags_epoch(void);                        /* hash of this thread's curren
 /* Device status word: kernels that detect a broken protocol at run time record it here instead of trapping (a trap poisons the whole
  * HIP context, graph replays and other streams included).  bit 0: a split-K block gave up waiting for its partner's partial sums
  * (dirty / shared scratch; the tile it wrote is incomplete).  bit 1: mv_softmax_xent_map_f32 met a label outside [0, C) on a counted
- * pixel (the pixel was left out; loss, gradient and sums of that call are not those of the labels given).  bit 2: mv_preprocess_u8_fwd was given a tap table that points outside the image or
+ * pixel (the pixel was left out; loss, gradient and sums of that call are not those of the labels given).  bit 2: mv_preprocess_u8_fwd / mv_preprocess_u8_ragged_fwd was given a tap table (or a device record) that points outside the image or
  * outside what its geometry can need (the taps were clamped; the output of that call is not the resize asked for).  Writes the word to *status, clears it if `clear`; SYNCHRONISES the
  * device -- call it where the host synchronises anyway (after a forward, at the end of a test). */
 int mv_device_status(int clear, unsigned* status);
@@ -549,6 +549,32 @@ int mv_copy_rows(const void* src, void* dst, int64_t rows, int64_t row_bytes, in
 int mv_preprocess_u8_fwd(const void* x, void* y, const void* tab_h, const void* tab_w, const float* a, const float* b, int B, int Hin,
                          int Win, int Hr, int Wr, int top, int left, int Hout, int Wout, int taps_h, int taps_w, int in_chw,
                          int out_dtype, int out_nhwc, mv_stream_t stream);
+
+/* The same transform for B images of DIFFERENT sizes in one launch (decoded photographs: every file has its own size).  The
+ * images lie tightly packed, at any byte alignment, in one uint8 buffer x of x_bytes bytes; the tables of all images and axes lie
+ * in one int32 buffer tab of tab_words words, each in the layout above; one record per image says where:
+ *   offset        byte offset of the image in x ([Hin,Win,3] or, with in_chw, [3,Hin,Win])
+ *   Hin, Win      its size;  Hr, Wr: the size it is resized to;  top, left: where the Hout x Wout box starts in the resized image
+ *   tab_h, tab_w  word offsets in tab of its row table (Hout entries, pitch mh) and its column table (Wout entries, pitch mw)
+ * Hout x Wout, in_chw, out_dtype, out_nhwc, a and b are per launch; y is [B,3,Hout,Wout] or [B,Hout,Wout,3].  The arithmetic of
+ * an output is that of mv_preprocess_u8_fwd, so an image gives the bits it gives alone, whatever shares the launch with it.
+ * The records are passed twice with the same contents.  rec_host (HOST memory, read before the call returns) is validated in
+ * full -- image inside x, tables inside tab, box inside the resized image, taps, x and y not overlapping: MV_E_INVALID or
+ * MV_E_UNSUPPORTED with a message that names the image, nothing launched -- and sizes the launch.  rec_dev (DEVICE memory) is
+ * what the kernel reads, and it trusts it no more than the tables: a device record that leaves either buffer or exceeds the
+ * pitches of the host copy stores nothing for its image, a table entry that leaves the image is clamped; both set bit 2 of
+ * mv_device_status.
+ * LDS rule: the grid is (tiles_x, tiles_y, B) with ONE tile and ONE LDS size, the largest tile of mv_preprocess_u8_fwd's list
+ * whose staged rectangle fits 64 KiB for the largest row span, column span and table pitches any image of the batch needs.  One
+ * steeply down-sampled image therefore gives the whole launch its small tile and its occupancy. */
+typedef struct mv_preprocess_image {
+    int64_t offset;
+    int32_t Hin, Win, Hr, Wr, top, left, tab_h, tab_w, mh, mw;
+} mv_preprocess_image;                           /* 48 bytes, no padding */
+int mv_preprocess_u8_ragged_fwd(const void* x, int64_t x_bytes, void* y, const mv_preprocess_image* rec_host,
+                                const mv_preprocess_image* rec_dev, const void* tab, int64_t tab_words, const float* a,
+                                const float* b, int B, int Hout, int Wout, int in_chw, int out_dtype, int out_nhwc,
+                                mv_stream_t stream);
 
 /* eqx.nn.MaxPool2d (resnet.py:254, alexnet.py:46,49,56): -inf padding, floor output size. */
 int mv_maxpool2d_nhwc_fwd(const void* x, void* y, int N, int H, int W, int C,
