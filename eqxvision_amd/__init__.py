@@ -13,9 +13,9 @@ __version__ = "0.1.0"
 
 from . import layers, models, nn, postprocess, preprocess, random, utils
 from ._act import (compute_dtype, precision, set_compute_dtype, set_head_fp32, set_residual_fp32, set_split_weights)
-from ._module import Module, tree_at, tree_inference, tree_leaves
+from ._module import Module, tree_at, tree_inference, tree_leaves, tree_map
 from .transforms import filter_jit, vmap
-from . import grad as optim          # optax-shaped names: optim.adam, optim.softmax_cross_entropy, optim.one_hot
+from . import grad as optim          # optax-shaped names: optim.adam / sgd / adamw / chain, the schedules, optim.softmax_cross_entropy, optim.one_hot
 from .grad import apply_updates, filter_value_and_grad
 from ._module import is_array
 
@@ -25,6 +25,6 @@ def filter(tree, predicate=None):
     skips non-array leaves itself, so the tree is returned as it is."""
     return tree
 
-__all__ = ["layers", "models", "nn", "postprocess", "preprocess", "random", "utils", "Module", "tree_at", "tree_inference", "tree_leaves",
+__all__ = ["layers", "models", "nn", "postprocess", "preprocess", "random", "utils", "Module", "tree_at", "tree_inference", "tree_leaves", "tree_map",
            "filter_jit", "vmap", "filter_value_and_grad", "apply_updates", "optim", "filter", "is_array", "compute_dtype", "precision", "set_compute_dtype", "set_head_fp32", "set_residual_fp32",
            "set_split_weights"]

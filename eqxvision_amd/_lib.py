@@ -19,6 +19,8 @@ F32, BF16 = 0, 1
 ACT_NONE, ACT_RELU, ACT_GELU_TANH = 0, 1, 2
 ACT_HARD_SWISH, ACT_HARD_SIGMOID, ACT_SIGMOID, ACT_SILU = 3, 4, 5, 6       # element-wise entries and the depthwise conv only
 ABI_VERSION = 2
+OPT_SGD, OPT_ADAMW, OPT_APPLY = 0, 1, 2                                    # mv_optim_step_f32's `kind`
+OPTIM_CHUNK = 4096                                                         # MV_OPTIM_CHUNK: elements per workgroup
 
 _vp, _i, _f, _i64 = C.c_void_p, C.c_int, C.c_float, C.c_int64
 
@@ -168,6 +170,8 @@ PROTOTYPES = {
     "mv_mha_bwd_f32": [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _vp],
     "mv_softmax_xent_f32": [_vp, _vp, _vp, _vp, _vp, _i, _i, _vp],
     "mv_adam_step_f32": [_vp, _vp, _vp, _vp, _i64] + [_f] * 6 + [_vp],
+    "mv_optim_sqnorm_f32": [_vp, _i, _i64, _vp, _vp, _f, _vp],
+    "mv_optim_step_f32": [_vp, _i, _i64, _i, _i] + [_f] * 9 + [_vp, _vp],
     "mv_transpose2d_f32": [_vp, _vp, _i, _i, _i64, _vp],
     "mv_swin_window_attn_bwd_f32": [_vp] * 5 + [_i] * 9 + [_vp],
     "mv_scatter_rows_sum_f32": [_vp, _vp, _vp, _i, _i, _i, _vp],

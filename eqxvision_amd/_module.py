@@ -254,15 +254,16 @@ def _children(node) -> List[Tuple[Any, Any]]:
     return None
 
 
-def tree_leaves(tree) -> list:
+def tree_leaves(tree, none_is_leaf: bool = False) -> list:
     """All leaves, depth-first in declaration order (== `jax.tree_util.tree_leaves` on the
-    reference's dataclass pytrees; `None` is not a leaf, like in jax)."""
+    reference's dataclass pytrees; `None` is not a leaf, like in jax, unless `none_is_leaf`: the
+    positions of a tree and of a gradient tree with `None` at its frozen leaves then line up)."""
     out = []
 
     def rec(n):
         ch = _children(n)
         if ch is None:
-            if n is not None:
+            if n is not None or none_is_leaf:
                 out.append(n)
             return
         for _, c in ch:
@@ -287,8 +288,9 @@ def _rebuild(n: "Module", rec: Callable, override: Callable = None) -> "Module":
     return new
 
 
-def tree_map(fn: Callable, tree):
-    """Rebuild `tree` with `fn` applied to every leaf (new Module objects, caches dropped)."""
+def tree_map(fn: Callable, tree, none_is_leaf: bool = False):
+    """Rebuild `tree` with `fn` applied to every leaf (new Module objects, caches dropped); `None` is kept as it is unless
+    `none_is_leaf`, which hands it to `fn` like any other leaf (the visiting order is tree_leaves')."""
 
     def rec(n):
         if isinstance(n, Module):
@@ -299,7 +301,7 @@ def tree_map(fn: Callable, tree):
             return tuple(rec(c) for c in n)
         if isinstance(n, dict):
             return {k: rec(c) for k, c in n.items()}
-        if n is None:
+        if n is None and not none_is_leaf:
             return None
         return fn(n)
 
@@ -333,12 +335,24 @@ def tree_inference(tree, value: bool = True):
 _MISSING = object()
 
 
+class _Box:
+    __slots__ = ("value",)
+
+    def __init__(self, value):
+        self.value = value
+
+
 def tree_at(where: Callable, tree, replace=_MISSING, replace_fn: Callable = None):
     """Tiny `eqx.tree_at`: `where(tree)` must return one node (or a tuple of nodes); the
     returned tree has them replaced by `replace` (same structure as the targets) or by `replace_fn(node)` (fcn.py:106).
     Implemented by identity search on a deep structural copy."""
     targets = where(tree)
     single = not isinstance(targets, (tuple, list))      # eqx.tree_at takes any sequence of nodes (experimental.py:73-80 passes a list)
+    if any(isinstance(t, (bool, np.bool_)) for t in ((targets,) if single else targets)):
+        # a filter spec (`tree_map(lambda _: False, model)`): every leaf is the SAME object, so identity cannot tell the targets
+        # apart.  Look them up in a copy whose leaves are boxed one by one, and un-box the result.
+        unbox = lambda b: b.value if isinstance(b, _Box) else b
+        return tree_map(unbox, tree_at(where, tree_map(_Box, tree), replace, replace_fn and (lambda b: replace_fn(unbox(b)))))
     targets = (targets,) if single else tuple(targets)
     if (replace is _MISSING) == (replace_fn is None):
         raise ValueError("tree_at: exactly one of `replace` and `replace_fn` must be given")

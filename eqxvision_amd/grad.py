@@ -41,7 +41,7 @@ import torch
 
 from . import _lib
 from ._act import Act, device, empty, precision, stream_ptr
-from ._module import DevArray, Module, tree_map
+from ._module import DevArray, Module, tree_leaves, tree_map
 
 _tls = threading.local()
 F32 = _lib.F32
@@ -57,6 +57,7 @@ class Tape:
         self.dev = {}           # (id(leaf), tag) -> device copy / re-layout of a parameter
         self.leaf_of = {}       # data_ptr of a device vector handed out by ops.prep_f32 -> leaf
         self.count = 0
+        self.frozen = None      # ids of the leaves a filter spec (filter_value_and_grad's `arg`) marks False; None = no spec
         self.inside = 0         # > 0 while a g_* function runs (its own C-ABI calls are allowed)
 
 
@@ -204,9 +205,21 @@ def _node(x) -> Optional[Node]:
     return getattr(x, "node", None) if isinstance(x, Act) else None
 
 
-def _mk(t: torch.Tensor, kind: str, batched: bool, parents, backward) -> Act:
+def _trainable(leaf) -> bool:
+    """Does this parameter leaf get a gradient?  Not when it is absent, nor when the filter spec froze it."""
+    if leaf is None:
+        return False
+    frozen = tape().frozen
+    return frozen is None or id(leaf) not in frozen
+
+
+def _mk(t: torch.Tensor, kind: str, batched: bool, parents, backward, leaves=()) -> Act:
+    """The result of a rule with its node; `leaves` = the parameter leaves the rule's backward accumulates into.  Under a filter
+    spec a rule none of whose inputs has a node and none of whose leaves is trainable records nothing: a frozen backbone costs
+    its forward only.  Without a spec every rule records its node."""
     a = Act(t, kind, batched)
-    a.node = Node(parents, backward)
+    if tape().frozen is None or any(p is not None for p in parents) or any(_trainable(l) for l in leaves):
+        a.node = Node(parents, backward)
     return a
 
 
@@ -452,13 +465,16 @@ def _bn_backward(bn, z: torch.Tensor, g: torch.Tensor, saved) -> torch.Tensor:
     sc, mean, var, train = saved
     C = z.shape[-1]
     s1 = s2 = None
-    if bn.weight is not None or train is not None:
+    wt, bt = _trainable(bn.weight), _trainable(bn.bias)      # a frozen leaf launches no parameter-gradient kernel
+    if wt or bt or train is not None:
         s1 = _colsum(g, None, C)
+    if wt or train is not None:
         s2 = _colsum(g, z, C)
-    if bn.weight is not None:
+    if wt:
         dg = _new((C,))
         _call("mv_bn_dgamma_f32", _p(s2), _p(s1), _p(mean), _p(var), float(bn.eps), _p(dg), C, _S())
         _acc_param(bn.weight, dg)                   # per-rank partial sums, like every other parameter gradient
+    if bt:
         _acc_param(bn.bias, s1)
     dz = _new(z.shape)
     zeros = torch.zeros((C,), dtype=torch.float32, device=device())
@@ -495,7 +511,8 @@ def g_batchnorm(x: Act, bn, act=None) -> Act:
     if act not in (None, "none"):
         y = _new(y1.shape)
         _call("mv_eltwise_fwd", _p(y1), _p(y), y1.numel(), ACTS[act], F32, _S())
-    return _mk(y, x.kind, x.batched, [_node(x)], lambda g: (_bn_backward(bn, z, _act_bwd(g, y1, act), saved),))
+    return _mk(y, x.kind, x.batched, [_node(x)], lambda g: (_bn_backward(bn, z, _act_bwd(g, y1, act), saved),),
+               leaves=(bn.weight, bn.bias))
 
 
 # ------------------------------------------------------------------------------------------------------------ convolution
@@ -545,20 +562,22 @@ def g_conv2d(x: Act, conv, bn=None, act=None, residual: Optional[Act] = None) ->
     def backward(g):
         g2 = _act_bwd(g, y2, act)
         dz = g2 if bn is None else _bn_backward(bn, z, g2, saved)
-        if conv.bias is not None:
+        if _trainable(conv.bias):
             _acc_param(conv.bias, _colsum(dz, None, K))
-        dwk = _new((K, kh, kw, C // G))
-        _offer_scratch()
-        _call("mv_conv2d_wgrad_nhwc_f32", _p(xin), _p(dz), _p(dwk), B, H, W, C, K, kh, kw, sh, sw, ph, pw, dh, dw, G, _S())
-        dwo = _new((K, C // G, kh, kw))
-        _call("mv_nhwc_to_nchw", _p(dwk), _p(dwo), K, C // G, kh, kw, F32, F32, _S())   # KRSC -> OIHW, the leaf's layout
-        _acc_param(conv.weight, dwo)
+        if _trainable(conv.weight):
+            dwk = _new((K, kh, kw, C // G))
+            _offer_scratch()
+            _call("mv_conv2d_wgrad_nhwc_f32", _p(xin), _p(dz), _p(dwk), B, H, W, C, K, kh, kw, sh, sw, ph, pw, dh, dw, G, _S())
+            dwo = _new((K, C // G, kh, kw))
+            _call("mv_nhwc_to_nchw", _p(dwk), _p(dwo), K, C // G, kh, kw, F32, F32, _S())   # KRSC -> OIHW, the leaf's layout
+            _acc_param(conv.weight, dwo)
         dx = None
         if need_dx:
             dx = _new((B, H, W, C))
             _call("mv_conv2d_dgrad_nhwc_f32", _p(dz), _p(w), _p(dx), B, H, W, C, K, kh, kw, sh, sw, ph, pw, dh, dw, G, _S())
         return (dx, g2 if r is not None else None)
-    return _mk(y, "map", x.batched, [_node(x), _node(r)], backward)
+    return _mk(y, "map", x.batched, [_node(x), _node(r)], backward,
+               leaves=(conv.weight, conv.bias) + ((bn.weight, bn.bias) if bn is not None else ()))
 
 
 @_op
@@ -591,16 +610,17 @@ def g_linear(x: Act, lin, act=None, residual: Optional[Act] = None, out_fp32: bo
 
     def backward(g):
         g2 = _act_bwd(g, y2, act)
-        if lin.bias is not None:
+        if _trainable(lin.bias):
             _acc_param(lin.bias, _colsum(g2, None, N))
-        gT, xT = _transpose(g2, M, N), _transpose(xin, M, K)            # dW[N,K] = g^T . x
-        _acc_param(lin.weight, _matmul_nt(gT, xT, N, K, M))
+        if _trainable(lin.weight):
+            gT, xT = _transpose(g2, M, N), _transpose(xin, M, K)        # dW[N,K] = g^T . x
+            _acc_param(lin.weight, _matmul_nt(gT, xT, N, K, M))
         dx = None
         if need_dx:
             Wt = _leaf_dev(lin.weight, "t", lambda raw: _transpose(raw, N, K))   # [K,N]
             dx = _matmul_nt(g2, Wt, M, K, N).reshape(tuple(xin.shape))         # dx[M,K] = g . W
         return (dx, g2 if residual is not None else None)
-    return _mk(y, x.kind, x.batched, [_node(x), _node(residual)], backward)
+    return _mk(y, x.kind, x.batched, [_node(x), _node(residual)], backward, leaves=(lin.weight, lin.bias))
 
 
 @_op
@@ -626,11 +646,12 @@ def g_layernorm(x: Act, ln, out_fp32: bool = False) -> Act:
     def backward(g):
         dx, gx = _new(xin.shape), _new(xin.shape)
         _call("mv_layernorm_bwd_f32", _p(xin), _p(gam), _p(g), _p(dx), _p(gx), M, C, float(ln.eps), _S())
-        if ln.weight is not None:
+        if _trainable(ln.weight):
             _acc_param(ln.weight, _colsum(gx, None, C))
+        if ln.weight is not None and _trainable(ln.bias):
             _acc_param(ln.bias, _colsum(g, None, C))
         return (dx,)
-    return _mk(y, x.kind, x.batched, [_node(x)], backward)
+    return _mk(y, x.kind, x.batched, [_node(x)], backward, leaves=(ln.weight, ln.bias))
 
 
 @_op
@@ -681,16 +702,16 @@ def g_patch_embed_tokens(x: Act, conv, cls, pos, n_extra: int, out_fp32: bool = 
     pos_leaf = t.leaf_of.get(pos.data_ptr()) if pos is not None else None
 
     def backward(g):                                                      # g [B, T, D]
-        if pos_leaf is not None:
+        if _trainable(pos_leaf):
             _acc_param(pos_leaf, _colsum(g, None, T * D))                 # sum over the batch
-        if cls_leaf is not None:
+        if _trainable(cls_leaf):
             rows = _new((B, D))
             _call("mv_copy_rows", _p(g), _p(rows), B, 4 * D, 4 * T * D, 4 * D, _S())
             _acc_param(cls_leaf, _colsum(rows, None, D))
         dy = _new((B, Hp, Wp, D))
         _call("mv_copy_rows", g.data_ptr() + 4 * n_extra * D, _p(dy), B, 4 * P * D, 4 * T * D, 4 * P * D, _S())
         return (dy,)
-    return _mk(out, "seq", x.batched, [_node(y)], backward)
+    return _mk(out, "seq", x.batched, [_node(y)], backward, leaves=(pos_leaf, cls_leaf))
 
 
 @_op
@@ -751,7 +772,7 @@ def g_swin_window_attention(qkv: Act, bias: torch.Tensor, heads: int, window, sh
         dqkv = _new((B, Hf, Wf, C3))
         gw = _new((B * nW, heads * n * n))
         _call("mv_swin_window_attn_bwd_f32", _p(qt), _p(bias), _p(g), _p(dqkv), _p(gw), B, Hf, Wf, C, heads, wh, ww, sh, sw, _S())
-        if info is not None:
+        if info is not None and _trainable(info[0]):
             table, idx, T = info
             db = _colsum(gw, None, heads * n * n)                         # [heads][n * n]: summed over images and windows
             dbt = _transpose(db, heads, n * n)                            # [n * n][heads]
@@ -759,7 +780,7 @@ def g_swin_window_attention(qkv: Act, bias: torch.Tensor, heads: int, window, sh
             _call("mv_scatter_rows_sum_f32", _p(dbt), _p(idx), _p(dt), n * n, heads, T, _S())
             _acc_param(table, dt)
         return (dqkv,)
-    return _mk(out, "map", qkv.batched, [_node(qkv)], backward)
+    return _mk(out, "map", qkv.batched, [_node(qkv)], backward, leaves=(info[0],) if info is not None else ())
 
 
 @_op
@@ -1067,14 +1088,65 @@ def _backward(root: Node):
         t.inside -= 1
 
 
-def filter_value_and_grad(fn: Callable) -> Callable:
+def _frozen_ids(model, spec) -> set:
+    """ids of the float array leaves of `model` that the filter spec marks False.  `spec` has the model's structure with a bool at
+    every array leaf (`tree_map(lambda _: False, model)`, then `tree_at` for the trainable parts); a bool in the place of a
+    whole sub-tree stands for every leaf below it.  Host work only; any other shape raises ValueError."""
+    frozen = set()
+
+    def bad(path, why):
+        raise ValueError(f"filter_value_and_grad: the `arg` spec does not match the model at {path or '<root>'}: {why}")
+
+    def rec(m, s, path):
+        if isinstance(s, (bool, np.bool_)):
+            if not s:
+                frozen.update(id(l) for l in tree_leaves(m) if _float_leaf(l))
+            return
+        if isinstance(m, Module):
+            if type(s) is not type(m):
+                bad(path, f"{type(m).__name__} in the model, {type(s).__name__} in the spec")
+            fields = [f for f in m.__fields__ if hasattr(m, f)]
+            if fields != [f for f in s.__fields__ if hasattr(s, f)]:
+                bad(path, "the two modules do not have the same fields")
+            for f in fields:
+                rec(getattr(m, f), getattr(s, f), f"{path}.{f}")
+        elif isinstance(m, (list, tuple)):
+            if not isinstance(s, (list, tuple)) or len(s) != len(m):
+                bad(path, f"a sequence of {len(m)} in the model, {_what(s)} in the spec")
+            for i, (a, b) in enumerate(zip(m, s)):
+                rec(a, b, f"{path}[{i}]")
+        elif isinstance(m, dict):
+            if not isinstance(s, dict) or list(s) != list(m):
+                bad(path, f"a dict with keys {list(m)} in the model, {_what(s)} in the spec")
+            for k in m:
+                rec(m[k], s[k], f"{path}[{k!r}]")
+        elif _float_leaf(m):
+            bad(path, f"an array leaf needs a bool, the spec has {_what(s)}")
+        # any other leaf (None, int, callable, integer array, StateIndex) has no gradient: whatever the spec holds there is ignored
+
+    def _what(s):
+        return f"a sequence of {len(s)}" if isinstance(s, (list, tuple)) else type(s).__name__
+
+    rec(model, spec, "")
+    return frozen
+
+
+def filter_value_and_grad(fn: Optional[Callable] = None, *, arg=None) -> Callable:
     """`eqx.filter_value_and_grad`: fn(model, *args) -> scalar loss; returns (loss, grads) with `grads` = the model tree with
-    every array leaf replaced by its gradient (zeros where the loss does not depend on it) and every other leaf kept."""
+    every array leaf replaced by its gradient (zeros where the loss does not depend on it) and every other leaf kept.
+
+    `arg` (a keyword, so `functools.partial(filter_value_and_grad, arg=filter_spec)` is the decorator of the reference's
+    transfer-learning tutorial): a tree of the model's structure with a bool at every array leaf.  A leaf whose bool is False is
+    frozen: its gradient is `None`, no parameter-gradient kernel is launched for it, and a rule with no trainable leaf and no
+    input on the tape records no node (`_mk`), so the backward pass stops where the trainable part of the network starts."""
+    if fn is None:
+        return functools.partial(filter_value_and_grad, arg=arg)
 
     @functools.wraps(fn)
     def wrapped(model, *args, **kwargs):
         if active():
             raise RuntimeError("filter_value_and_grad does not nest")
+        frozen = None if arg is None else _frozen_ids(model, arg)
         # under filter_jit (the reference wraps its make_step in eqx.filter_jit): the loss is a host float and the gradients are read
         # after a synchronize -- a replay of the launches would hand back the first call's values.  The trace in progress is marked
         # so that filter_jit runs this function eagerly on every call (transforms.jitted).
@@ -1082,6 +1154,7 @@ def filter_value_and_grad(fn: Callable) -> Callable:
         if not torch.cuda.is_available():
             raise _lib.MVError("eqxvision_amd needs an MI355X (no HIP device visible); there is no CPU fallback")
         t = _tls.tape = Tape()
+        t.frozen = frozen
         try:
             with precision("fp32"):
                 loss = fn(model, *args, **kwargs)
@@ -1096,6 +1169,8 @@ def filter_value_and_grad(fn: Callable) -> Callable:
                 def leaf_grad(leaf):
                     if not _float_leaf(leaf):
                         return leaf
+                    if frozen is not None and id(leaf) in frozen:
+                        return None
                     g = t.pgrads.get(id(leaf))
                     if g is None:
                         g = torch.zeros(tuple(leaf.shape), dtype=torch.float32, device=device())
@@ -1113,37 +1188,47 @@ def _float_leaf(x) -> bool:
 
 
 class _Adam:
-    """optax.adam(learning_rate, b1, b2, eps): init(params) -> state; update(grads, state) -> (updates, state)."""
+    """optax.adam(learning_rate, b1, b2, eps): init(params) -> state; update(grads, state) -> (updates, state).  One
+    mv_adam_step_f32 launch per leaf (moving it onto csrc/optim.hip's one-launch kernel is future work).  `learning_rate` is a float
+    or a schedule (a function of the step count; the first update uses schedule(0), as in optax).  `None` gradients -- the frozen
+    leaves of a filter spec -- are skipped: no launch, `None` in the updates, moments untouched."""
 
-    def __init__(self, learning_rate: float, b1: float = 0.9, b2: float = 0.999, eps: float = 1e-8):
-        self.lr, self.b1, self.b2, self.eps = float(learning_rate), float(b1), float(b2), float(eps)
+    def __init__(self, learning_rate, b1: float = 0.9, b2: float = 0.999, eps: float = 1e-8):
+        self.lr = learning_rate if callable(learning_rate) else float(learning_rate)
+        self.b1, self.b2, self.eps = float(b1), float(b2), float(eps)
 
     def init(self, params):
-        from ._module import tree_leaves
-        n = [int(np.prod(l.shape)) for l in tree_leaves(params) if _float_leaf(l)]
+        index, n = _optim.leaf_index(params)
         z = lambda k: torch.zeros(k, dtype=torch.float32, device=device())
-        return {"count": 0, "mu": [z(k) for k in n], "nu": [z(k) for k in n]}
+        return {"count": 0, "mu": [z(k) for k in n], "nu": [z(k) for k in n], "index": index}
 
     def update(self, grads, state, params=None):
         count = state["count"] + 1
+        lr = _optim.rate(self.lr, state["count"])
         bc1, bc2 = 1.0 - self.b1 ** count, 1.0 - self.b2 ** count
-        it = iter(range(len(state["mu"])))
+        index = state["index"]
+        pos = iter(index)
 
         def step(leaf):
-            if not _float_leaf(leaf):
+            i = next(pos, None)
+            if not _float_leaf(leaf):                   # None (a frozen leaf) and every non-array leaf stay as they are
                 return leaf
-            i = next(it)
+            if i is None or i < 0:
+                raise ValueError("adam.update: the gradients do not have the structure of the tree given to init")
             g = _upload(leaf)
             upd = torch.empty(g.numel(), dtype=torch.float32, device=device())
-            _lib.call("mv_adam_step_f32", _p(g), _p(state["mu"][i]), _p(state["nu"][i]), _p(upd), g.numel(), self.lr, self.b1, self.b2,
+            _lib.call("mv_adam_step_f32", _p(g), _p(state["mu"][i]), _p(state["nu"][i]), _p(upd), g.numel(), lr, self.b1, self.b2,
                       self.eps, bc1, bc2, stream_ptr())
             return DevArray(upd.reshape(tuple(leaf.shape)))
-        updates = tree_map(step, grads)
-        return updates, {"count": count, "mu": state["mu"], "nu": state["nu"]}
+        updates = tree_map(step, grads, none_is_leaf=True)
+        return updates, {"count": count, "mu": state["mu"], "nu": state["nu"], "index": index}
 
 
-def adam(learning_rate: float, b1: float = 0.9, b2: float = 0.999, eps: float = 1e-8) -> _Adam:
+def adam(learning_rate, b1: float = 0.9, b2: float = 0.999, eps: float = 1e-8) -> _Adam:
     return _Adam(learning_rate, b1, b2, eps)
+
+
+_APPLY_RECORDS = {}        # the record buffer of the last apply_updates launch (reused while the pointers repeat)
 
 
 def apply_updates(model, updates):
@@ -1151,20 +1236,38 @@ def apply_updates(model, updates):
     device and STAYS there: the new leaves are `DevArray`s (the analogue of the reference's jax.Array leaves), so a training loop
     moves its parameters across PCIe once -- the first step's upload -- and its gradients, moments and updates never
     (`np.asarray(leaf)` / `state_dict` fetch a host copy on demand).  Round 4 downloaded every leaf here and uploaded it again in
-    the next step: 5 crossings of the parameter set per step (alexnet B = 8: 118 ms)."""
-    from ._module import tree_leaves
-    ups = [u for u in tree_leaves(updates) if _float_leaf(u)]
-    it = iter(ups)
+    the next step: 5 crossings of the parameter set per step (alexnet B = 8: 118 ms).
 
-    def step(leaf):
-        if not _float_leaf(leaf):
-            return leaf
-        u = next(it)
+    All fp32 leaves are summed by ONE launch (mv_optim_step_f32, MV_OPT_APPLY: a single fp32 add per element, correctly rounded
+    like mv_add_fwd's); other float widths keep their dtype and are summed on the host.  A leaf whose update is `None` (frozen) is
+    kept: the same object, not a copy."""
+    leaves, ups = tree_leaves(model, none_is_leaf=True), tree_leaves(updates, none_is_leaf=True)
+    if len(ups) != len(leaves):
+        raise ValueError(f"apply_updates: the updates have {len(ups)} leaves, the model has {len(leaves)}")
+    new, rows, keep = [], [], []
+    for leaf, u in zip(leaves, ups):
+        if u is None or not _float_leaf(leaf):
+            new.append(leaf)
+            continue
+        if not _float_leaf(u):
+            raise ValueError(f"apply_updates: a {type(u).__name__} where the update of a float array leaf was expected")
         if leaf.dtype != np.float32:               # the device state is fp32 only: other float widths keep their dtype, summed on the host
-            return (np.asarray(leaf) + np.asarray(u).reshape(leaf.shape).astype(leaf.dtype)).astype(leaf.dtype)
-        ud = _upload(u)
-        p = _upload(leaf)
+            new.append((np.asarray(leaf) + np.asarray(u).reshape(leaf.shape).astype(leaf.dtype)).astype(leaf.dtype))
+            continue
+        p, ud = _upload(leaf).contiguous(), _upload(u).contiguous()
+        if ud.numel() != p.numel():
+            raise ValueError(f"apply_updates: an update of shape {tuple(u.shape)} for a leaf of shape {tuple(leaf.shape)}")
         out = torch.empty_like(p)
-        _lib.call("mv_add_fwd", _p(p), _p(ud.reshape(p.shape)), _p(out), p.numel(), _lib.ACT_NONE, F32, stream_ptr())
-        return DevArray(out.reshape(tuple(leaf.shape)))
-    return tree_map(step, model)
+        if p.numel():
+            rows.append((_p(ud), _p(p), 0, 0, _p(out), p.numel()))
+            keep.append((p, ud))
+        new.append(DevArray(out.reshape(tuple(leaf.shape))))
+    if rows:
+        _optim.launch(_APPLY_RECORDS, rows, _lib.OPT_APPLY)
+    it = iter(new)
+    return tree_map(lambda _: next(it), model, none_is_leaf=True)
+
+
+from . import _optim                                                      # noqa: E402  (it uses the helpers above)
+from ._optim import (adamw, chain, clip_by_global_norm, constant_schedule, cosine_decay_schedule, sgd,     # noqa: E402,F401
+                     warmup_cosine_decay_schedule)

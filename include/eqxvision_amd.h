@@ -796,6 +796,39 @@ int mv_softmax_xent_f32(const float* logits, const float* target, float* loss_ro
  * bias_corr = 1 - beta^t computed by the caller; eqx.apply_updates adds `update` to the parameter (mv_add_fwd). */
 int mv_adam_step_f32(const float* grad, float* m, float* v, float* update, int64_t n, float lr, float b1, float b2, float eps,
                      float bias_corr1, float bias_corr2, mv_stream_t stream);
+/* ---- optimisers over a whole parameter set (csrc/optim.hip).  One record per tensor, all records in ONE device
+ * buffer; a 256-thread workgroup owns one chunk of MV_OPTIM_CHUNK elements of one tensor and finds its record by binary search of
+ * first_block over its block index (first_block[0] = 0, first_block[i + 1] = first_block[i] + ceil(n[i] / MV_OPTIM_CHUNK),
+ * total_blocks = the sum).  param / m / v may be NULL where the rule does not use them; grad, out and n > 0 are required.  A
+ * tensor whose pointers are all 16-byte aligned is streamed as float4 (scalar tail for n % 4), any other element by element.  No
+ * atomics; out may alias nothing else of its record.  The records are trusted: the caller builds them from live allocations. */
+#define MV_OPTIM_CHUNK 4096
+typedef struct mv_optim_tensor {
+    const float* grad;
+    const float* param;
+    float* m;
+    float* v;
+    float* out;
+    int64_t n;
+    int64_t first_block;
+} mv_optim_tensor;                               /* 56 bytes, no padding */
+enum { MV_OPT_SGD = 0, MV_OPT_ADAMW = 1, MV_OPT_APPLY = 2 };
+/* Sum of squares of every grad of the set, and optax.clip_by_global_norm's factor.  Two launches: every workgroup writes the sum
+ * of its chunk to partial[block] (total_blocks floats; per lane in element order, a fixed butterfly over the wave, the four waves
+ * in order through LDS), then one workgroup adds the partials (thread t takes t, t + 256, ... in order, then the same tree) and
+ * writes out2[0] = sum, out2[1] = (sqrt(sum) < max_norm ? 1 : max_norm / sqrt(sum)).  The order is fixed: same bits every run. */
+int mv_optim_sqnorm_f32(const mv_optim_tensor* recs, int n_tensors, int64_t total_blocks, float* partial, float* out2,
+                        float max_norm, mv_stream_t stream);
+/* One launch over all tensors.  g = grad * scale[1] when scale != NULL (the out2 of mv_optim_sqnorm_f32), else grad.
+ *   MV_OPT_SGD   (optax.sgd / trace): m == NULL: out = -lr g.  Else m = g + b1 m (b1 = the momentum), out = -lr m, or with
+ *                nesterov != 0 out = -lr (g + b1 m).
+ *   MV_OPT_ADAMW (optax.adamw): m = b1 m + one_minus_b1 g, v = b2 v + one_minus_b2 g^2,
+ *                out = -lr ((m / bias_corr1) / (sqrt(v / bias_corr2) + eps) + weight_decay param); param may be NULL when
+ *                weight_decay == 0.  one_minus_b* and bias_corr* = 1 - b*^t come from the caller (rounded once from float64).
+ *   MV_OPT_APPLY (eqx.apply_updates): out = param + grad. */
+int mv_optim_step_f32(const mv_optim_tensor* recs, int n_tensors, int64_t total_blocks, int kind, int nesterov, float lr, float b1,
+                      float b2, float one_minus_b1, float one_minus_b2, float eps, float weight_decay, float bias_corr1,
+                      float bias_corr2, const float* scale, mv_stream_t stream);
 /* Backward of mv_swin_window_attn_fwd (swin.py:123-250), fp32: dqkv[B,Hf,Wf,3C] from qkv, the relative-position bias
  * [heads][n][n] and dout[B,Hf,Wf,C]; g_windows [B * windows][heads][n * n] receives the gradient w.r.t. the attention logits of
  * every window (its column sum over the windows = the bias gradient).  Windows of <= 64 tokens. */
