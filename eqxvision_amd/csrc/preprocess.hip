@@ -3,9 +3,11 @@
 // The filter lives in two tap tables the host builds in float64 (eqxvision_amd/preprocess.py: axis_table); the kernel only
 // applies them, so the same entry serves the antialiased ImageNet preset and plain two-tap up-sampling.  HBM-bound gather, no
 // matrix work: every input byte a tile needs is read once into LDS, both passes run out of LDS, every output is stored once.
-// Two entries share the tile body: one image size per launch (mv_preprocess_u8_fwd), or one record per image for a packed batch
-// of any sizes (mv_preprocess_u8_ragged_fwd).  A launch has ONE tile and ONE LDS size; the ragged entry sizes them for the largest
-// spans and pitches of its batch, so one steeply down-sampled image lowers the occupancy of the whole launch (accepted).
+// Three entries share the tile body: one image size per launch (mv_preprocess_u8_fwd), one record per image for a packed batch
+// of any sizes (mv_preprocess_u8_ragged_fwd), and one box per image that is cropped FIRST and then resized, mirrored or not
+// (mv_preprocess_u8_boxes_fwd: the training transform; its filter is generated in the tile, no tables).  A launch has ONE tile
+// and ONE LDS size; the record entries size them for the largest spans and pitches of their batch, so one steeply down-sampled
+// image lowers the occupancy of the whole launch (accepted).
 #include "common.h"
 
 namespace mv {
@@ -38,8 +40,149 @@ struct PrepRaggedP {
 
 __device__ __forceinline__ int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
 
+// taps an n_in -> n_out resize can give one output: the open interval of half-width max(1, in / out), no more than the axis
+__host__ __device__ inline int taps_needed(int in, int out_full) {
+    const double ratio = (double)in / (double)out_full, sup = ratio > 1.0 ? ratio : 1.0;
+    const double n = 2.0 * sup + 1.0;
+    return n >= in ? in : (int)n;
+}
+
+// mv_preprocess_u8_boxes_fwd: one box per image (blockIdx.z), no tables.  In `p`, x is the packed buffer, mh / mw / rows_cap /
+// cols_cap / pitch the largest any box of the batch needs; Hin, Win, tab_h and tab_w are not used.
+struct PrepBoxesP {
+    PrepP p;
+    const mv_preprocess_box* rec;
+    long long x_bytes;
+};
+
+// The LDS of one tile: staged uint8 lines | fp32 horizontal sums | first / count of the tile's rows and columns | their weights.
+struct TileLds {
+    uint8_t* su8;
+    float* sh;
+    int *sfy, *sny, *sfx, *snx;
+    float *swy, *swx;
+};
+
+// The input rectangle [r0, r1) x [c0, c1) a tile's taps touch; bad: something had to be cut to get there.
+struct TileRect {
+    int r0, r1, c0, c1, bad;
+};
+
+template <bool CHW_IN> __device__ __forceinline__ TileLds tile_lds(const PrepP& p) {
+    extern __shared__ uint4 smem4[];
+    const int lines_cap = CHW_IN ? 3 * p.rows_cap : p.rows_cap;
+    TileLds L;
+    L.su8 = (uint8_t*)smem4;
+    L.sh = (float*)(L.su8 + (size_t)lines_cap * p.pitch);
+    L.sfy = (int*)(L.sh + (size_t)p.rows_cap * 3 * p.TW);
+    L.sny = L.sfy + p.TH;
+    L.sfx = L.sny + p.TH;
+    L.snx = L.sfx + p.TW;
+    L.swy = (float*)(L.snx + p.TW);
+    L.swx = L.swy + p.TH * p.mh;
+    return L;
+}
+
+// Nothing that decides an address is trusted: the rectangle is cut to the image and to the LDS it was sized for, tap indices
+// are clamped into it by the passes, and a source that needed either sets bit 2 of the device status word.
+__device__ __forceinline__ void cut_rect(const PrepP& p, TileRect& t) {
+    t.r0 = clampi(t.r0, 0, p.Hin - 1);
+    t.c0 = clampi(t.c0, 0, p.Win - 1);
+    t.r1 = clampi(t.r1, t.r0 + 1, p.Hin);
+    t.c1 = clampi(t.c1, t.c0 + 1, p.Win);
+    if (t.r1 - t.r0 > p.rows_cap) { t.r1 = t.r0 + p.rows_cap; t.bad = 1; }
+    if (t.c1 - t.c0 > p.cols_cap) { t.c1 = t.c0 + p.cols_cap; t.bad = 1; }
+    if (t.bad && threadIdx.x == 0) atomicOr(p.status, 4u);
+}
+
+// Step 1, source A: the tables of the tile's rows / columns from global memory (p.tab_h, p.tab_w).  The rectangle is uniform
+// over the workgroup (scalar loads).  The tables are device data the host cannot see at launch time: see cut_rect.
+__device__ __forceinline__ TileRect tables_from_global(const PrepP& p, const TileLds& L, int y0, int x0, int th, int tw) {
+    const int tid = threadIdx.x;
+    TileRect t = {p.Hin, 0, p.Win, 0, 0};
+    for (int i = 0; i < th; ++i) {
+        const int f = p.tab_h[y0 + i], n = p.tab_h[p.Hout + y0 + i];
+        t.bad |= (f < 0) | (n < 1) | (n > p.mh) | (f + n > p.Hin);
+        t.r0 = min(t.r0, f);
+        t.r1 = max(t.r1, f + n);
+    }
+    for (int i = 0; i < tw; ++i) {
+        const int f = p.tab_w[x0 + i], n = p.tab_w[p.Wout + x0 + i];
+        t.bad |= (f < 0) | (n < 1) | (n > p.mw) | (f + n > p.Win);
+        t.c0 = min(t.c0, f);
+        t.c1 = max(t.c1, f + n);
+    }
+    cut_rect(p, t);
+    for (int i = tid; i < th; i += 256) {
+        L.sfy[i] = p.tab_h[y0 + i] - t.r0;
+        L.sny[i] = clampi(p.tab_h[p.Hout + y0 + i], 1, p.mh);
+    }
+    for (int i = tid; i < tw; i += 256) {
+        L.sfx[i] = p.tab_w[x0 + i] - t.c0;
+        L.snx[i] = clampi(p.tab_w[p.Wout + x0 + i], 1, p.mw);
+    }
+    const float* wy = (const float*)(p.tab_h + 2 * (size_t)p.Hout) + (size_t)y0 * p.mh;
+    for (int i = tid; i < th * p.mh; i += 256) L.swy[i] = wy[i];
+    const float* wx = (const float*)(p.tab_w + 2 * (size_t)p.Wout) + (size_t)x0 * p.mw;
+    for (int i = tid; i < tw * p.mw; i += 256) L.swx[i] = wx[i];
+    return t;
+}
+
+// preprocess.axis_table(n_box, n_out) for output o, in float64 and without contraction, so that it is the same arithmetic as
+// the host's: centre s, half-width sup, taps first .. last inside the box (box coordinates).
+struct AxisTaps {
+    double s, sup;
+    int first, last;
+};
+__device__ __forceinline__ AxisTaps axis_taps(int n_box, int n_out, int o) {
+#pragma clang fp contract(off)
+    AxisTaps t;
+    const double ratio = (double)n_box / (double)n_out;
+    t.sup = ratio > 1.0 ? ratio : 1.0;
+    t.s = ((double)o + 0.5) * ratio - 0.5;
+    t.first = max((int)floor(t.s - t.sup) + 1, 0);
+    t.last = min((int)ceil(t.s + t.sup) - 1, n_box - 1);
+    return t;
+}
+__device__ __forceinline__ double axis_weight(const AxisTaps& t, int k) {
+#pragma clang fp contract(off)
+    return fmax(0.0, 1.0 - fabs((double)(t.first + k) - t.s) / t.sup);
+}
+
+// Step 1, source B: the filter of an h x w box at (top, left) of the image, generated in place; output column j of a mirrored
+// image is the unmirrored column Wout - 1 - j (same taps, same tap order).  One thread per row or column of the tile: weights in
+// ascending tap order, their sum accumulated in that order, each quotient rounded once to fp32.  first / last grow with the
+// output, so the rectangle follows from the tile's extreme outputs (with a mirror the two column ends swap).  The caller has
+// clamped the box into the image; counts are clamped to the pitches the launch was sized for.
+__device__ __forceinline__ TileRect tables_generated(const PrepP& p, const TileLds& L, int top, int left, int h, int w, int flip,
+                                                     int y0, int x0, int th, int tw) {
+    const int tid = threadIdx.x;
+    const int j0 = flip ? p.Wout - x0 - tw : x0;             // the tile's unmirrored columns are j0 .. j0 + tw - 1
+    TileRect t;
+    t.r0 = top + axis_taps(h, p.Hout, y0).first;
+    t.r1 = top + axis_taps(h, p.Hout, y0 + th - 1).last + 1;
+    t.c0 = left + axis_taps(w, p.Wout, j0).first;
+    t.c1 = left + axis_taps(w, p.Wout, j0 + tw - 1).last + 1;
+    t.bad = 0;
+    cut_rect(p, t);
+    for (int i = tid; i < th + tw; i += 256) {
+        const bool row = i < th;
+        const int e = row ? i : i - th;
+        const AxisTaps a = row ? axis_taps(h, p.Hout, y0 + e) : axis_taps(w, p.Wout, flip ? p.Wout - 1 - (x0 + e) : x0 + e);
+        const int m = row ? p.mh : p.mw;
+        const int n = clampi(a.last - a.first + 1, 1, m);
+        double sum = 0.0;
+        for (int k = 0; k < n; ++k) sum += axis_weight(a, k);
+        float* dst = (row ? L.swy : L.swx) + e * m;
+        for (int k = 0; k < n; ++k) dst[k] = (float)(axis_weight(a, k) / sum);
+        (row ? L.sfy : L.sfx)[e] = row ? top + a.first - t.r0 : left + a.first - t.c0;
+        (row ? L.sny : L.snx)[e] = n;
+    }
+    return t;
+}
+
 // One workgroup = one TH x TW tile of the cropped output of one image, all three channels.
-//   1. the tables of the tile's rows / columns -> LDS
+//   1. the tables of the tile's rows / columns -> LDS, read from global memory or generated (the two sources above)
 //   2. the input rectangle the tile's taps touch -> LDS as uint8, 16-byte global loads on 16-byte global addresses (a staged line
 //      starts `address & 15` bytes into its LDS line); chunks that would cross the ends of the image go byte by byte
 //   3. horizontal pass: every staged row x tile column x channel -> fp32 LDS
@@ -49,65 +192,18 @@ __device__ __forceinline__ int clampi(int v, int lo, int hi) { return v < lo ? l
 // >= 0 and <= the result, so the rounding error is bounded by (taps + 1) 2^-24 of the result itself whatever the image; and a
 // constant neighbourhood comes out as that constant exactly, however the fp32 weights happen to round (a flat image gives
 // fma(v, a, b) bit for bit, borders included).  Nothing is shared between workgroups: two runs give the same bits.
-// `img`: the first byte of image `b`, whose geometry and tables are p's; the output goes to image b of p.y.
+// Steps 2 - 4.  `img`: the first byte of image `b`, whose size is p's; `t`: the rectangle step 1 left; the output goes to image b
+// of p.y.
 template <bool CHW_IN, bool NHWC_OUT, bool BF16_OUT>
-__device__ __forceinline__ void preprocess_tile(const PrepP& p, const uint8_t* img, const int b) {
-    extern __shared__ uint4 smem4[];
+__device__ __forceinline__ void tile_passes(const PrepP& p, const TileLds& L, const TileRect& t, const uint8_t* img, const int b,
+                                            const int y0, const int x0, const int th, const int tw) {
     const int tid = threadIdx.x;
-    const int y0 = blockIdx.y * p.TH, x0 = blockIdx.x * p.TW;
-    const int th = min(p.TH, p.Hout - y0), tw = min(p.TW, p.Wout - x0);
     constexpr int PIX = CHW_IN ? 1 : 3;                      // bytes from one pixel of a channel to the next
-    const int lines_cap = CHW_IN ? 3 * p.rows_cap : p.rows_cap;
-
-    uint8_t* su8 = (uint8_t*)smem4;
-    float* sh = (float*)(su8 + (size_t)lines_cap * p.pitch);
-    int* sfy = (int*)(sh + (size_t)p.rows_cap * 3 * p.TW);
-    int* sny = sfy + p.TH;
-    int* sfx = sny + p.TH;
-    int* snx = sfx + p.TW;
-    float* swy = (float*)(snx + p.TW);
-    float* swx = swy + p.TH * p.mh;
-
-    // the input rectangle: uniform over the workgroup (scalar loads).  The tables are device data the host cannot see at launch
-    // time, so nothing read from them is trusted with an address: the rectangle is cut to the image and to the LDS it was sized
-    // for, tap indices are clamped into it below, and a table that needed either sets bit 2 of the device status word.
-    int r0 = p.Hin, r1 = 0, c0 = p.Win, c1 = 0, bad = 0;
-    for (int i = 0; i < th; ++i) {
-        const int f = p.tab_h[y0 + i], n = p.tab_h[p.Hout + y0 + i];
-        bad |= (f < 0) | (n < 1) | (n > p.mh) | (f + n > p.Hin);
-        r0 = min(r0, f);
-        r1 = max(r1, f + n);
-    }
-    for (int i = 0; i < tw; ++i) {
-        const int f = p.tab_w[x0 + i], n = p.tab_w[p.Wout + x0 + i];
-        bad |= (f < 0) | (n < 1) | (n > p.mw) | (f + n > p.Win);
-        c0 = min(c0, f);
-        c1 = max(c1, f + n);
-    }
-    r0 = clampi(r0, 0, p.Hin - 1);
-    c0 = clampi(c0, 0, p.Win - 1);
-    r1 = clampi(r1, r0 + 1, p.Hin);
-    c1 = clampi(c1, c0 + 1, p.Win);
-    if (r1 - r0 > p.rows_cap) { r1 = r0 + p.rows_cap; bad = 1; }
-    if (c1 - c0 > p.cols_cap) { c1 = c0 + p.cols_cap; bad = 1; }
-    const int nrows = r1 - r0, ncols = c1 - c0;
-    if (bad && tid == 0) atomicOr(p.status, 4u);
-
-    // 1. tables
-    for (int i = tid; i < th; i += 256) {
-        sfy[i] = p.tab_h[y0 + i] - r0;
-        sny[i] = clampi(p.tab_h[p.Hout + y0 + i], 1, p.mh);
-    }
-    for (int i = tid; i < tw; i += 256) {
-        sfx[i] = p.tab_w[x0 + i] - c0;
-        snx[i] = clampi(p.tab_w[p.Wout + x0 + i], 1, p.mw);
-    }
-    {
-        const float* wy = (const float*)(p.tab_h + 2 * (size_t)p.Hout) + (size_t)y0 * p.mh;
-        for (int i = tid; i < th * p.mh; i += 256) swy[i] = wy[i];
-        const float* wx = (const float*)(p.tab_w + 2 * (size_t)p.Wout) + (size_t)x0 * p.mw;
-        for (int i = tid; i < tw * p.mw; i += 256) swx[i] = wx[i];
-    }
+    uint8_t* su8 = L.su8;
+    float* sh = L.sh;
+    const int *sfy = L.sfy, *sny = L.sny, *sfx = L.sfx, *snx = L.snx;
+    const float *swy = L.swy, *swx = L.swx;
+    const int r0 = t.r0, c0 = t.c0, nrows = t.r1 - t.r0, ncols = t.c1 - t.c0;
 
     // 2. input rectangle
     const size_t img_bytes = (size_t)p.Hin * p.Win * 3;
@@ -183,6 +279,16 @@ __device__ __forceinline__ void preprocess_tile(const PrepP& p, const uint8_t* i
     }
 }
 
+
+template <bool CHW_IN, bool NHWC_OUT, bool BF16_OUT>
+__device__ __forceinline__ void preprocess_tile(const PrepP& p, const uint8_t* img, const int b) {
+    const int y0 = blockIdx.y * p.TH, x0 = blockIdx.x * p.TW;
+    const int th = min(p.TH, p.Hout - y0), tw = min(p.TW, p.Wout - x0);
+    const TileLds L = tile_lds<CHW_IN>(p);
+    const TileRect t = tables_from_global(p, L, y0, x0, th, tw);
+    tile_passes<CHW_IN, NHWC_OUT, BF16_OUT>(p, L, t, img, b, y0, x0, th, tw);
+}
+
 template <bool CHW_IN, bool NHWC_OUT, bool BF16_OUT>
 __global__ __launch_bounds__(256) void preprocess_u8_kernel(const PrepP p) {
     const int b = blockIdx.z;
@@ -213,18 +319,39 @@ __global__ __launch_bounds__(256) void preprocess_u8_ragged_kernel(const PrepRag
     preprocess_tile<CHW_IN, NHWC_OUT, BF16_OUT>(p, p.x + g.offset, b);
 }
 
+// The box record is device data too.  A record whose image would leave x forms no address: its tiles store nothing.  A box that
+// leaves its image is clamped into it, and a box that needs more taps than the launch's pitches has its counts clamped (in
+// tables_generated); each of these sets bit 2.  (Uniform over the workgroup, before any barrier.)
+template <bool CHW_IN, bool NHWC_OUT, bool BF16_OUT>
+__global__ __launch_bounds__(256) void preprocess_u8_boxes_kernel(const PrepBoxesP r) {
+    const int b = blockIdx.z;
+    const mv_preprocess_box g = r.rec[b];
+    PrepP p = r.p;
+    const long long img_bytes = (long long)g.Hin * g.Win * 3;
+    const bool ok = g.Hin >= 1 && g.Win >= 1 && img_bytes < (1LL << 31) && g.offset >= 0 && g.offset <= r.x_bytes - img_bytes;
+    if (!ok) {
+        if (threadIdx.x == 0) atomicOr(p.status, 4u);
+        return;
+    }
+    p.Hin = g.Hin; p.Win = g.Win;
+    const int top = clampi(g.top, 0, g.Hin - 1), left = clampi(g.left, 0, g.Win - 1);
+    const int h = clampi(g.h, 1, g.Hin - top), w = clampi(g.w, 1, g.Win - left);
+    const bool cut = top != g.top || left != g.left || h != g.h || w != g.w || taps_needed(h, p.Hout) > p.mh ||
+                     taps_needed(w, p.Wout) > p.mw;
+    if (cut && threadIdx.x == 0) atomicOr(p.status, 4u);
+    const int y0 = blockIdx.y * p.TH, x0 = blockIdx.x * p.TW;
+    const int th = min(p.TH, p.Hout - y0), tw = min(p.TW, p.Wout - x0);
+    const TileLds L = tile_lds<CHW_IN>(p);
+    const TileRect t = tables_generated(p, L, top, left, h, w, g.flip != 0, y0, x0, th, tw);
+    tile_passes<CHW_IN, NHWC_OUT, BF16_OUT>(p, L, t, p.x + g.offset, b, y0, x0, th, tw);
+}
+
 // input samples a run of T outputs can touch on one axis: (T - 1) * ratio between the first and the last centre, the support on
 // both sides, one for the inclusive end, one for rounding
 int span_cap(int T, int in, int out_full) {
     const double ratio = (double)in / (double)out_full, sup = ratio > 1.0 ? ratio : 1.0;
     const double s = (T - 1) * ratio + 2.0 * sup + 2.0;
     return s >= in ? in : (int)s;
-}
-
-int taps_needed(int in, int out_full) {
-    const double ratio = (double)in / (double)out_full, sup = ratio > 1.0 ? ratio : 1.0;
-    const double n = 2.0 * sup + 1.0;
-    return n >= in ? in : (int)n;
 }
 
 size_t lds_bytes(int TH, int TW, int rows_cap, int cols_cap, int in_chw, int mh, int mw, int* pitch) {
@@ -400,6 +527,74 @@ int mv_preprocess_u8_ragged_fwd(const void* x, int64_t x_bytes, void* y, const m
     hipStream_t st = (hipStream_t)stream;
     set_kernel_name("preprocess_u8_ragged");
     PREPROCESS_LAUNCH(preprocess_u8_ragged_kernel, r);
+    MV_LAUNCH_CHECK();
+    return MV_OK;
+}
+
+int mv_preprocess_u8_boxes_fwd(const void* x, int64_t x_bytes, void* y, const mv_preprocess_box* rec_host,
+                               const mv_preprocess_box* rec_dev, const float* a, const float* b, int B, int Hout, int Wout,
+                               int in_chw, int out_dtype, int out_nhwc, mv_stream_t stream) {
+    MV_CHECK_ARG(B > 0 && Hout > 0 && Wout > 0 && x_bytes > 0, "preprocess_u8_boxes: bad sizes");
+    MV_CHECK_ARG(out_dtype == MV_F32 || out_dtype == MV_BF16, "preprocess_u8_boxes: out_dtype must be MV_F32 or MV_BF16");
+    MV_CHECK_ARG(B <= 65535, "preprocess_u8_boxes: batch %d too large", B);
+    if (!x || !y || !rec_host || !rec_dev || !a || !b) {
+        set_error("preprocess_u8_boxes: null buffer");
+        return MV_E_UNSUPPORTED;
+    }
+    int mh = 0, mw = 0;
+    for (int i = 0; i < B; ++i) {
+        const mv_preprocess_box& g = rec_host[i];
+        MV_CHECK_ARG(g.Hin > 0 && g.Win > 0, "preprocess_u8_boxes: image %d: bad sizes", i);
+        const long long img_bytes = (long long)g.Hin * g.Win * 3;
+        MV_CHECK_ARG(img_bytes < (1LL << 31), "preprocess_u8_boxes: image %d: %dx%d too large", i, g.Hin, g.Win);
+        MV_CHECK_ARG(g.offset >= 0 && g.offset <= x_bytes - img_bytes,
+                     "preprocess_u8_boxes: image %d: %lld bytes at offset %lld do not lie inside the buffer of %lld bytes", i, img_bytes,
+                     (long long)g.offset, (long long)x_bytes);
+        MV_CHECK_ARG(g.h > 0 && g.w > 0 && g.top >= 0 && g.left >= 0 && (long long)g.top + g.h <= g.Hin &&
+                         (long long)g.left + g.w <= g.Win,
+                     "preprocess_u8_boxes: image %d: box %dx%d at (%d, %d) does not lie inside the image %dx%d", i, g.h, g.w, g.top,
+                     g.left, g.Hin, g.Win);
+        const int need_h = taps_needed(g.h, Hout), need_w = taps_needed(g.w, Wout);
+        if (need_h > MV_PREPROCESS_MAX_TAPS || need_w > MV_PREPROCESS_MAX_TAPS) {
+            set_error("preprocess_u8_boxes: image %d: box %dx%d -> %dx%d needs up to %d x %d taps; at most %d per axis (down-sampling "
+                      "by up to %.1f)", i, g.h, g.w, Hout, Wout, need_h, need_w, MV_PREPROCESS_MAX_TAPS,
+                      (MV_PREPROCESS_MAX_TAPS - 1) / 2.0);
+            return MV_E_UNSUPPORTED;
+        }
+        mh = need_h > mh ? need_h : mh;
+        mw = need_w > mw ? need_w : mw;
+    }
+    const size_t out_bytes = (size_t)B * 3 * Hout * Wout * dsize(out_dtype);
+    const uintptr_t xa = (uintptr_t)x, ya = (uintptr_t)y;
+    if (xa < ya + out_bytes && ya < xa + (size_t)x_bytes) {
+        set_error("preprocess_u8_boxes: input and output overlap");
+        return MV_E_UNSUPPORTED;
+    }
+    unsigned* status = device_status_word();
+    MV_CHECK_ARG(status != nullptr, "preprocess_u8_boxes: the device status word is not available");
+
+    // One tile and one LDS size per launch, as in the ragged entry: the largest spans and tap counts any box of the batch needs.
+    PrepBoxesP r;
+    PrepP& p = r.p;
+    p.x = (const uint8_t*)x; p.y = y; p.tab_h = nullptr; p.tab_w = nullptr; p.a = a; p.b = b; p.status = status;
+    p.Hin = 0; p.Win = 0; p.Hout = Hout; p.Wout = Wout; p.mh = mh; p.mw = mw;
+    r.rec = rec_dev; r.x_bytes = x_bytes;
+    size_t lds = 0;
+    if (!pick_tile(p, in_chw, &lds, [&](int TH, int TW, int* rows, int* cols) {
+            *rows = *cols = 0;
+            for (int i = 0; i < B; ++i) {
+                *rows = std::max(*rows, span_cap(TH, rec_host[i].h, Hout));
+                *cols = std::max(*cols, span_cap(TW, rec_host[i].w, Wout));
+            }
+        })) {
+        set_error("preprocess_u8_boxes: the batch does not fit the LDS tile (%zu bytes for the smallest tile)", lds);
+        return MV_E_UNSUPPORTED;
+    }
+    const dim3 grid((Wout + p.TW - 1) / p.TW, (Hout + p.TH - 1) / p.TH, B);
+    MV_CHECK_ARG(grid.y <= 65535, "preprocess_u8_boxes: %d output rows are too many tiles", Hout);
+    hipStream_t st = (hipStream_t)stream;
+    set_kernel_name("preprocess_u8_boxes");
+    PREPROCESS_LAUNCH(preprocess_u8_boxes_kernel, r);
     MV_LAUNCH_CHECK();
     return MV_OK;
 }

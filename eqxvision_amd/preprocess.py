@@ -15,6 +15,13 @@ A list of images takes `mv_preprocess_u8_ragged_fwd`: the images packed tightly 
 buffer, one record per image (`RECORD`) that says where they lie.  The geometry belongs to that call, so nothing is kept on the
 device and only the per-axis tables are cached, on the host and bounded (`AXIS_CACHE`).
 
+    x = eqv.preprocess.imagenet_train(images_u8, key)      # RandomResizedCrop(224) -> RandomHorizontalFlip -> ToTensor -> Normalize
+
+The training preset crops FIRST and resizes the crop, with a fresh random box per image and step, so tables would be rebuilt and
+uploaded on every call.  `mv_preprocess_u8_boxes_fwd` takes one 40-byte record per image (`BOX`: where the image lies, the box,
+whether to mirror) and generates the filter of each tile in the kernel, in float64, by the formulas of `axis_table`; the host
+only draws the boxes (`random_resized_crop_boxes`, `random_flips`).  `crop_resize_normalize` is the deterministic core.
+
 Outputs: NCHW in fp32 or bf16 are what the models' entry kernels read without a conversion launch (`_act.wrap` takes a [B, 3, H, W]
 tensor as the image batch; the entry convolutions read fp32 or bf16).  The models have no NHWC entry, so `imagenet_eval` does not
 offer one; `resize_crop_normalize(layout="nhwc")` returns a plain tensor for other consumers.
@@ -27,6 +34,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from . import random as _random
 from ._act import DT, TORCH_DT, device, empty, stream_ptr
 from ._act import _tls as _act_tls
 
@@ -342,3 +350,148 @@ def imagenet_eval(images_u8, resize=256, crop=224, mean=IMAGENET_MEAN, std=IMAGE
     _, _, _, hin, win = _check_input(images_u8, channels_last)
     hr, wr = resized_size(hin, win, resize)
     return resize_crop_normalize(images_u8, (hr, wr), center_crop_box(hr, wr, crop), mean, std, dtype, layout, channels_last)
+
+
+# ---- the training transform: crop a box, resize it, mirror it -> mv_preprocess_u8_boxes_fwd, one launch, no tables --------------
+
+# `mv_preprocess_box` of include/eqxvision_amd.h, 40 bytes
+BOX = np.dtype([("offset", "<i8"), ("Hin", "<i4"), ("Win", "<i4"), ("top", "<i4"), ("left", "<i4"), ("h", "<i4"), ("w", "<i4"),
+                ("flip", "<i4"), ("pad", "<i4")])
+RRC_ATTEMPTS = 10      # torchvision's RandomResizedCrop.get_params tries ten boxes before it falls back
+
+
+def random_resized_crop_boxes(key, sizes, scale=(0.08, 1.0), ratio=(3.0 / 4.0, 4.0 / 3.0)) -> np.ndarray:
+    """torchvision's `RandomResizedCrop.get_params` for B images: `sizes` [(H, W)] -> int32 [B, 4] of (top, left, h, w) in source
+    pixels.  Host only.  Image i draws from `random.split(key, B)[i]`: with u = random.uniform(k_i, (10, 4)), attempt t takes
+    area = H W (scale0 + u[t, 0] (scale1 - scale0)), aspect = exp(log r0 + u[t, 1] (log r1 - log r0)),
+    w = round(sqrt(area aspect)), h = round(sqrt(area / aspect)); the first attempt that fits the image wins and is placed at
+    top = min(int(u[t, 2] (H - h + 1)), H - h), left likewise from u[t, 3].  If none fits: the largest centred box whose aspect
+    lies inside `ratio` (torchvision's fallback).
+    This is torchvision's DISTRIBUTION, not torch's random stream: the same seed gives other boxes than torchvision does."""
+    sizes = [(int(h), int(w)) for h, w in sizes]
+    s0, s1 = (float(v) for v in scale)
+    r0, r1 = (float(v) for v in ratio)
+    if not (0.0 < s0 <= s1) or not (0.0 < r0 <= r1):
+        raise ValueError(f"preprocess: scale {scale} and ratio {ratio} must be positive (min, max) pairs")
+    if len(sizes) == 0:
+        raise ValueError("preprocess: no image sizes")
+    out = np.zeros((len(sizes), 4), np.int32)
+    keys = _random.split(key, len(sizes))
+    log0, log1 = np.log(np.float64(r0)), np.log(np.float64(r1))
+    for i, (H, W) in enumerate(sizes):
+        if H < 1 or W < 1:
+            raise ValueError(f"preprocess: image {i}: empty image {H}x{W}")
+        u = np.asarray(_random.uniform(keys[i], (RRC_ATTEMPTS, 4)), np.float64)
+        for t in range(RRC_ATTEMPTS):
+            area = H * W * (s0 + u[t, 0] * (s1 - s0))
+            ar = np.exp(log0 + u[t, 1] * (log1 - log0))
+            w, h = int(round(float(np.sqrt(area * ar)))), int(round(float(np.sqrt(area / ar))))
+            if 0 < w <= W and 0 < h <= H:
+                out[i] = (min(int(u[t, 2] * (H - h + 1)), H - h), min(int(u[t, 3] * (W - w + 1)), W - w), h, w)
+                break
+        else:
+            if W / H < r0:
+                w = W
+                h = int(round(w / r0))
+            elif W / H > r1:
+                h = H
+                w = int(round(h * r1))
+            else:
+                h, w = H, W
+            out[i] = ((H - h) // 2, (W - w) // 2, h, w)
+    return out
+
+
+def random_flips(key, B, p=0.5) -> np.ndarray:
+    """bool [B]: `random.uniform(key, (B,)) < p` (torchvision's RandomHorizontalFlip, one draw per image)."""
+    return np.asarray(_random.uniform(key, (int(B),)) < p, bool)
+
+
+def boxes_plan(sizes, boxes, flip, size):
+    """Host half of `crop_resize_normalize`, no device involved: `sizes` [(Hin, Win)] of tightly packed images in order, `boxes`
+    [B, 4] of (top, left, h, w), `flip` None or [B].  Returns (records, (Hout, Wout)), `records` a BOX array [B]; every refusal is
+    a ValueError that names the image."""
+    B = len(sizes)
+    hout, wout = (int(size), int(size)) if isinstance(size, (int, np.integer)) else (int(size[0]), int(size[1]))
+    if hout < 1 or wout < 1:
+        raise ValueError(f"preprocess: output size {(hout, wout)} must be positive")
+    bx = np.asarray(boxes)
+    if bx.dtype.kind not in "iu" or bx.shape != (B, 4):
+        raise ValueError(f"preprocess: boxes must be integers [{B}, 4] of (top, left, h, w), one box per image, got "
+                         f"{bx.dtype} {tuple(bx.shape)}")
+    fl = np.zeros(B, bool) if flip is None else np.asarray(flip)
+    if fl.shape != (B,):
+        raise ValueError(f"preprocess: flip must hold one flag per image ({B}), got shape {tuple(fl.shape)}")
+    rec = np.zeros(B, BOX)
+    offset = 0
+    for i, (hin, win) in enumerate(sizes):
+        who = f"preprocess: image {i}"
+        top, left, h, w = (int(v) for v in bx[i])
+        if h < 1 or w < 1 or top < 0 or left < 0 or top + h > hin or left + w > win:
+            raise ValueError(f"{who}: box {h}x{w} at ({top}, {left}) does not lie inside the image {hin}x{win}")
+        _check_taps(h, w, hout, wout, who)
+        rec[i] = (offset, hin, win, top, left, h, w, int(bool(fl[i])), 0)
+        offset += hin * win * 3
+    return rec, (hout, wout)
+
+
+def crop_resize_normalize(images_u8, boxes, size, flip=None, mean=IMAGENET_MEAN, std=IMAGENET_STD, dtype="fp32", layout="nchw",
+                          channels_last=None) -> torch.Tensor:
+    """Crop box i = (top, left, h, w) out of image i (source pixels), resize it to `size` (an int or (Hout, Wout)) with the
+    antialiased triangle filter of `resize_crop_normalize` -- its taps stop at the edge of the BOX, as if the crop had been copied
+    out first -- mirror it left-right where `flip[i]`, and return (x / 255 - mean) / std as a device tensor [B, 3, Hout, Wout]
+    (`layout="nchw"`) or [B, Hout, Wout, 3], fp32 or bf16.  `images_u8`: [B, H, W, 3] or [B, 3, H, W], one image without the batch
+    axis (then `boxes` is one box and the result has no batch axis), or a list of images of different sizes (packed with
+    `pack_images`); numpy or torch, host or device.  One launch of `mv_preprocess_u8_boxes_fwd` on the current stream for every
+    form: the kernel generates the filter of each box itself, so a fresh random box per image and step costs one 40-byte record.
+    The call cannot be recorded by `filter_jit`: the boxes belong to this one call."""
+    if getattr(_act_tls, "keep", None) is not None:
+        raise ValueError("preprocess: crop_resize_normalize cannot be recorded by filter_jit: its boxes, flips and offsets belong "
+                         "to this one call, and a replay would apply them to other images; preprocess outside the recorded "
+                         "function")
+    if isinstance(images_u8, (list, tuple)):
+        chw, sizes = _check_list(images_u8, channels_last)
+        batched = True
+    else:
+        x, batched, chw, hin, win = _check_input(images_u8, channels_last)
+        sizes = [(hin, win)] * (int(x.shape[0]) if batched else 1)
+        if batched and len(sizes) == 0:
+            raise ValueError("preprocess: the batch of images is empty")
+        if not batched:
+            boxes = np.asarray(boxes).reshape(1, -1) if np.asarray(boxes).ndim == 1 else boxes
+            flip = flip if flip is None else np.asarray(flip).reshape(-1)
+    _check_output(dtype, layout)
+    rec, (hout, wout) = boxes_plan(sizes, boxes, flip, size)
+    affine(mean, std)                                        # validates before the device is touched
+    a, b = _device_affine(mean, std)
+    if isinstance(images_u8, (list, tuple)):
+        t = pack_images(images_u8)
+    else:
+        t = x if isinstance(x, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(x))
+        t = t.to(device(), non_blocking=True).contiguous()
+    rec_dev = torch.from_numpy(rec.view(np.uint8)).to(device())
+    B = len(sizes)
+    y = empty((B, 3, hout, wout) if layout == "nchw" else (B, hout, wout, 3), TORCH_DT[dtype])
+    _lib.call("mv_preprocess_u8_boxes_fwd", t.data_ptr(), t.numel(), y.data_ptr(), rec.ctypes.data, rec_dev.data_ptr(),
+              a.data_ptr(), b.data_ptr(), B, hout, wout, int(chw), DT[dtype], int(layout == "nhwc"), stream_ptr())
+    return y if batched else y[0]
+
+
+def imagenet_train(images_u8, key, size=224, scale=(0.08, 1.0), ratio=(3.0 / 4.0, 4.0 / 3.0), flip_p=0.5, mean=IMAGENET_MEAN,
+                   std=IMAGENET_STD, dtype="fp32", channels_last=None) -> torch.Tensor:
+    """torchvision's ImageNet training preset on the device: RandomResizedCrop(size, scale, ratio) -> RandomHorizontalFlip(flip_p)
+    -> ToTensor -> Normalize, one launch.  `key` is split in two: `random_resized_crop_boxes` draws the boxes from the first
+    half, `random_flips` the flips from the second; the same key gives the same tensor.  Returns [B, 3, size, size], fp32 or
+    bf16: what `eqv.vmap(net)` reads.  `images_u8`: as for `crop_resize_normalize`."""
+    if isinstance(images_u8, (list, tuple)):
+        _, sizes = _check_list(images_u8, channels_last)
+        single = False
+    else:
+        x, batched, _, hin, win = _check_input(images_u8, channels_last)
+        sizes, single = [(hin, win)] * (int(x.shape[0]) if batched else 1), not batched
+        if len(sizes) == 0:
+            raise ValueError("preprocess: the batch of images is empty")
+    k_box, k_flip = _random.split(key, 2)
+    boxes = random_resized_crop_boxes(k_box, sizes, scale, ratio)
+    flips = random_flips(k_flip, len(sizes), flip_p)
+    return crop_resize_normalize(images_u8, boxes[0] if single else boxes, size, flips, mean, std, dtype, "nchw", channels_last)

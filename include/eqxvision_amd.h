@@ -77,7 +77,7 @@ int mv_flags_epoch(void);                        /* hash of this thread's curren
 /* Device status word: kernels that detect a broken protocol at run time record it here instead of trapping (a trap poisons the whole
  * HIP context, graph replays and other streams included).  bit 0: a split-K block gave up waiting for its partner's partial sums
  * (dirty / shared scratch; the tile it wrote is incomplete).  bit 1: mv_softmax_xent_map_f32 met a label outside [0, C) on a counted
- * pixel (the pixel was left out; loss, gradient and sums of that call are not those of the labels given).  bit 2: mv_preprocess_u8_fwd / mv_preprocess_u8_ragged_fwd was given a tap table (or a device record) that points outside the image or
+ * pixel (the pixel was left out; loss, gradient and sums of that call are not those of the labels given).  bit 2: mv_preprocess_u8_fwd / mv_preprocess_u8_ragged_fwd / mv_preprocess_u8_boxes_fwd was given a tap table (or a device record) that points outside the image or
  * outside what its geometry can need (the taps were clamped; the output of that call is not the resize asked for).  Writes the word to *status, clears it if `clear`; SYNCHRONISES the
  * device -- call it where the host synchronises anyway (after a forward, at the end of a test). */
 int mv_device_status(int clear, unsigned* status);
@@ -575,6 +575,30 @@ int mv_preprocess_u8_ragged_fwd(const void* x, int64_t x_bytes, void* y, const m
                                 const mv_preprocess_image* rec_dev, const void* tab, int64_t tab_words, const float* a,
                                 const float* b, int B, int Hout, int Wout, int in_chw, int out_dtype, int out_nhwc,
                                 mv_stream_t stream);
+
+/* The training transform in one launch (torchvision's RandomResizedCrop -> RandomHorizontalFlip -> ToTensor -> Normalize, the
+ * random draws made by the caller): image i of a packed buffer x (as above: any sizes, one record each) is CROPPED to the h x w
+ * box at (top, left) of its SOURCE pixels, the box is resized to Hout x Wout, mirrored left-right if flip != 0, and stored as
+ * y = acc * a[c] + b[c] like mv_preprocess_u8_fwd (same layouts, dtypes and epilogue).  The filter is that entry's -- half-pixel
+ * centres, support max(1, n_box / n_out), triangle weights normalised over the taps present -- with "present" meaning inside the
+ * BOX: the result has the bits of a call on the box copied out as an image of its own.  There are no tables: the kernel
+ * generates each tile's filter in float64 (centre s = (o + 0.5) n_box / n_out - 0.5; first = floor(s - sup) + 1 and
+ * last = ceil(s + sup) - 1 clipped to the box; weights 1 - |x - s| / sup in ascending tap order, summed in that order, each
+ * quotient rounded once to fp32), so a weight is within one fp32 rounding of the float64 value.  Output column j of a mirrored
+ * image is the unmirrored column Wout - 1 - j, taps and tap order unchanged.  No atomics, sums in tap order: same bits every run.
+ * rec_host (HOST memory) is validated in full before anything is launched -- image inside x, box non-empty and inside its image
+ * (MV_E_INVALID), at most MV_PREPROCESS_MAX_TAPS taps per axis, min(n_box, int(2 max(1, n_box / n_out) + 1)), and x and y not
+ * overlapping (MV_E_UNSUPPORTED), each message naming the image -- and sizes the one tile of the launch by the LDS rule of the
+ * ragged entry.  rec_dev (DEVICE memory, same contents) is what the kernel reads; it forms no address from it unchecked: a record
+ * whose image leaves x stores nothing, a box that leaves its image is clamped into it, tap counts are clamped to the pitches of
+ * the launch; each sets bit 2 of mv_device_status. */
+typedef struct mv_preprocess_box {
+    int64_t offset;                                  /* byte offset of the image in x */
+    int32_t Hin, Win, top, left, h, w, flip, pad;    /* box in SOURCE pixels; flip != 0: mirror left-right */
+} mv_preprocess_box;                                 /* 40 bytes, no padding */
+int mv_preprocess_u8_boxes_fwd(const void* x, int64_t x_bytes, void* y, const mv_preprocess_box* rec_host,
+                               const mv_preprocess_box* rec_dev, const float* a, const float* b, int B, int Hout, int Wout,
+                               int in_chw, int out_dtype, int out_nhwc, mv_stream_t stream);
 
 /* eqx.nn.MaxPool2d (resnet.py:254, alexnet.py:46,49,56): -inf padding, floor output size. */
 int mv_maxpool2d_nhwc_fwd(const void* x, void* y, int N, int H, int W, int C,
