@@ -109,6 +109,7 @@ PROTOTYPES = {
     "mv_preprocess_u8_fwd": [_vp] * 6 + [_i] * 14 + [_vp],
     "mv_preprocess_u8_ragged_fwd": [_vp, _i64, _vp, _vp, _vp, _vp, _i64, _vp, _vp] + [_i] * 6 + [_vp],
     "mv_preprocess_u8_boxes_fwd": [_vp, _i64, _vp, _vp, _vp, _vp, _vp] + [_i] * 6 + [_vp],
+    "mv_preprocess_u8_seg_fwd": [_vp, _i64, _vp, _i64] + [_vp] * 6 + [_i] * 8 + [_vp],
     "mv_maxpool2d_nhwc_fwd": [_vp, _vp] + [_i] * 10 + [_i, _vp],
     "mv_adaptive_avgpool2d_nhwc_fwd": [_vp, _vp] + [_i] * 6 + [_i, _i, _vp],
     "mv_layernorm_fwd": [_vp, _vp, _vp, _vp, _i64, _i, _i64, _f, _i, _i, _vp],

@@ -3,9 +3,11 @@
 // The filter lives in two tap tables the host builds in float64 (eqxvision_amd/preprocess.py: axis_table); the kernel only
 // applies them, so the same entry serves the antialiased ImageNet preset and plain two-tap up-sampling.  HBM-bound gather, no
 // matrix work: every input byte a tile needs is read once into LDS, both passes run out of LDS, every output is stored once.
-// Three entries share the tile body: one image size per launch (mv_preprocess_u8_fwd), one record per image for a packed batch
-// of any sizes (mv_preprocess_u8_ragged_fwd), and one box per image that is cropped FIRST and then resized, mirrored or not
-// (mv_preprocess_u8_boxes_fwd: the training transform; its filter is generated in the tile, no tables).  A launch has ONE tile
+// Four entries share the tile body: one image size per launch (mv_preprocess_u8_fwd), one record per image for a packed batch
+// of any sizes (mv_preprocess_u8_ragged_fwd), one box per image that is cropped FIRST and then resized, mirrored or not
+// (mv_preprocess_u8_boxes_fwd: the training transform; its filter is generated in the tile, no tables), and one window per image
+// of the WHOLE image resized, mirrored and padded, with the label map gathered alongside (mv_preprocess_u8_seg_fwd: the
+// segmentation training transform; the same generated filter on the part of a tile that is not padding).  A launch has ONE tile
 // and ONE LDS size; the record entries size them for the largest spans and pitches of their batch, so one steeply down-sampled
 // image lowers the occupancy of the whole launch (accepted).
 #include "common.h"
@@ -53,6 +55,18 @@ struct PrepBoxesP {
     PrepP p;
     const mv_preprocess_box* rec;
     long long x_bytes;
+};
+
+// mv_preprocess_u8_seg_fwd: one record per image (blockIdx.z), no tables.  In `p`, x is the packed image buffer, Hout x Wout the
+// window, mh / mw / rows_cap / cols_cap / pitch the largest any resize of the batch needs; Hin, Win, tab_h and tab_w are not used.
+// m / labels: the packed masks and the int32 label maps, both NULL for an image-only launch.
+struct PrepSegP {
+    PrepP p;
+    const mv_preprocess_seg* rec;
+    const uint8_t* m;
+    int* labels;
+    long long x_bytes, m_bytes;
+    int image_fill, mask_fill;
 };
 
 // The LDS of one tile: staged uint8 lines | fp32 horizontal sums | first / count of the tile's rows and columns | their weights.
@@ -149,26 +163,27 @@ __device__ __forceinline__ double axis_weight(const AxisTaps& t, int k) {
     return fmax(0.0, 1.0 - fabs((double)(t.first + k) - t.s) / t.sup);
 }
 
-// Step 1, source B: the filter of an h x w box at (top, left) of the image, generated in place; output column j of a mirrored
-// image is the unmirrored column Wout - 1 - j (same taps, same tap order).  One thread per row or column of the tile: weights in
-// ascending tap order, their sum accumulated in that order, each quotient rounded once to fp32.  first / last grow with the
-// output, so the rectangle follows from the tile's extreme outputs (with a mirror the two column ends swap).  The caller has
-// clamped the box into the image; counts are clamped to the pitches the launch was sized for.
-__device__ __forceinline__ TileRect tables_generated(const PrepP& p, const TileLds& L, int top, int left, int h, int w, int flip,
-                                                     int y0, int x0, int th, int tw) {
+// Step 1, generated: the filter of an h x w box at (top, left) of the image resized to Hr x Wr, for rows y0 .. y0 + th - 1 and
+// columns x0 .. x0 + tw - 1 of the resized box; column j of a mirrored result is the unmirrored column Wr - 1 - j (same taps,
+// same tap order).  One thread per row or column of the tile: weights in ascending tap order, their sum accumulated in that
+// order, each quotient rounded once to fp32.  first / last grow with the output, so the rectangle follows from the tile's extreme
+// outputs (with a mirror the two column ends swap).  The caller has clamped the box into the image; counts are clamped to the
+// pitches the launch was sized for.
+__device__ __forceinline__ TileRect tables_resized(const PrepP& p, const TileLds& L, int top, int left, int h, int w, int Hr, int Wr,
+                                                   int flip, int y0, int x0, int th, int tw) {
     const int tid = threadIdx.x;
-    const int j0 = flip ? p.Wout - x0 - tw : x0;             // the tile's unmirrored columns are j0 .. j0 + tw - 1
+    const int j0 = flip ? Wr - x0 - tw : x0;                 // the tile's unmirrored columns are j0 .. j0 + tw - 1
     TileRect t;
-    t.r0 = top + axis_taps(h, p.Hout, y0).first;
-    t.r1 = top + axis_taps(h, p.Hout, y0 + th - 1).last + 1;
-    t.c0 = left + axis_taps(w, p.Wout, j0).first;
-    t.c1 = left + axis_taps(w, p.Wout, j0 + tw - 1).last + 1;
+    t.r0 = top + axis_taps(h, Hr, y0).first;
+    t.r1 = top + axis_taps(h, Hr, y0 + th - 1).last + 1;
+    t.c0 = left + axis_taps(w, Wr, j0).first;
+    t.c1 = left + axis_taps(w, Wr, j0 + tw - 1).last + 1;
     t.bad = 0;
     cut_rect(p, t);
     for (int i = tid; i < th + tw; i += 256) {
         const bool row = i < th;
         const int e = row ? i : i - th;
-        const AxisTaps a = row ? axis_taps(h, p.Hout, y0 + e) : axis_taps(w, p.Wout, flip ? p.Wout - 1 - (x0 + e) : x0 + e);
+        const AxisTaps a = row ? axis_taps(h, Hr, y0 + e) : axis_taps(w, Wr, flip ? Wr - 1 - (x0 + e) : x0 + e);
         const int m = row ? p.mh : p.mw;
         const int n = clampi(a.last - a.first + 1, 1, m);
         double sum = 0.0;
@@ -179,6 +194,19 @@ __device__ __forceinline__ TileRect tables_generated(const PrepP& p, const TileL
         (row ? L.sny : L.snx)[e] = n;
     }
     return t;
+}
+
+// Step 1, source B: a box resized to the output itself (mv_preprocess_u8_boxes_fwd); the tile is a tile of the output.
+__device__ __forceinline__ TileRect tables_generated(const PrepP& p, const TileLds& L, int top, int left, int h, int w, int flip,
+                                                     int y0, int x0, int th, int tw) {
+    return tables_resized(p, L, top, left, h, w, p.Hout, p.Wout, flip, y0, x0, th, tw);
+}
+
+// Step 1, source C: the whole image resized to Hr x Wr, of which the output is a window (mv_preprocess_u8_seg_fwd); r0, q0: the
+// resized row / mirrored column of the tile's first output, th_v x tw_v: the prefix of the tile that lies inside Hr x Wr.
+__device__ __forceinline__ TileRect tables_window(const PrepP& p, const TileLds& L, int Hr, int Wr, int flip, int r0, int q0,
+                                                  int th_v, int tw_v) {
+    return tables_resized(p, L, 0, 0, p.Hin, p.Win, Hr, Wr, flip, r0, q0, th_v, tw_v);
 }
 
 // One workgroup = one TH x TW tile of the cropped output of one image, all three channels.
@@ -344,6 +372,85 @@ __global__ __launch_bounds__(256) void preprocess_u8_boxes_kernel(const PrepBoxe
     const TileLds L = tile_lds<CHW_IN>(p);
     const TileRect t = tables_generated(p, L, top, left, h, w, g.flip != 0, y0, x0, th, tw);
     tile_passes<CHW_IN, NHWC_OUT, BF16_OUT>(p, L, t, p.x + g.offset, b, y0, x0, th, tw);
+}
+
+// The elements of a th x tw tile outside its valid th_v x tw_v prefix <- v[c], in the store order of tile_passes' step 4.
+template <bool NHWC_OUT, bool BF16_OUT>
+__device__ __forceinline__ void tile_fill(const PrepP& p, const int b, const int y0, const int x0, const int th, const int tw,
+                                          const int th_v, const int tw_v, const float v0, const float v1, const float v2) {
+    for (int it = threadIdx.x; it < th * 3 * tw; it += 256) {
+        int y, c, x;
+        if (NHWC_OUT) {
+            const int yx = it / 3;
+            c = it - yx * 3;
+            y = yx / tw;
+            x = yx - y * tw;
+        } else {
+            const int yc = it / tw;
+            x = it - yc * tw;
+            y = yc / 3;
+            c = yc - y * 3;
+        }
+        if (y < th_v && x < tw_v) continue;
+        const float v = c == 0 ? v0 : (c == 1 ? v1 : v2);
+        const size_t o = NHWC_OUT ? (((size_t)b * p.Hout + y0 + y) * p.Wout + x0 + x) * 3 + c
+                                  : (((size_t)b * 3 + c) * p.Hout + y0 + y) * p.Wout + x0 + x;
+        if (BF16_OUT) ((bf16_t*)p.y)[o] = f2bf(v);
+        else ((float*)p.y)[o] = v;
+    }
+}
+
+// The seg record is device data too.  A record whose image or mask would leave its buffer forms no address: its tiles store
+// nothing.  The resized size is raised to 1 x 1, the window origin is clamped into the padded image max(Hr, Hout) x max(Wr, Wout),
+// and a resize that needs more taps than the launch's pitches has its counts clamped (in tables_resized); each of these sets bit
+// 2.  (Uniform over the workgroup, before any barrier.)  The padding is a suffix of rows and columns, so the part of a tile that
+// lies inside the resized image is a prefix th_v x tw_v: that prefix goes through the tile body, the rest of the tile is the fill,
+// and a tile that lies wholly in the padding stages nothing.  Labels: one thread per output pixel of the tile, rows of int32.
+template <bool CHW_IN, bool NHWC_OUT, bool BF16_OUT>
+__global__ __launch_bounds__(256) void preprocess_u8_seg_kernel(const PrepSegP r) {
+    const int b = blockIdx.z;
+    const mv_preprocess_seg g = r.rec[b];
+    PrepP p = r.p;
+    const long long px = (long long)g.Hin * g.Win;
+    const bool ok = g.Hin >= 1 && g.Win >= 1 && px * 3 < (1LL << 31) && g.offset >= 0 && g.offset <= r.x_bytes - px * 3 &&
+                    (!r.m || (g.mask_offset >= 0 && g.mask_offset <= r.m_bytes - px));
+    if (!ok) {
+        if (threadIdx.x == 0) atomicOr(p.status, 4u);
+        return;
+    }
+    p.Hin = g.Hin; p.Win = g.Win;
+    const int Hr = max(g.Hr, 1), Wr = max(g.Wr, 1);
+    const int top = clampi(g.top, 0, max(Hr, p.Hout) - p.Hout), left = clampi(g.left, 0, max(Wr, p.Wout) - p.Wout);
+    const bool cut = Hr != g.Hr || Wr != g.Wr || top != g.top || left != g.left || taps_needed(g.Hin, Hr) > p.mh ||
+                     taps_needed(g.Win, Wr) > p.mw;
+    if (cut && threadIdx.x == 0) atomicOr(p.status, 4u);
+    const int flip = g.flip != 0;
+    const int y0 = blockIdx.y * p.TH, x0 = blockIdx.x * p.TW;
+    const int th = min(p.TH, p.Hout - y0), tw = min(p.TW, p.Wout - x0);
+    const int r0 = top + y0, q0 = left + x0;                 // < max(Hr, Hout), max(Wr, Wout): no overflow
+    const int th_v = clampi(Hr - r0, 0, th), tw_v = clampi(Wr - q0, 0, tw);
+    if (th_v > 0 && tw_v > 0) {
+        const TileLds L = tile_lds<CHW_IN>(p);
+        const TileRect t = tables_window(p, L, Hr, Wr, flip, r0, q0, th_v, tw_v);
+        tile_passes<CHW_IN, NHWC_OUT, BF16_OUT>(p, L, t, p.x + g.offset, b, y0, x0, th_v, tw_v);
+    }
+    if (th_v < th || tw_v < tw) {
+        const float f = (float)r.image_fill;
+        tile_fill<NHWC_OUT, BF16_OUT>(p, b, y0, x0, th, tw, th_v, tw_v, fmaf(f, p.a[0], p.b[0]), fmaf(f, p.a[1], p.b[1]),
+                                      fmaf(f, p.a[2], p.b[2]));
+    }
+    if (!r.labels) return;
+    const uint8_t* mask = r.m + g.mask_offset;
+    for (int it = threadIdx.x; it < th * tw; it += 256) {
+        const int i = it / tw, j = it - i * tw;
+        int v = r.mask_fill;
+        if (i < th_v && j < tw_v) {
+            const int q = q0 + j, cr = flip ? Wr - 1 - q : q;
+            const long long sr = ((2LL * (r0 + i) + 1) * g.Hin) / (2LL * Hr), sc = ((2LL * cr + 1) * g.Win) / (2LL * Wr);
+            v = mask[min(sr, (long long)g.Hin - 1) * g.Win + min(sc, (long long)g.Win - 1)];
+        }
+        r.labels[((size_t)b * p.Hout + y0 + i) * p.Wout + x0 + j] = v;
+    }
 }
 
 // input samples a run of T outputs can touch on one axis: (T - 1) * ratio between the first and the last centre, the support on
@@ -595,6 +702,88 @@ int mv_preprocess_u8_boxes_fwd(const void* x, int64_t x_bytes, void* y, const mv
     hipStream_t st = (hipStream_t)stream;
     set_kernel_name("preprocess_u8_boxes");
     PREPROCESS_LAUNCH(preprocess_u8_boxes_kernel, r);
+    MV_LAUNCH_CHECK();
+    return MV_OK;
+}
+
+int mv_preprocess_u8_seg_fwd(const void* x, int64_t x_bytes, const void* m, int64_t m_bytes, void* y, int32_t* labels,
+                             const mv_preprocess_seg* rec_host, const mv_preprocess_seg* rec_dev, const float* a, const float* b,
+                             int B, int Hout, int Wout, int image_fill, int mask_fill, int in_chw, int out_dtype, int out_nhwc,
+                             mv_stream_t stream) {
+    MV_CHECK_ARG(B > 0 && Hout > 0 && Wout > 0 && x_bytes > 0, "preprocess_u8_seg: bad sizes");
+    MV_CHECK_ARG(out_dtype == MV_F32 || out_dtype == MV_BF16, "preprocess_u8_seg: out_dtype must be MV_F32 or MV_BF16");
+    MV_CHECK_ARG(B <= 65535, "preprocess_u8_seg: batch %d too large", B);
+    MV_CHECK_ARG((m != nullptr) == (labels != nullptr), "preprocess_u8_seg: masks and labels go together, got %s without %s",
+                 m ? "masks" : "labels", m ? "labels" : "masks");
+    MV_CHECK_ARG(!m || m_bytes > 0, "preprocess_u8_seg: bad sizes");
+    MV_CHECK_ARG(image_fill >= 0 && image_fill <= 255 && mask_fill >= 0 && mask_fill <= 255,
+                 "preprocess_u8_seg: image_fill %d and mask_fill %d must lie in [0, 255]", image_fill, mask_fill);
+    if (!x || !y || !rec_host || !rec_dev || !a || !b) {
+        set_error("preprocess_u8_seg: null buffer");
+        return MV_E_UNSUPPORTED;
+    }
+    int mh = 0, mw = 0;
+    for (int i = 0; i < B; ++i) {
+        const mv_preprocess_seg& g = rec_host[i];
+        MV_CHECK_ARG(g.Hin > 0 && g.Win > 0 && g.Hr > 0 && g.Wr > 0, "preprocess_u8_seg: image %d: bad sizes", i);
+        const long long px = (long long)g.Hin * g.Win;
+        MV_CHECK_ARG(px * 3 < (1LL << 31), "preprocess_u8_seg: image %d: %dx%d too large", i, g.Hin, g.Win);
+        MV_CHECK_ARG(g.offset >= 0 && g.offset <= x_bytes - px * 3,
+                     "preprocess_u8_seg: image %d: %lld bytes at offset %lld do not lie inside the buffer of %lld bytes", i, px * 3,
+                     (long long)g.offset, (long long)x_bytes);
+        MV_CHECK_ARG(!m || (g.mask_offset >= 0 && g.mask_offset <= m_bytes - px),
+                     "preprocess_u8_seg: image %d: mask of %lld bytes at offset %lld does not lie inside the buffer of %lld bytes", i, px,
+                     (long long)g.mask_offset, (long long)m_bytes);
+        const int Hp = std::max(g.Hr, Hout), Wp = std::max(g.Wr, Wout);
+        MV_CHECK_ARG(g.top >= 0 && g.left >= 0 && (long long)g.top + Hout <= Hp && (long long)g.left + Wout <= Wp,
+                     "preprocess_u8_seg: image %d: window %dx%d at (%d, %d) does not lie inside the padded image %dx%d", i, Hout, Wout,
+                     g.top, g.left, Hp, Wp);
+        const int need_h = taps_needed(g.Hin, g.Hr), need_w = taps_needed(g.Win, g.Wr);
+        if (need_h > MV_PREPROCESS_MAX_TAPS || need_w > MV_PREPROCESS_MAX_TAPS) {
+            set_error("preprocess_u8_seg: image %d: %dx%d -> %dx%d needs up to %d x %d taps; at most %d per axis (down-sampling by up "
+                      "to %.1f)", i, g.Hin, g.Win, g.Hr, g.Wr, need_h, need_w, MV_PREPROCESS_MAX_TAPS, (MV_PREPROCESS_MAX_TAPS - 1) / 2.0);
+            return MV_E_UNSUPPORTED;
+        }
+        mh = need_h > mh ? need_h : mh;
+        mw = need_w > mw ? need_w : mw;
+    }
+    // an output may overlap neither an input nor the other output (x and m are only read)
+    const size_t px_out = (size_t)B * Hout * Wout;
+    const uintptr_t lo[4] = {(uintptr_t)x, (uintptr_t)m, (uintptr_t)y, (uintptr_t)labels};
+    const size_t len[4] = {(size_t)x_bytes, m ? (size_t)m_bytes : 0, px_out * 3 * dsize(out_dtype), labels ? px_out * 4 : 0};
+    static const char* const names[4] = {"images", "masks", "output", "labels"};
+    for (int o = 2; o < 4; ++o)
+        for (int i = 0; i < o; ++i)
+            if (len[o] && len[i] && lo[i] < lo[o] + len[o] && lo[o] < lo[i] + len[i]) {
+                set_error("preprocess_u8_seg: %s and %s overlap", names[i], names[o]);
+                return MV_E_UNSUPPORTED;
+            }
+
+    // One tile and one LDS size per launch, as in the ragged entry: the largest spans and tap counts any resize of the batch needs.
+    PrepSegP r;
+    PrepP& p = r.p;
+    p.x = (const uint8_t*)x; p.y = y; p.tab_h = nullptr; p.tab_w = nullptr; p.a = a; p.b = b; p.status = nullptr;
+    p.Hin = 0; p.Win = 0; p.Hout = Hout; p.Wout = Wout; p.mh = mh; p.mw = mw;
+    r.rec = rec_dev; r.m = (const uint8_t*)m; r.labels = labels; r.x_bytes = x_bytes; r.m_bytes = m ? m_bytes : 0;
+    r.image_fill = image_fill; r.mask_fill = mask_fill;
+    size_t lds = 0;
+    if (!pick_tile(p, in_chw, &lds, [&](int TH, int TW, int* rows, int* cols) {
+            *rows = *cols = 0;
+            for (int i = 0; i < B; ++i) {
+                *rows = std::max(*rows, span_cap(TH, rec_host[i].Hin, rec_host[i].Hr));
+                *cols = std::max(*cols, span_cap(TW, rec_host[i].Win, rec_host[i].Wr));
+            }
+        })) {
+        set_error("preprocess_u8_seg: the batch does not fit the LDS tile (%zu bytes for the smallest tile)", lds);
+        return MV_E_UNSUPPORTED;
+    }
+    const dim3 grid((Wout + p.TW - 1) / p.TW, (Hout + p.TH - 1) / p.TH, B);
+    MV_CHECK_ARG(grid.y <= 65535, "preprocess_u8_seg: %d output rows are too many tiles", Hout);
+    p.status = device_status_word();                         // the first touch of the device: everything above is host work
+    MV_CHECK_ARG(p.status != nullptr, "preprocess_u8_seg: the device status word is not available");
+    hipStream_t st = (hipStream_t)stream;
+    set_kernel_name("preprocess_u8_seg");
+    PREPROCESS_LAUNCH(preprocess_u8_seg_kernel, r);
     MV_LAUNCH_CHECK();
     return MV_OK;
 }

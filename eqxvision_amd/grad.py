@@ -1036,12 +1036,17 @@ def softmax_cross_entropy_with_integer_labels(logits, labels, axis: int = -1, wh
     if tuple(labels.shape if on_device else np.shape(labels)) != (B, H, W):
         raise ValueError(f"softmax_cross_entropy_with_integer_labels: logits {shape} need labels of shape {(B, H, W)}, got "
                          f"{tuple(np.shape(labels))}")
-    mask = None
+    mask = md = None
     if where is not None:
-        mask = where.detach().cpu().numpy() if isinstance(where, torch.Tensor) else np.asarray(where)
-        if tuple(mask.shape) != (B, H, W):
-            raise ValueError(f"softmax_cross_entropy_with_integer_labels: `where` of shape {tuple(mask.shape)}, expected {(B, H, W)}")
-        mask = np.ascontiguousarray(mask != 0)
+        if tuple(where.shape if isinstance(where, torch.Tensor) else np.shape(where)) != (B, H, W):
+            raise ValueError(f"softmax_cross_entropy_with_integer_labels: `where` of shape {tuple(np.shape(where))}, expected {(B, H, W)}")
+        if isinstance(where, torch.Tensor) and where.is_cuda:    # used where it lies: uint8, contiguous, no host copy
+            md = (where.detach().to(device()) != 0).to(torch.uint8).contiguous()
+            if not on_device:                                    # host labels are checked on the host, under the mask
+                mask = md.cpu().numpy() != 0
+        else:
+            mask = where.detach().numpy() if isinstance(where, torch.Tensor) else np.asarray(where)
+            mask = np.ascontiguousarray(mask != 0)
     if on_device:
         lab = labels.to(torch.int32).contiguous()
     else:
@@ -1053,7 +1058,8 @@ def softmax_cross_entropy_with_integer_labels(logits, labels, axis: int = -1, wh
             raise ValueError(f"softmax_cross_entropy_with_integer_labels: {int(bad.sum())} counted pixel(s) carry a label outside "
                              f"[0, {C}) (first: {int(lab_h[bad][0])})")
         lab = torch.from_numpy(np.ascontiguousarray(lab_h.astype(np.int32))).to(device())
-    md = None if mask is None else torch.from_numpy(mask.astype(np.uint8)).to(device())
+    if md is None and mask is not None:
+        md = torch.from_numpy(mask.astype(np.uint8)).to(device())
     lt = act.t if act is not None else (logits if isinstance(logits, torch.Tensor) else _upload(logits)).to(device()).float().contiguous()
     losses, sums, dl = (torch.empty(s, dtype=torch.float32, device=device()) for s in ((B, H, W), (2,), (B, C, H, W)))
     _launching(_call, "mv_softmax_xent_map_f32", _p(lt), _p(lab), _p(md), _p(losses), _p(dl), _p(sums), B, C, H * W, _S())

@@ -22,6 +22,15 @@ uploaded on every call.  `mv_preprocess_u8_boxes_fwd` takes one 40-byte record p
 whether to mirror) and generates the filter of each tile in the kernel, in float64, by the formulas of `axis_table`; the host
 only draws the boxes (`random_resized_crop_boxes`, `random_flips`).  `crop_resize_normalize` is the deterministic core.
 
+    x, labels = eqv.preprocess.segmentation_train(images_u8, masks_u8, key)   # RandomResize -> flip -> RandomCrop(pad) -> Normalize
+
+The segmentation preset resizes the WHOLE image to a random size, mirrors it, pads it on the right and bottom up to the crop and
+keeps a random window, and the label map goes through the same geometry.  `mv_preprocess_u8_seg_fwd` takes one 48-byte record
+per image (`SEG`) and writes both in one launch: the image through the generated filter above with `image_fill` in the padding,
+the labels as int32 by the centre-based nearest rule with `mask_fill` (255, the void label) in the padding.  The host draws sizes,
+flips and origins (`random_resize_sizes`, `random_flips`, `random_crop_origins`); `resize_pad_crop_pair` is the deterministic
+core, `segmentation_eval` the evaluation preset.
+
 Outputs: NCHW in fp32 or bf16 are what the models' entry kernels read without a conversion launch (`_act.wrap` takes a [B, 3, H, W]
 tensor as the image batch; the entry convolutions read fp32 or bf16).  The models have no NHWC entry, so `imagenet_eval` does not
 offer one; `resize_crop_normalize(layout="nhwc")` returns a plain tensor for other consumers.
@@ -495,3 +504,219 @@ def imagenet_train(images_u8, key, size=224, scale=(0.08, 1.0), ratio=(3.0 / 4.0
     boxes = random_resized_crop_boxes(k_box, sizes, scale, ratio)
     flips = random_flips(k_flip, len(sizes), flip_p)
     return crop_resize_normalize(images_u8, boxes[0] if single else boxes, size, flips, mean, std, dtype, "nchw", channels_last)
+
+
+# ---- segmentation training: resize the whole image, mirror, pad, take a window; image and label map -> mv_preprocess_u8_seg_fwd ----
+
+# `mv_preprocess_seg` of include/eqxvision_amd.h, 48 bytes
+SEG = np.dtype([("offset", "<i8"), ("mask_offset", "<i8"), ("Hin", "<i4"), ("Win", "<i4"), ("Hr", "<i4"), ("Wr", "<i4"),
+                ("top", "<i4"), ("left", "<i4"), ("flip", "<i4"), ("pad", "<i4")])
+
+
+def _pair(v, what):
+    hw = (int(v), int(v)) if isinstance(v, (int, np.integer)) else tuple(int(s) for s in v)
+    if len(hw) != 2 or hw[0] < 1 or hw[1] < 1:
+        raise ValueError(f"preprocess: {what} {v!r} must be a positive int or (height, width)")
+    return hw
+
+
+def random_resize_sizes(key, sizes, min_size, max_size) -> np.ndarray:
+    """torchvision's segmentation `RandomResize(min_size, max_size)` for B images: `sizes` [(H, W)] -> int32 [B, 2] of (Hr, Wr).
+    Host only.  Image i draws u = random.uniform(random.split(key, B)[i], ()) and takes
+    s = min_size + min(int(u (max_size - min_size + 1)), max_size - min_size), an integer uniform over [min_size, max_size] like
+    torch.randint(min_size, max_size + 1), then (Hr, Wr) = resized_size(H, W, s): the shorter side becomes s.
+    This is torchvision's DISTRIBUTION, not torch's random stream: the same seed gives other sizes than torchvision does."""
+    sizes = [(int(h), int(w)) for h, w in sizes]
+    lo, hi = int(min_size), int(max_size)
+    if lo < 1 or hi < lo:
+        raise ValueError(f"preprocess: min_size {min_size} and max_size {max_size} must satisfy 1 <= min_size <= max_size")
+    if len(sizes) == 0:
+        raise ValueError("preprocess: no image sizes")
+    out = np.zeros((len(sizes), 2), np.int32)
+    keys = _random.split(key, len(sizes))
+    for i, (H, W) in enumerate(sizes):
+        if H < 1 or W < 1:
+            raise ValueError(f"preprocess: image {i}: empty image {H}x{W}")
+        u = float(_random.uniform(keys[i], ()))
+        out[i] = resized_size(H, W, lo + min(int(u * (hi - lo + 1)), hi - lo))
+    return out
+
+
+def random_crop_origins(key, resized, crop) -> np.ndarray:
+    """torchvision's `RandomCrop.get_params` on the padded size, for B images: `resized` [(Hr, Wr)], `crop` an int or (Hc, Wc) ->
+    int32 [B, 2] of (top, left) in the image padded to max(Hr, Hc) x max(Wr, Wc).  Host only.  Image i draws
+    u = random.uniform(random.split(key, B)[i], (2,)): top = min(int(u[0] (max(Hr, Hc) - Hc + 1)), max(Hr, Hc) - Hc), left
+    likewise from u[1]; an axis that had to be padded leaves only the origin 0.
+    This is torchvision's DISTRIBUTION, not torch's random stream: the same seed gives other origins than torchvision does."""
+    hc, wc = _pair(crop, "crop")
+    resized = [(int(h), int(w)) for h, w in resized]
+    if len(resized) == 0:
+        raise ValueError("preprocess: no image sizes")
+    out = np.zeros((len(resized), 2), np.int32)
+    keys = _random.split(key, len(resized))
+    for i, (hr, wr) in enumerate(resized):
+        if hr < 1 or wr < 1:
+            raise ValueError(f"preprocess: image {i}: empty resized image {hr}x{wr}")
+        u = np.asarray(_random.uniform(keys[i], (2,)), np.float64)
+        fh, fw = max(hr, hc) - hc, max(wr, wc) - wc
+        out[i] = (min(int(u[0] * (fh + 1)), fh), min(int(u[1] * (fw + 1)), fw))
+    return out
+
+
+def seg_plan(sizes, resized, origins, flip, crop):
+    """Host half of `resize_pad_crop_pair`, no device involved: `sizes` [(Hin, Win)] of tightly packed images (and, one plane
+    each, masks) in order, `resized` [B, 2] of (Hr, Wr), `origins` [B, 2] of (top, left) in the padded image, `flip` None or [B],
+    `crop` an int or (Hc, Wc).  Returns (records, (Hc, Wc)), `records` a SEG array [B]; every refusal is a ValueError that names
+    the image."""
+    B = len(sizes)
+    hc, wc = _pair(crop, "crop")
+    rs, og = np.asarray(resized), np.asarray(origins)
+    if rs.dtype.kind not in "iu" or rs.shape != (B, 2):
+        raise ValueError(f"preprocess: resized must be integers [{B}, 2] of (Hr, Wr), one size per image, got {rs.dtype} {tuple(rs.shape)}")
+    if og.dtype.kind not in "iu" or og.shape != (B, 2):
+        raise ValueError(f"preprocess: origins must be integers [{B}, 2] of (top, left), one origin per image, got {og.dtype} "
+                         f"{tuple(og.shape)}")
+    fl = np.zeros(B, bool) if flip is None else np.asarray(flip)
+    if fl.shape != (B,):
+        raise ValueError(f"preprocess: flip must hold one flag per image ({B}), got shape {tuple(fl.shape)}")
+    rec = np.zeros(B, SEG)
+    offset = 0
+    for i, (hin, win) in enumerate(sizes):
+        who = f"preprocess: image {i}"
+        (hr, wr), (top, left) = (int(v) for v in rs[i]), (int(v) for v in og[i])
+        if hr < 1 or wr < 1:
+            raise ValueError(f"{who}: resized size {(hr, wr)} must be positive")
+        hp, wp = max(hr, hc), max(wr, wc)
+        if top < 0 or left < 0 or top + hc > hp or left + wc > wp:
+            raise ValueError(f"{who}: window {hc}x{wc} at ({top}, {left}) does not lie inside the padded image {hp}x{wp}")
+        _check_taps(hin, win, hr, wr, who)
+        rec[i] = (3 * offset, offset, hin, win, hr, wr, top, left, int(bool(fl[i])), 0)
+        offset += hin * win
+    return rec, (hc, wc)
+
+
+def _check_masks(masks, sizes, listed, batched):
+    """Masks in the form of the images, without the channel axis and of matching sizes; every refusal names the image."""
+    who = "preprocess: masks"
+    if listed:
+        if not isinstance(masks, (list, tuple)) or len(masks) != len(sizes):
+            raise ValueError(f"{who}: a list of {len(sizes)} images needs a list of {len(sizes)} masks")
+        planes = list(masks)
+    else:
+        if not isinstance(masks, (np.ndarray, torch.Tensor)) or masks.ndim != (3 if batched else 2):
+            raise ValueError(f"{who}: must be an array {'[B, H, W]' if batched else '[H, W]'} like the images without their channel axis")
+        if batched and int(masks.shape[0]) != len(sizes):
+            raise ValueError(f"{who}: {int(masks.shape[0])} masks for {len(sizes)} images")
+        planes = list(masks) if batched else [masks]
+    for i, (m, hw) in enumerate(zip(planes, sizes)):
+        if not isinstance(m, (np.ndarray, torch.Tensor)) or m.dtype != (torch.uint8 if isinstance(m, torch.Tensor) else np.uint8):
+            raise ValueError(f"preprocess: image {i}: the mask must be a uint8 array of labels, got "
+                             f"{getattr(m, 'dtype', type(m).__name__)}")
+        if tuple(int(v) for v in m.shape) != tuple(hw):
+            raise ValueError(f"preprocess: image {i}: mask of shape {tuple(m.shape)} for an image of {hw[0]}x{hw[1]}")
+
+
+def _one_buffer(v):
+    """A list -> `pack_images` (which packs any uint8 arrays, planes included); an array -> itself on the device, contiguous."""
+    if isinstance(v, (list, tuple)):
+        return pack_images(v)
+    t = v if isinstance(v, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(v))
+    return t.to(device(), non_blocking=True).contiguous()
+
+
+def resize_pad_crop_pair(images_u8, masks_u8, resized, origins, crop, flip=None, mean=IMAGENET_MEAN, std=IMAGENET_STD, dtype="fp32",
+                         layout="nchw", image_fill=0, mask_fill=255, channels_last=None):
+    """Resize image i WHOLE to `resized[i]` = (Hr, Wr) with the antialiased triangle filter of `crop_resize_normalize`, mirror it
+    left-right where `flip[i]`, pad it on the right and bottom to max(Hr, Hc) x max(Wr, Wc), and keep the `crop` = (Hc, Wc) window
+    at `origins[i]` = (top, left) of the padded image.  Returns (x, labels): x = (image / 255 - mean) / std as a device tensor
+    [B, 3, Hc, Wc] (`layout="nchw"`) or [B, Hc, Wc, 3], fp32 or bf16, with `image_fill` (a pixel value 0..255, normalised like the
+    rest) in the padding; labels int32 [B, Hc, Wc], the mask through the same geometry with the centre-based nearest rule,
+    mask[(2 r + 1) Hin // (2 Hr)][(2 c + 1) Win // (2 Wr)] (PIL, torch's "nearest-exact": the half-pixel grid of the image
+    filter), and `mask_fill` in the padding -- what `optim.softmax_cross_entropy_with_integer_labels(out, labels, axis=1,
+    where=labels != 255)` reads.  `images_u8`: as for `crop_resize_normalize`; `masks_u8`: the same form without the channel
+    axis, sizes matching, or None (then labels is None).  One launch of `mv_preprocess_u8_seg_fwd` on the current stream for
+    every form; lists are packed with `pack_images`, one upload each.  The call cannot be recorded by `filter_jit`: the sizes and
+    origins belong to this one call."""
+    if getattr(_act_tls, "keep", None) is not None:
+        raise ValueError("preprocess: resize_pad_crop_pair cannot be recorded by filter_jit: its sizes, origins, flips and offsets "
+                         "belong to this one call, and a replay would apply them to other images; preprocess outside the recorded "
+                         "function")
+    listed = isinstance(images_u8, (list, tuple))
+    if listed:
+        chw, sizes = _check_list(images_u8, channels_last)
+        batched = True
+    else:
+        x, batched, chw, hin, win = _check_input(images_u8, channels_last)
+        sizes = [(hin, win)] * (int(x.shape[0]) if batched else 1)
+        if len(sizes) == 0:
+            raise ValueError("preprocess: the batch of images is empty")
+        if not batched:
+            resized = np.asarray(resized).reshape(1, -1) if np.asarray(resized).ndim == 1 else resized
+            origins = np.asarray(origins).reshape(1, -1) if np.asarray(origins).ndim == 1 else origins
+            flip = flip if flip is None else np.asarray(flip).reshape(-1)
+    if masks_u8 is not None:
+        _check_masks(masks_u8, sizes, listed, batched)
+    _check_output(dtype, layout)
+    for name, v in (("image_fill", image_fill), ("mask_fill", mask_fill)):
+        if not isinstance(v, (int, np.integer)) or not 0 <= int(v) <= 255:
+            raise ValueError(f"preprocess: {name} must be an integer in [0, 255], got {v!r}")
+    rec, (hc, wc) = seg_plan(sizes, resized, origins, flip, crop)
+    affine(mean, std)                                        # validates before the device is touched
+    a, b = _device_affine(mean, std)
+    t = _one_buffer(images_u8)
+    m = None if masks_u8 is None else _one_buffer(masks_u8)
+    rec_dev = torch.from_numpy(rec.view(np.uint8)).to(device())
+    B = len(sizes)
+    y = empty((B, 3, hc, wc) if layout == "nchw" else (B, hc, wc, 3), TORCH_DT[dtype])
+    labels = None if m is None else empty((B, hc, wc), torch.int32)
+    _lib.call("mv_preprocess_u8_seg_fwd", t.data_ptr(), t.numel(), None if m is None else m.data_ptr(), 0 if m is None else m.numel(),
+              y.data_ptr(), None if m is None else labels.data_ptr(), rec.ctypes.data, rec_dev.data_ptr(), a.data_ptr(), b.data_ptr(),
+              B, hc, wc, int(image_fill), int(mask_fill), int(chw), DT[dtype], int(layout == "nhwc"), stream_ptr())
+    if batched:
+        return y, labels
+    return y[0], None if labels is None else labels[0]
+
+
+def _sizes_of(images_u8, channels_last):
+    """-> ([(Hin, Win)] per image, single): the sizes of any accepted form of input."""
+    if isinstance(images_u8, (list, tuple)):
+        return _check_list(images_u8, channels_last)[1], False
+    x, batched, _, hin, win = _check_input(images_u8, channels_last)
+    sizes = [(hin, win)] * (int(x.shape[0]) if batched else 1)
+    if len(sizes) == 0:
+        raise ValueError("preprocess: the batch of images is empty")
+    return sizes, not batched
+
+
+def segmentation_train(images_u8, masks_u8, key, base_size=520, crop_size=480, flip_p=0.5, mean=IMAGENET_MEAN, std=IMAGENET_STD,
+                       dtype="fp32", image_fill=0, mask_fill=255, channels_last=None):
+    """torchvision's segmentation training preset on the device: RandomResize(int(0.5 base_size), int(2 base_size)) -- image
+    antialiased bilinear, mask nearest -- -> RandomHorizontalFlip(flip_p) -> RandomCrop(crop_size) with pad-if-smaller on the
+    right and bottom (image 0, mask 255) -> ToTensor -> Normalize, image and label map in one launch.  `key` is split in three:
+    `random_resize_sizes` draws from the first, `random_flips` from the second, `random_crop_origins` from the third; the same
+    key gives the same bits.  Returns (x [B, 3, crop, crop] fp32 or bf16, labels int32 [B, crop, crop]).  `images_u8`,
+    `masks_u8`: as for `resize_pad_crop_pair`."""
+    sizes, single = _sizes_of(images_u8, channels_last)
+    k_size, k_flip, k_origin = _random.split(key, 3)
+    resized = random_resize_sizes(k_size, sizes, int(0.5 * base_size), int(2.0 * base_size))
+    flips = random_flips(k_flip, len(sizes), flip_p)
+    origins = random_crop_origins(k_origin, resized, crop_size)
+    return resize_pad_crop_pair(images_u8, masks_u8, resized[0] if single else resized, origins[0] if single else origins, crop_size,
+                                flips, mean, std, dtype, "nchw", image_fill, mask_fill, channels_last)
+
+
+def segmentation_eval(images_u8, masks_u8=None, base_size=520, mean=IMAGENET_MEAN, std=IMAGENET_STD, dtype="fp32",
+                      channels_last=None):
+    """torchvision's segmentation evaluation preset on the device: the shorter side to `base_size` (image antialiased bilinear,
+    mask nearest), no flip, no crop, ToTensor, Normalize; the core with crop = resized size and origin (0, 0).  Returns
+    (x [B, 3, Hr, Wr], labels int32 [B, Hr, Wr] or None).  Images of different sizes give outputs of different sizes and are
+    refused: evaluate them one by one."""
+    sizes, single = _sizes_of(images_u8, channels_last)
+    resized = [resized_size(h, w, base_size) for h, w in sizes]
+    for i, hw in enumerate(resized):
+        if hw != resized[0]:
+            raise ValueError(f"preprocess: image {i}: segmentation_eval resizes it to {hw[0]}x{hw[1]} and image 0 to "
+                             f"{resized[0][0]}x{resized[0][1]}; the outputs of one call share a size, evaluate such images one by one")
+    rs, og = np.asarray(resized, np.int32), np.zeros((len(sizes), 2), np.int32)
+    return resize_pad_crop_pair(images_u8, masks_u8, rs[0] if single else rs, og[0] if single else og, resized[0], None, mean, std,
+                                dtype, "nchw", 0, 255, channels_last)

@@ -600,6 +600,37 @@ int mv_preprocess_u8_boxes_fwd(const void* x, int64_t x_bytes, void* y, const mv
                                const mv_preprocess_box* rec_dev, const float* a, const float* b, int B, int Hout, int Wout,
                                int in_chw, int out_dtype, int out_nhwc, mv_stream_t stream);
 
+/* The segmentation training transform in one launch (torchvision's segmentation preset: RandomResize -> RandomHorizontalFlip ->
+ * RandomCrop with pad-if-smaller -> ToTensor -> Normalize, the random draws made by the caller): image i of a packed buffer x and
+ * its label map in a packed buffer m (one record each) are resized WHOLE to Hr x Wr, mirrored left-right if flip != 0, padded on
+ * the right and bottom to max(Hr, Hout) x max(Wr, Wout), and the Hout x Wout window at (top, left) of that padded image is stored.
+ * Output pixel (i, j): r = top + i, q = left + j.  r >= Hr or q >= Wr: y = fma((float)image_fill, a[c], b[c]), labels = mask_fill.
+ * Otherwise, with the resized column c' = flip ? Wr - 1 - q : q, y is the value of mv_preprocess_u8_boxes_fwd's generated filter
+ * for resizing Hin x Win to Hr x Wr at (r, c') -- same taps, same tap order, same two passes and epilogue, so it has the bits of
+ * that entry on the whole image -- and labels = m[(2 r + 1) Hin / (2 Hr)][(2 c' + 1) Win / (2 Wr)], integer division in 64 bits:
+ * the centre-based nearest rule (PIL, torch's "nearest-exact"), on the half-pixel grid of the image filter.
+ * y is [B,3,Hout,Wout] or [B,Hout,Wout,3], MV_F32 or MV_BF16; labels int32 [B,Hout,Wout], what mv_softmax_xent_map_f32 reads.
+ * m == NULL and labels == NULL together: the image only.  No atomics, nothing shared between workgroups: same bits every run.
+ * rec_host (HOST memory) is validated in full before anything is launched, each message naming the image.  MV_E_INVALID: image or
+ * mask outside its buffer; Hin, Win, Hr or Wr < 1; top < 0, left < 0, top + Hout > max(Hr, Hout) or left + Wout > max(Wr, Wout);
+ * m without labels or the reverse; a fill outside [0, 255].  MV_E_UNSUPPORTED: more than MV_PREPROCESS_MAX_TAPS taps on an axis,
+ * min(n_in, int(2 max(1, n_in / n_out) + 1)); an output overlapping an input or the other output.  The one tile of the launch
+ * follows the LDS rule of the ragged entry.  rec_dev (DEVICE memory, same contents) is what the kernel reads; it forms no address
+ * from it unchecked: a record whose image or mask leaves its buffer stores nothing for that image, sizes and origins are clamped
+ * into range, tap counts are clamped to the pitches of the launch; each sets bit 2 of mv_device_status. */
+typedef struct mv_preprocess_seg {
+    int64_t offset;        /* byte offset of the image in x ([Hin,Win,3] or, with in_chw, [3,Hin,Win]) */
+    int64_t mask_offset;   /* byte offset of the mask in m ([Hin,Win] uint8); ignored when m is NULL */
+    int32_t Hin, Win;      /* source size */
+    int32_t Hr, Wr;        /* size the WHOLE image is resized to */
+    int32_t top, left;     /* origin of the Hout x Wout window in the padded image */
+    int32_t flip, pad;     /* flip != 0: mirror left-right after the resize, before padding */
+} mv_preprocess_seg;       /* 48 bytes, no padding */
+int mv_preprocess_u8_seg_fwd(const void* x, int64_t x_bytes, const void* m, int64_t m_bytes, void* y, int32_t* labels,
+                             const mv_preprocess_seg* rec_host, const mv_preprocess_seg* rec_dev, const float* a, const float* b,
+                             int B, int Hout, int Wout, int image_fill, int mask_fill, int in_chw, int out_dtype, int out_nhwc,
+                             mv_stream_t stream);
+
 /* eqx.nn.MaxPool2d (resnet.py:254, alexnet.py:46,49,56): -inf padding, floor output size. */
 int mv_maxpool2d_nhwc_fwd(const void* x, void* y, int N, int H, int W, int C,
                           int kh, int kw, int sh, int sw, int ph, int pw, int dtype, mv_stream_t stream);
