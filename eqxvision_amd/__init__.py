@@ -11,7 +11,7 @@ Everything below the module `__call__`s is hand-written HIP for gfx950 behind a 
 """
 __version__ = "0.1.0"
 
-from . import layers, models, nn, postprocess, preprocess, random, utils
+from . import layers, metrics, models, nn, postprocess, preprocess, random, utils
 from ._act import (compute_dtype, precision, set_compute_dtype, set_head_fp32, set_residual_fp32, set_split_weights)
 from ._module import Module, tree_at, tree_inference, tree_leaves, tree_map
 from .transforms import filter_jit, vmap
@@ -25,6 +25,6 @@ def filter(tree, predicate=None):
     skips non-array leaves itself, so the tree is returned as it is."""
     return tree
 
-__all__ = ["layers", "models", "nn", "postprocess", "preprocess", "random", "utils", "Module", "tree_at", "tree_inference", "tree_leaves", "tree_map",
+__all__ = ["layers", "metrics", "models", "nn", "postprocess", "preprocess", "random", "utils", "Module", "tree_at", "tree_inference", "tree_leaves", "tree_map",
            "filter_jit", "vmap", "filter_value_and_grad", "apply_updates", "optim", "filter", "is_array", "compute_dtype", "precision", "set_compute_dtype", "set_head_fp32", "set_residual_fp32",
            "set_split_weights"]

@@ -105,6 +105,9 @@ PROTOTYPES = {
     "mv_resize_bilinear_nhwc_fwd": [_vp, _vp] + [_i] * 6 + [_i, _i, _i, _vp],
     "mv_resize_argmax_nhwc_fwd": [_vp, _vp] + [_i] * 7 + [_vp],
     "mv_softmax_topk_f32": [_vp, _vp, _vp, _i, _i, _i, _i, _vp],
+    "mv_confusion_from_logits": [_vp, _vp, _vp] + [_i] * 8 + [_vp],
+    "mv_confusion_from_labels": [_vp, _vp, _vp, C.c_longlong, _i, _i, _i, _vp],
+    "mv_topk_correct_f32": [_vp, _vp, _vp, _i, _i, _vp, _i, _vp],
     "mv_copy_rows": [_vp, _vp, _i64, _i64, _i64, _i64, _vp],
     "mv_preprocess_u8_fwd": [_vp] * 6 + [_i] * 14 + [_vp],
     "mv_preprocess_u8_ragged_fwd": [_vp, _i64, _vp, _vp, _vp, _vp, _i64, _vp, _vp] + [_i] * 6 + [_vp],

@@ -71,6 +71,43 @@ __global__ __launch_bounds__(TOPK_THREADS) void softmax_topk_kernel(const float*
     }
 }
 
+// ---- top-k accuracy: is the label among the k best of its row?  No selection is kept, so k is unbounded. ------------------------
+// rank = #{j : x[j] > x[label] or (x[j] == x[label] and j < label)}: the position of the label in the order of the kernel above
+// for rows without NaN (ties by ascending index; -0 == +0).  One workgroup per row, one pass; counts[i] += 1 where rank < ks[i],
+// counts[nk] += B (block 0).  A label outside [0, K) or a NaN at the label's logit: wrong for every k, still counted.
+struct TopkKs {
+    int k[MV_TOPK_MAX_KS];
+};
+
+__global__ __launch_bounds__(TOPK_THREADS) void topk_correct_kernel(const float* __restrict__ logits, const int* __restrict__ labels,
+                                                                   unsigned long long* __restrict__ counts, int B, int K, TopkKs ks,
+                                                                   int nk) {
+    __shared__ int s_rank[TOPK_WAVES];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    if (blockIdx.x == 0 && tid == 0) atomicAdd(&counts[nk], (unsigned long long)B);
+    const int label = labels[blockIdx.x];
+    if (label < 0 || label >= K) return;             // block-uniform
+    const float* row = logits + (long long)blockIdx.x * K;
+    const float xl = row[label];
+    if (xl != xl) return;
+    int rank = 0;
+    for (int i = tid; i < K; i += TOPK_THREADS) {
+        const float v = row[i];
+        rank += (v > xl || (v == xl && i < label)) ? 1 : 0;
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) rank += __shfl_xor(rank, o);
+    if (lane == 0) s_rank[wave] = rank;
+    __syncthreads();
+    if (tid == 0) {
+        rank = 0;
+#pragma unroll
+        for (int q = 0; q < TOPK_WAVES; ++q) rank += s_rank[q];
+        for (int i = 0; i < nk; ++i)
+            if (rank < ks.k[i]) atomicAdd(&counts[i], 1ull);
+    }
+}
+
 }  // namespace mv
 
 using namespace mv;
@@ -86,6 +123,22 @@ int mv_softmax_topk_f32(const float* logits, float* values, int* indices, int B,
     set_kernel_name("softmax_topk");
     hipLaunchKernelGGL(softmax_topk_kernel, dim3(B), dim3(TOPK_THREADS), 0, (hipStream_t)stream, logits, values, indices, K, k,
                        want_prob);
+    MV_LAUNCH_CHECK();
+    return MV_OK;
+}
+
+int mv_topk_correct_f32(const float* logits, const int* labels, unsigned long long* counts, int B, int K, const int* ks, int nk,
+                        mv_stream_t stream) {
+    MV_CHECK_ARG(logits && labels && counts && ks, "topk_correct: NULL buffer");
+    MV_CHECK_ARG(B > 0 && K >= 1 && K <= 65536, "topk_correct: bad dimensions B=%d K=%d (1 <= K <= 65536)", B, K);
+    MV_CHECK_ARG(nk >= 1 && nk <= MV_TOPK_MAX_KS, "topk_correct: nk=%d must be in 1 .. %d", nk, MV_TOPK_MAX_KS);
+    TopkKs v = {};
+    for (int i = 0; i < nk; ++i) {
+        MV_CHECK_ARG(ks[i] >= 1, "topk_correct: k=%d must be at least 1", ks[i]);
+        v.k[i] = ks[i];
+    }
+    set_kernel_name("topk_correct");
+    hipLaunchKernelGGL(topk_correct_kernel, dim3(B), dim3(TOPK_THREADS), 0, (hipStream_t)stream, logits, labels, counts, B, K, v, nk);
     MV_LAUNCH_CHECK();
     return MV_OK;
 }

@@ -196,6 +196,32 @@ def all_reduce_sum_(t: torch.Tensor, group=None) -> torch.Tensor:
     return t
 
 
+def all_reduce_sum_int64_(t: torch.Tensor, group=None) -> torch.Tensor:
+    """In-place EXACT sum over ranks of an int64 tensor (the counters of `eqxvision_amd.metrics`; `all_reduce_sum_` is fp32 and
+    loses integers above 2^24).  `torch.distributed` on the integers where a process group is up (gloo stages through the host);
+    with only the native RCCL communicator, the tensors of all ranks are gathered as bytes (`mv_allgather`) and summed locally;
+    a single process returns `t` unchanged."""
+    if t.dtype != torch.int64:
+        raise ValueError(f"all_reduce_sum_int64_: expected an int64 tensor, got {t.dtype}")
+    if group is None and _state["group"] is not None:
+        group = _state["group"]
+    if dist.is_initialized():
+        if dist.get_world_size(group) == 1:
+            return t
+        if t.is_cuda and dist.get_backend(group) == "gloo":
+            h = t.cpu()
+            dist.all_reduce(h, op=dist.ReduceOp.SUM, group=group)
+            t.copy_(h)
+        else:
+            dist.all_reduce(t, op=dist.ReduceOp.SUM, group=group)
+        return t
+    if _state["native"] and t.is_cuda:
+        world = _lib.load().mv_comm_size()
+        if world > 1:
+            t.copy_(all_gather_rows(t.reshape(1, -1), world).sum(0).reshape(t.shape))
+    return t
+
+
 def world_size(group=None) -> int:
     if _state["native"] and group is None:
         return max(1, _lib.load().mv_comm_size())

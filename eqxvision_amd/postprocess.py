@@ -34,23 +34,23 @@ def _check_array(x, who, dtypes):
     return x
 
 
-def _check_logits(logits, size, channels_last):
+def _check_logits(logits, size, channels_last, who="postprocess.upsample_argmax"):
     """-> (batched, h, w, C, H, W); raises ValueError before anything touches the device."""
-    x = _check_array(logits, "postprocess.upsample_argmax", (torch.float32, torch.bfloat16))
+    x = _check_array(logits, who, (torch.float32, torch.bfloat16))
     if x.ndim not in (3, 4):
-        raise ValueError(f"postprocess.upsample_argmax: logits must be [h, w, C] / [C, h, w] or a batch of them, got shape {tuple(x.shape)}")
+        raise ValueError(f"{who}: logits must be [h, w, C] / [C, h, w] or a batch of them, got shape {tuple(x.shape)}")
     s = tuple(int(v) for v in x.shape[-3:])
     h, w, C = s if channels_last else (s[1], s[2], s[0])
     try:
         H, W = (int(v) for v in size)
     except (TypeError, ValueError):
-        raise ValueError(f"postprocess.upsample_argmax: size must be (H, W), got {size!r}") from None
+        raise ValueError(f"{who}: size must be (H, W), got {size!r}") from None
     if min(h, w, C) < 1 or (x.ndim == 4 and x.shape[0] < 1):
-        raise ValueError(f"postprocess.upsample_argmax: empty logits, shape {tuple(x.shape)}")
+        raise ValueError(f"{who}: empty logits, shape {tuple(x.shape)}")
     if C > MAX_CLASSES:
-        raise ValueError(f"postprocess.upsample_argmax: {C} classes do not fit a uint8 label (at most {MAX_CLASSES})")
+        raise ValueError(f"{who}: {C} classes do not fit a uint8 label (at most {MAX_CLASSES})")
     if H < h or W < w:
-        raise ValueError(f"postprocess.upsample_argmax: {h}x{w} -> {H}x{W} is down-sampling; only up-sampling is supported")
+        raise ValueError(f"{who}: {h}x{w} -> {H}x{W} is down-sampling; only up-sampling is supported")
     return x.ndim == 4, h, w, C, H, W
 
 
@@ -91,25 +91,22 @@ def upsample_argmax(logits, size, channels_last=True) -> torch.Tensor:
     return y if batched else y[0]
 
 
-def segment(net, images, *, key=None) -> torch.Tensor:
-    """The label map of a segmentation model: argmax over the classes of what `vmap(net)(images, key=...)[1]` returns, uint8
-    [B, H, W], without that tensor ever being written.  Backbone and classifier run exactly as in the model's own forward; the
-    auxiliary head, whose result inference discards, is skipped; the final resize is `upsample_argmax`.  `net`: fcn / deeplabv3 /
-    lraspp_mobilenet_v3_large in inference mode; `images`: [B, 3, H, W], fp32 or bf16; `key`: as for the model (None, one key, or
-    [B, 2] keys -- dead values in inference)."""
+def _head_logits(net, images, key, who):
+    """What `segment` and `metrics.evaluate_segmentation` share: the checks, then backbone and classifier exactly as in the model's
+    own forward, the auxiliary head skipped.  -> (NHWC logits of the head on the device, H, W of the images)."""
     from .models.segmentation._utils import _SimpleSegmentationModel
     from .models.segmentation.lraspp import LRASPP
     from .transforms import _train_layers
     if not isinstance(net, (_SimpleSegmentationModel, LRASPP)):
-        raise ValueError(f"postprocess.segment: net must be a segmentation model (fcn, deeplabv3, lraspp_mobilenet_v3_large), got "
+        raise ValueError(f"{who}: net must be a segmentation model (fcn, deeplabv3, lraspp_mobilenet_v3_large), got "
                          f"{type(net).__name__}")
     bns, stochastic = _train_layers(net)
     if bns or stochastic:
-        raise ValueError("postprocess.segment: the model is in training mode; label maps are an inference result "
+        raise ValueError(f"{who}: the model is in training mode; label maps are an inference result "
                          "(use tree_inference(net, True))")
-    x = _check_array(images, "postprocess.segment", (torch.float32, torch.bfloat16))
+    x = _check_array(images, who, (torch.float32, torch.bfloat16))
     if x.ndim != 4 or x.shape[1] != 3 or min(int(v) for v in x.shape) < 1:
-        raise ValueError(f"postprocess.segment: images must be [B, 3, H, W], got shape {tuple(x.shape)}")
+        raise ValueError(f"{who}: images must be [B, 3, H, W], got shape {tuple(x.shape)}")
     a = wrap(x, batched=True)
     H, W = (int(v) for v in a.shape[-2:])
     if isinstance(net, LRASPP):                  # its forward takes no key (lraspp.py), and its head reads both feature maps
@@ -119,7 +116,16 @@ def segment(net, images, *, key=None) -> torch.Tensor:
         k_backbone, k_clf, _ = jr.split(jr.PRNGKey(0) if key is None else key, 3)
         _, feats = net.backbone(a, key=k_backbone)
         logits = net.classifier(feats[-1], key=k_clf)
-    return _labels(ops.as_map(logits).t, H, W)
+    return ops.as_map(logits).t, H, W
+
+
+def segment(net, images, *, key=None) -> torch.Tensor:
+    """The label map of a segmentation model: argmax over the classes of what `vmap(net)(images, key=...)[1]` returns, uint8
+    [B, H, W], without that tensor ever being written.  Backbone and classifier run exactly as in the model's own forward; the
+    auxiliary head, whose result inference discards, is skipped; the final resize is `upsample_argmax`.  `net`: fcn / deeplabv3 /
+    lraspp_mobilenet_v3_large in inference mode; `images`: [B, 3, H, W], fp32 or bf16; `key`: as for the model (None, one key, or
+    [B, 2] keys -- dead values in inference)."""
+    return _labels(*_head_logits(net, images, key, "postprocess.segment"))
 
 
 def topk(logits, k: int = 5, probabilities: bool = True):

@@ -527,6 +527,31 @@ int mv_resize_argmax_nhwc_fwd(const void* x, void* labels, int B, int h, int w, 
 int mv_softmax_topk_f32(const float* logits, float* values, int* indices, int B, int K, int k, int want_prob,
                         mv_stream_t stream);
 
+/* Scoring on the device (no counterpart in the reference; the rule of torchvision's reference segmentation ConfusionMatrix):
+ * mat[t * C + p] += 1 for every pixel with target t and prediction p, mat uint64 [C][C] (rows = target).  A pixel counts iff
+ * 0 <= t < C -- 255, any other value >= C and negative int32 targets do not.  Both entries ADD into mat; the caller zeroes it.
+ * Integer atomics only: the result is exact and the same for every run.  One launch each.
+ *   mv_confusion_from_logits: p = the label mv_resize_argmax_nhwc_fwd writes for the same logits (same code), which is not stored;
+ *     logits NHWC [B,h,w,C] MV_F32 / MV_BF16, labels [B,H,W] uint8 (label_bytes 1) or int32 (4).
+ *   mv_confusion_from_labels: p read from a second label map; pred and labels n elements each, uint8 or int32 independently, any
+ *     byte alignment for uint8.  A pixel whose p is outside [0, C) has no cell and is not counted.
+ * MV_E_INVALID: a NULL buffer, a non-positive size, C outside 1 .. 256, an unknown dtype or byte width, H < h or W < w, an
+ * int32 map that is not 4-byte aligned. */
+int mv_confusion_from_logits(const void* logits, const void* labels, unsigned long long* mat, int B, int h, int w, int C,
+                             int H, int W, int logits_dtype, int label_bytes, mv_stream_t stream);
+int mv_confusion_from_labels(const void* pred, const void* labels, unsigned long long* mat, long long n, int C,
+                             int pred_bytes, int label_bytes, mv_stream_t stream);
+
+/* Top-k accuracy counters in one launch: for every row of logits fp32 [B][K] with label l = labels[row] (int32),
+ * rank = #{j : x[j] > x[l] or (x[j] == x[l] and j < l)} (the tie rule of mv_softmax_topk_f32); counts[i] += 1 where
+ * rank < ks[i], i < nk, and counts[nk] += B.  counts: uint64 [nk + 1] on the device, ADDED to; ks: nk values on the HOST, read
+ * during the call, each >= 1 and otherwise unbounded (nothing is selected, MV_TOPK_MAX_K does not apply).  A row whose label is
+ * outside [0, K) or whose logit at the label is NaN is wrong for every k and still counted in counts[nk].
+ * 1 <= K <= 65536, 1 <= nk <= MV_TOPK_MAX_KS, else MV_E_INVALID. */
+#define MV_TOPK_MAX_KS 8
+int mv_topk_correct_f32(const float* logits, const int* labels, unsigned long long* counts, int B, int K, const int* ks, int nk,
+                        mv_stream_t stream);
+
 /* rows x row_bytes strided copy (jnp.concatenate of NHWC maps along channels, deeplabv3.py:132-136: one call per source with
  * dst offset by the channels already placed).  Sizes and pitches in bytes, multiples of 2. */
 int mv_copy_rows(const void* src, void* dst, int64_t rows, int64_t row_bytes, int64_t src_pitch, int64_t dst_pitch,
