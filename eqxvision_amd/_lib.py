@@ -19,7 +19,7 @@ F32, BF16 = 0, 1
 ACT_NONE, ACT_RELU, ACT_GELU_TANH = 0, 1, 2
 ACT_HARD_SWISH, ACT_HARD_SIGMOID, ACT_SIGMOID, ACT_SILU = 3, 4, 5, 6       # element-wise entries and the depthwise conv only
 ABI_VERSION = 2
-OPT_SGD, OPT_ADAMW, OPT_APPLY = 0, 1, 2                                    # mv_optim_step_f32's `kind`
+OPT_SGD, OPT_ADAMW, OPT_APPLY, OPT_EMA = 0, 1, 2, 3                        # mv_optim_step_f32's `kind`
 OPTIM_CHUNK = 4096                                                         # MV_OPTIM_CHUNK: elements per workgroup
 
 _vp, _i, _f, _i64 = C.c_void_p, C.c_int, C.c_float, C.c_int64
@@ -112,6 +112,7 @@ PROTOTYPES = {
     "mv_preprocess_u8_fwd": [_vp] * 6 + [_i] * 14 + [_vp],
     "mv_preprocess_u8_ragged_fwd": [_vp, _i64, _vp, _vp, _vp, _vp, _i64, _vp, _vp] + [_i] * 6 + [_vp],
     "mv_preprocess_u8_boxes_fwd": [_vp, _i64, _vp, _vp, _vp, _vp, _vp] + [_i] * 6 + [_vp],
+    "mv_preprocess_u8_mix_fwd": [_vp, _i64] + [_vp] * 10 + [_i, _f, _f] + [_i] * 6 + [_vp],
     "mv_preprocess_u8_seg_fwd": [_vp, _i64, _vp, _i64] + [_vp] * 6 + [_i] * 8 + [_vp],
     "mv_maxpool2d_nhwc_fwd": [_vp, _vp] + [_i] * 10 + [_i, _vp],
     "mv_adaptive_avgpool2d_nhwc_fwd": [_vp, _vp] + [_i] * 6 + [_i, _i, _vp],
@@ -322,6 +323,9 @@ def check_device_status(clear: bool = True) -> int:
     if v.value & 4:
         raise MVError(f"device status 0x{v.value:x}: mv_preprocess_u8_fwd was given a tap table that points outside the image or its "
                       "tile; the taps were clamped and the output of that call is wrong")
+    if v.value & 8:
+        raise MVError(f"device status 0x{v.value:x}: mv_preprocess_u8_mix_fwd met a device label outside [0, classes); it matched no "
+                      "class and that row of the targets is wrong")
     if v.value:
         raise MVError(f"device status 0x{v.value:x}: a split-K tile was finished without its partner's partial sums -- the scratch of "
                       "mv_set_scratch was shared by concurrent launches or not zero-initialised; results of that launch are wrong")

@@ -1,5 +1,5 @@
 """optax-shaped optimisers over a whole parameter set in one launch (csrc/optim.hip).  The names are re-exported
-by `eqxvision_amd.grad`, so they are `eqv.optim.sgd`, `eqv.optim.adamw`, `eqv.optim.clip_by_global_norm`, `eqv.optim.chain` and the
+by `eqxvision_amd.grad`, so they are `eqv.optim.sgd`, `eqv.optim.adamw`, `eqv.optim.clip_by_global_norm`, `eqv.optim.chain`, `eqv.optim.ema` and the
 schedules `eqv.optim.constant_schedule` / `cosine_decay_schedule` / `warmup_cosine_decay_schedule`.
 
     optimizer = eqv.optim.chain(eqv.optim.clip_by_global_norm(1.0), eqv.optim.adamw(eqv.optim.cosine_decay_schedule(1e-3, 1000)))
@@ -257,6 +257,66 @@ class _Chain:
         if s.rows:
             launch(self._records, s.rows, _lib.OPT_SGD, lr=-1.0, scale=sqnorm(self._records, s.rows, self.clip.max_norm))
         return self.opt.update(s.updates(), state, params)
+
+
+class _Ema:
+    """torchvision's `ExponentialMovingAverage(model, decay)` (the `--model-ema` of its reference training script) over the whole
+    parameter set: e = decay e + (1 - decay) p as fadd(fmul(decay, e), fmul(1 - decay, p)), 1 - decay taken in float64 and
+    rounded once.  `init(params)` copies the float leaves to device slots; `update(params, state)` is ONE launch
+    (mv_optim_step_f32, MV_OPT_EMA) that overwrites the slots, and the first one after `init` copies the parameters, as
+    torch's AveragedModel does; `state_params(state, like)` is the tree `like` with the averages as `DevArray` leaves.  A leaf that
+    is `None` (frozen) or not a float array has no slot and is passed through."""
+    name = "ema"
+
+    def __init__(self, decay):
+        self.decay = float(decay)
+        if not 0.0 <= self.decay <= 1.0:
+            raise ValueError(f"ema: decay = {decay} must lie in [0, 1]")
+        self._records = {}
+
+    def init(self, params):
+        index, _ = leaf_index(params)
+        slots = [_g._upload(leaf).reshape(-1).clone() for leaf in tree_leaves(params, none_is_leaf=True) if _g._float_leaf(leaf)]
+        return {"count": 0, "index": index, "ema": slots}
+
+    def update(self, params, state):
+        index, slots = state["index"], state["ema"]
+        pl = tree_leaves(params, none_is_leaf=True)
+        if len(pl) != len(index):
+            raise ValueError("ema.update: `params` does not have the structure of the tree given to init")
+        rows, keep = [], []
+        for k, leaf in enumerate(pl):
+            if not _g._float_leaf(leaf):
+                continue
+            i = index[k]
+            if i < 0:
+                raise ValueError("ema.update: `params` does not have the structure of the tree given to init")
+            pd = _g._upload(leaf).contiguous()
+            if pd.numel() != slots[i].numel():
+                raise ValueError(f"ema.update: a parameter of {pd.numel()} elements for a leaf of {slots[i].numel()}")
+            if pd.numel():
+                keep.append(pd)
+                rows.append((pd.data_ptr(), 0, 0, 0, slots[i].data_ptr(), pd.numel()))
+        if rows:
+            launch(self._records, rows, _lib.OPT_EMA, nesterov=state["count"] == 0, b1=self.decay)
+        return {"count": state["count"] + 1, "index": index, "ema": slots}
+
+    def state_params(self, state, like):
+        index, slots = state["index"], state["ema"]
+        pos = iter(index)
+
+        def leaf(x):
+            i = next(pos, None)
+            if not _g._float_leaf(x):
+                return x
+            if i is None or i < 0 or slots[i].numel() != int(np.prod(x.shape)):
+                raise ValueError("ema.state_params: `like` does not have the structure of the tree given to init")
+            return DevArray(slots[i].reshape(tuple(x.shape)))
+        return tree_map(leaf, like, none_is_leaf=True)
+
+
+def ema(decay) -> _Ema:
+    return _Ema(decay)
 
 
 def sgd(learning_rate, momentum=None, nesterov: bool = False) -> _Sgd:

@@ -19,6 +19,13 @@ __device__ __forceinline__ float bf2f(bf16_t v) { return __uint_as_float(((uint3
 // (v_cvt_pk_bf16_f32, two values per instruction) instead of ~6 VALU ops of bit arithmetic per value
 typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ bf16_t f2bf(float f) { return __builtin_bit_cast(bf16_t, (__bf16)f); }
+// fl(fl(a x) + fl(b y)): two rounded products and one rounded sum, never contracted into an fma (what float32 numpy computes for
+// a * x + b * y).  hipcc's __fmul_rn / __fadd_rn are plain * and + and fuse under the default -ffp-contract=fast.
+__device__ __forceinline__ float mul_add_rn(float a, float x, float b, float y) {
+#pragma clang fp contract(off)
+    const float p = a * x, q = b * y;
+    return p + q;
+}
 __device__ __forceinline__ uint32_t pack_bf2(float lo, float hi) {
     bf16x2_t v;
     v[0] = (__bf16)lo;

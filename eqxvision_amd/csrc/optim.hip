@@ -9,7 +9,7 @@
 //   * plain vector stores, no atomics; the squared norm is reduced in a fixed order (below), so it has the same bits every run.
 // Whatever first_block says, a workgroup only touches elements [0, n) of the record it picked.
 // The kernels are HBM streams; bytes moved per element: sgd 8 (16 with momentum: m is read and written), adamw 24 (28 with weight
-// decay: the parameter is read), apply 12, squared norm 4.
+// decay: the parameter is read), apply 12, ema 12 (4 when it copies), squared norm 4.
 #include "common.h"
 
 namespace mv {
@@ -120,13 +120,23 @@ template <int KIND> __device__ __forceinline__ float opt_rule(float g, float p, 
     return -h.lr * ((m / h.bc1) / (sqrtf(v / h.bc2) + h.eps) + h.wd * p);
 }
 
+// e = fadd(fmul(d, e), fmul(omd, p)): what float32 numpy computes for d * e + omd * p
+__device__ __forceinline__ float4 ema4(const float4 e, const float4 p, const OptHyper& h) {
+    float4 o;
+    o.x = mul_add_rn(h.b1, e.x, h.omb1, p.x);
+    o.y = mul_add_rn(h.b1, e.y, h.omb1, p.y);
+    o.z = mul_add_rn(h.b1, e.z, h.omb1, p.z);
+    o.w = mul_add_rn(h.b1, e.w, h.omb1, p.w);
+    return o;
+}
+
 template <int KIND> __global__ __launch_bounds__(OPT_THREADS) void optim_step_kernel(const mv_optim_tensor* __restrict__ recs,
                                                                                       int n_tensors, const OptHyper h,
                                                                                       const float* __restrict__ scale) {
     const OptChunk c = opt_chunk(recs, n_tensors);
     const float s = scale ? scale[1] : 1.f;
-    const bool has_p = c.r.param != nullptr && KIND != MV_OPT_SGD;
-    const bool has_m = c.r.m != nullptr && KIND != MV_OPT_APPLY;
+    const bool has_p = c.r.param != nullptr && KIND != MV_OPT_SGD && KIND != MV_OPT_EMA;
+    const bool has_m = c.r.m != nullptr && KIND != MV_OPT_APPLY && KIND != MV_OPT_EMA;
     const bool has_v = c.r.v != nullptr && KIND == MV_OPT_ADAMW;
     if (KIND == MV_OPT_APPLY && !has_p) return;
     if (KIND == MV_OPT_ADAMW && !(has_m && has_v)) return;
@@ -137,6 +147,11 @@ template <int KIND> __global__ __launch_bounds__(OPT_THREADS) void optim_step_ke
         if (rem <= 0) continue;
         const long long i = c.base + off;
         float4 g = ld4(c.r.grad, i, rem, c.vec);
+        if (KIND == MV_OPT_EMA) {                       // out is the average: read, unless this update copies, and written
+            const float4 e = h.nesterov ? g : ld4(c.r.out, i, rem, c.vec);
+            st4(c.r.out, i, rem, c.vec, h.nesterov ? g : ema4(e, g, h));
+            continue;
+        }
         const float4 p = has_p ? ld4(c.r.param, i, rem, c.vec) : zero;
         float4 m = has_m ? ld4(c.r.m, i, rem, c.vec) : zero;
         float4 v = has_v ? ld4(c.r.v, i, rem, c.vec) : zero;
@@ -181,7 +196,8 @@ int mv_optim_step_f32(const mv_optim_tensor* recs, int n_tensors, int64_t total_
     MV_CHECK_ARG(recs && n_tensors > 0, "optim_step: bad arguments");
     MV_CHECK_ARG(total_blocks >= n_tensors && total_blocks < (1LL << 31), "optim_step: %lld blocks for %d tensors",
                  (long long)total_blocks, n_tensors);
-    MV_CHECK_ARG(kind == MV_OPT_SGD || kind == MV_OPT_ADAMW || kind == MV_OPT_APPLY, "optim_step: unknown kind %d", kind);
+    MV_CHECK_ARG(kind == MV_OPT_SGD || kind == MV_OPT_ADAMW || kind == MV_OPT_APPLY || kind == MV_OPT_EMA, "optim_step: unknown kind %d",
+                 kind);
     if (kind == MV_OPT_ADAMW)
         MV_CHECK_ARG(bias_corr1 > 0.f && bias_corr2 > 0.f, "optim_step: adamw needs positive bias corrections (count >= 1)");
     const OptHyper h = {lr, b1, b2, one_minus_b1, one_minus_b2, eps, weight_decay, bias_corr1, bias_corr2, nesterov};
@@ -192,6 +208,9 @@ int mv_optim_step_f32(const mv_optim_tensor* recs, int n_tensors, int64_t total_
     } else if (kind == MV_OPT_ADAMW) {
         set_kernel_name("optim_adamw_f32");
         hipLaunchKernelGGL(optim_step_kernel<MV_OPT_ADAMW>, grid, block, 0, (hipStream_t)stream, recs, n_tensors, h, scale);
+    } else if (kind == MV_OPT_EMA) {
+        set_kernel_name("optim_ema_f32");
+        hipLaunchKernelGGL(optim_step_kernel<MV_OPT_EMA>, grid, block, 0, (hipStream_t)stream, recs, n_tensors, h, scale);
     } else {
         set_kernel_name("optim_apply_f32");
         hipLaunchKernelGGL(optim_step_kernel<MV_OPT_APPLY>, grid, block, 0, (hipStream_t)stream, recs, n_tensors, h, scale);

@@ -3,11 +3,13 @@
 // The filter lives in two tap tables the host builds in float64 (eqxvision_amd/preprocess.py: axis_table); the kernel only
 // applies them, so the same entry serves the antialiased ImageNet preset and plain two-tap up-sampling.  HBM-bound gather, no
 // matrix work: every input byte a tile needs is read once into LDS, both passes run out of LDS, every output is stored once.
-// Four entries share the tile body: one image size per launch (mv_preprocess_u8_fwd), one record per image for a packed batch
+// Five entries share the tile body: one image size per launch (mv_preprocess_u8_fwd), one record per image for a packed batch
 // of any sizes (mv_preprocess_u8_ragged_fwd), one box per image that is cropped FIRST and then resized, mirrored or not
 // (mv_preprocess_u8_boxes_fwd: the training transform; its filter is generated in the tile, no tables), and one window per image
 // of the WHOLE image resized, mirrored and padded, with the label map gathered alongside (mv_preprocess_u8_seg_fwd: the
-// segmentation training transform; the same generated filter on the part of a tile that is not padding).  A launch has ONE tile
+// segmentation training transform; the same generated filter on the part of a tile that is not padding), and the boxes entry
+// with a partner per image mixed in, rectangles erased or replaced and the soft targets written alongside
+// (mv_preprocess_u8_mix_fwd: mixup / cutmix / random erasing; a tile runs the passes once per image it needs).  A launch has ONE tile
 // and ONE LDS size; the record entries size them for the largest spans and pitches of their batch, so one steeply down-sampled
 // image lowers the occupancy of the whole launch (accepted).
 #include "common.h"
@@ -209,6 +211,29 @@ __device__ __forceinline__ TileRect tables_window(const PrepP& p, const TileLds&
     return tables_resized(p, L, 0, 0, p.Hin, p.Win, Hr, Wr, flip, r0, q0, th_v, tw_v);
 }
 
+// Element `it` of a th x tw tile in store order: (row, channel, column) of the tile.
+template <bool NHWC_OUT> __device__ __forceinline__ void tile_elem(const int it, const int tw, int& y, int& c, int& x) {
+    if (NHWC_OUT) {
+        const int yx = it / 3;
+        c = it - yx * 3;
+        y = yx / tw;
+        x = yx - y * tw;
+    } else {
+        const int yc = it / tw;
+        x = it - yc * tw;
+        y = yc / 3;
+        c = yc - y * 3;
+    }
+}
+
+// v -> channel c of output pixel (Y, X) of image b of p.y; the one rounding of a bf16 output.
+template <bool NHWC_OUT, bool BF16_OUT>
+__device__ __forceinline__ void tile_store(const PrepP& p, const int b, const int Y, const int c, const int X, const float v) {
+    const size_t o = NHWC_OUT ? (((size_t)b * p.Hout + Y) * p.Wout + X) * 3 + c : (((size_t)b * 3 + c) * p.Hout + Y) * p.Wout + X;
+    if (BF16_OUT) ((bf16_t*)p.y)[o] = f2bf(v);
+    else ((float*)p.y)[o] = v;
+}
+
 // One workgroup = one TH x TW tile of the cropped output of one image, all three channels.
 //   1. the tables of the tile's rows / columns -> LDS, read from global memory or generated (the two sources above)
 //   2. the input rectangle the tile's taps touch -> LDS as uint8, 16-byte global loads on 16-byte global addresses (a staged line
@@ -220,11 +245,11 @@ __device__ __forceinline__ TileRect tables_window(const PrepP& p, const TileLds&
 // >= 0 and <= the result, so the rounding error is bounded by (taps + 1) 2^-24 of the result itself whatever the image; and a
 // constant neighbourhood comes out as that constant exactly, however the fp32 weights happen to round (a flat image gives
 // fma(v, a, b) bit for bit, borders included).  Nothing is shared between workgroups: two runs give the same bits.
-// Steps 2 - 4.  `img`: the first byte of image `b`, whose size is p's; `t`: the rectangle step 1 left; the output goes to image b
-// of p.y.
-template <bool CHW_IN, bool NHWC_OUT, bool BF16_OUT>
-__device__ __forceinline__ void tile_passes(const PrepP& p, const TileLds& L, const TileRect& t, const uint8_t* img, const int b,
-                                            const int y0, const int x0, const int th, const int tw) {
+// Steps 2 - 4.  `img`: the first byte of the image, whose size is p's; `t`: the rectangle step 1 left; sink(y, c, x, v) receives the
+// fp32 value of every element of the tile, in store order, before any output rounding.
+template <bool CHW_IN, bool NHWC_OUT, class Sink>
+__device__ __forceinline__ void tile_rows(const PrepP& p, const TileLds& L, const TileRect& t, const uint8_t* img, const int th,
+                                          const int tw, Sink&& sink) {
     const int tid = threadIdx.x;
     constexpr int PIX = CHW_IN ? 1 : 3;                      // bytes from one pixel of a channel to the next
     uint8_t* su8 = L.su8;
@@ -281,17 +306,7 @@ __device__ __forceinline__ void tile_passes(const PrepP& p, const TileLds& L, co
     const float a0 = p.a[0], a1 = p.a[1], a2 = p.a[2], b0 = p.b[0], b1 = p.b[1], b2 = p.b[2];
     for (int it = tid; it < th * 3 * tw; it += 256) {
         int y, c, x;
-        if (NHWC_OUT) {
-            const int yx = it / 3;
-            c = it - yx * 3;
-            y = yx / tw;
-            x = yx - y * tw;
-        } else {
-            const int yc = it / tw;
-            x = it - yc * tw;
-            y = yc / 3;
-            c = yc - y * 3;
-        }
+        tile_elem<NHWC_OUT>(it, tw, y, c, x);
         const int f = sfy[y], n = sny[y];
         const float* w = swy + y * p.mh;
         float m = sh[(clampi(f, 0, nrows - 1) * 3 + c) * p.TW + x];
@@ -299,12 +314,17 @@ __device__ __forceinline__ void tile_passes(const PrepP& p, const TileLds& L, co
         float acc = 0.f;
         for (int k = 0; k < n; ++k) acc = fmaf(w[k], sh[(clampi(f + k, 0, nrows - 1) * 3 + c) * p.TW + x] - m, acc);
         acc += m;
-        const float v = fmaf(acc, c == 0 ? a0 : (c == 1 ? a1 : a2), c == 0 ? b0 : (c == 1 ? b1 : b2));
-        const size_t o = NHWC_OUT ? (((size_t)b * p.Hout + y0 + y) * p.Wout + x0 + x) * 3 + c
-                                  : (((size_t)b * 3 + c) * p.Hout + y0 + y) * p.Wout + x0 + x;
-        if (BF16_OUT) ((bf16_t*)p.y)[o] = f2bf(v);
-        else ((float*)p.y)[o] = v;
+        sink(y, c, x, fmaf(acc, c == 0 ? a0 : (c == 1 ? a1 : a2), c == 0 ? b0 : (c == 1 ? b1 : b2)));
     }
+}
+
+// Steps 2 - 4 with the plain store: the tile of image b of p.y.
+template <bool CHW_IN, bool NHWC_OUT, bool BF16_OUT>
+__device__ __forceinline__ void tile_passes(const PrepP& p, const TileLds& L, const TileRect& t, const uint8_t* img, const int b,
+                                            const int y0, const int x0, const int th, const int tw) {
+    tile_rows<CHW_IN, NHWC_OUT>(p, L, t, img, th, tw, [&](const int y, const int c, const int x, const float v) {
+        tile_store<NHWC_OUT, BF16_OUT>(p, b, y0 + y, c, x0 + x, v);
+    });
 }
 
 
@@ -350,28 +370,174 @@ __global__ __launch_bounds__(256) void preprocess_u8_ragged_kernel(const PrepRag
 // The box record is device data too.  A record whose image would leave x forms no address: its tiles store nothing.  A box that
 // leaves its image is clamped into it, and a box that needs more taps than the launch's pitches has its counts clamped (in
 // tables_generated); each of these sets bit 2.  (Uniform over the workgroup, before any barrier.)
+struct BoxSrc {
+    const uint8_t* img;
+    int Hin, Win, top, left, h, w, flip;
+    bool ok, cut;       // ok: the image lies inside x (else nothing of the record is used); cut: the box or its taps had to be clamped
+};
+__device__ __forceinline__ BoxSrc box_source(const PrepP& p, const mv_preprocess_box& g, const long long x_bytes) {
+    BoxSrc s;
+    const long long img_bytes = (long long)g.Hin * g.Win * 3;
+    s.ok = g.Hin >= 1 && g.Win >= 1 && img_bytes < (1LL << 31) && g.offset >= 0 && g.offset <= x_bytes - img_bytes;
+    s.img = p.x + (s.ok ? g.offset : 0);
+    s.Hin = g.Hin; s.Win = g.Win; s.flip = g.flip != 0;
+    s.top = clampi(g.top, 0, g.Hin - 1); s.left = clampi(g.left, 0, g.Win - 1);
+    s.h = clampi(g.h, 1, g.Hin - s.top); s.w = clampi(g.w, 1, g.Win - s.left);
+    s.cut = s.top != g.top || s.left != g.left || s.h != g.h || s.w != g.w || taps_needed(s.h, p.Hout) > p.mh ||
+            taps_needed(s.w, p.Wout) > p.mw;
+    return s;
+}
+
 template <bool CHW_IN, bool NHWC_OUT, bool BF16_OUT>
 __global__ __launch_bounds__(256) void preprocess_u8_boxes_kernel(const PrepBoxesP r) {
     const int b = blockIdx.z;
-    const mv_preprocess_box g = r.rec[b];
     PrepP p = r.p;
-    const long long img_bytes = (long long)g.Hin * g.Win * 3;
-    const bool ok = g.Hin >= 1 && g.Win >= 1 && img_bytes < (1LL << 31) && g.offset >= 0 && g.offset <= r.x_bytes - img_bytes;
-    if (!ok) {
+    const BoxSrc s = box_source(p, r.rec[b], r.x_bytes);
+    if (!s.ok) {
         if (threadIdx.x == 0) atomicOr(p.status, 4u);
         return;
     }
-    p.Hin = g.Hin; p.Win = g.Win;
-    const int top = clampi(g.top, 0, g.Hin - 1), left = clampi(g.left, 0, g.Win - 1);
-    const int h = clampi(g.h, 1, g.Hin - top), w = clampi(g.w, 1, g.Win - left);
-    const bool cut = top != g.top || left != g.left || h != g.h || w != g.w || taps_needed(h, p.Hout) > p.mh ||
-                     taps_needed(w, p.Wout) > p.mw;
-    if (cut && threadIdx.x == 0) atomicOr(p.status, 4u);
+    p.Hin = s.Hin; p.Win = s.Win;
+    if (s.cut && threadIdx.x == 0) atomicOr(p.status, 4u);
     const int y0 = blockIdx.y * p.TH, x0 = blockIdx.x * p.TW;
     const int th = min(p.TH, p.Hout - y0), tw = min(p.TW, p.Wout - x0);
     const TileLds L = tile_lds<CHW_IN>(p);
-    const TileRect t = tables_generated(p, L, top, left, h, w, g.flip != 0, y0, x0, th, tw);
-    tile_passes<CHW_IN, NHWC_OUT, BF16_OUT>(p, L, t, p.x + g.offset, b, y0, x0, th, tw);
+    const TileRect t = tables_generated(p, L, s.top, s.left, s.h, s.w, s.flip, y0, x0, th, tw);
+    tile_passes<CHW_IN, NHWC_OUT, BF16_OUT>(p, L, t, s.img, b, y0, x0, th, tw);
+}
+
+// mv_preprocess_u8_mix_fwd.  The image workgroups (blockIdx.z < B): one tile of image b as in the boxes kernel, where every
+// element is a function of v_i (this image through its own box) and v_r (its partner through the partner's box):
+//     v_i = 0 inside image b's erase rectangle, v_r = 0 inside the PARTNER's;
+//     inside the cut rectangle v_r; else, without a partner or with lam == 1, v_i; else fadd(fmul(lam, v_i), fmul(oml, v_r)).
+// Which of the two resamples a tile runs is decided per tile from the records (uniform over the workgroup, before any barrier):
+//     v_r is needed  unless there is no partner, or lam == 1 and the tile lies wholly outside the cut rectangle;
+//     v_i is needed  unless there is a partner and the tile lies wholly inside the cut rectangle;
+//     a needed value whose erase rectangle holds the whole tile is 0 without staging its image.
+// A tile that runs both keeps the partner's th x tw x 3 fp32 values in LDS (`sv`, behind the tables: the launch was sized for it
+// when the host records hold a partner, `keep`) while the passes run again on its own window: the two staged windows are never
+// resident together.  The records are device data: a partner outside [0, B), a partner whose image leaves x, or a partner the
+// launch has no `sv` for is treated as none, rectangles are clamped to the output; each sets bit 2.
+// The target workgroups (blockIdx.z >= B) write targets[i][k] = fadd(fmul(lam_t, s(labels[i], k)), fmul(oml_t, s(labels[r], k))),
+// s(y, k) = k == y ? on : off, grid-stride over B * K; a label outside [0, K) matches no k (off everywhere) and sets bit 3.
+struct PrepMixP {
+    PrepP p;
+    const mv_preprocess_box* rec;
+    const mv_preprocess_mix* mix;
+    long long x_bytes;
+    const int* labels;
+    float* targets;
+    int B, K, keep;
+    float on, off;
+};
+
+struct OutRect {
+    int y0, x0, y1, x1;
+};
+__device__ __forceinline__ OutRect out_rect(const PrepP& p, int y0, int x0, int y1, int x1, bool& bad) {
+    const OutRect r = {clampi(y0, 0, p.Hout), clampi(x0, 0, p.Wout), clampi(y1, 0, p.Hout), clampi(x1, 0, p.Wout)};
+    bad |= r.y0 != y0 || r.x0 != x0 || r.y1 != y1 || r.x1 != x1;
+    return r;
+}
+__device__ __forceinline__ bool rect_has(const OutRect& r, int Y, int X) { return Y >= r.y0 && Y < r.y1 && X >= r.x0 && X < r.x1; }
+// the non-empty tile [y0, y0 + th) x [x0, x0 + tw) lies wholly inside r / shares a pixel with r
+__device__ __forceinline__ bool rect_holds(const OutRect& r, int y0, int x0, int th, int tw) {
+    return r.y0 <= y0 && y0 + th <= r.y1 && r.x0 <= x0 && x0 + tw <= r.x1;
+}
+__device__ __forceinline__ bool rect_meets(const OutRect& r, int y0, int x0, int th, int tw) {
+    return max(r.y0, y0) < min(r.y1, y0 + th) && max(r.x0, x0) < min(r.x1, x0 + tw);
+}
+
+__device__ __forceinline__ void mix_targets(const PrepMixP& r) {
+    const long long nthr = (long long)gridDim.x * gridDim.y * (gridDim.z - r.B) * 256;
+    const long long first = (((long long)(blockIdx.z - r.B) * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x) * 256 + threadIdx.x;
+    const long long total = (long long)r.B * r.K;
+    unsigned bits = 0;
+    for (long long e = first; e < total; e += nthr) {
+        const int i = (int)(e / r.K), k = (int)(e - (long long)i * r.K);
+        int pr = r.mix[i].partner;
+        if (pr < 0 || pr >= r.B) { pr = i; bits |= 4u; }
+        const int yi = r.labels[i], yr = r.labels[pr];
+        if (yi < 0 || yi >= r.K || yr < 0 || yr >= r.K) bits |= 8u;
+        r.targets[e] = mul_add_rn(r.mix[i].lam_t, k == yi ? r.on : r.off, r.mix[i].oml_t, k == yr ? r.on : r.off);
+    }
+    if (bits) atomicOr(r.p.status, bits);
+}
+
+template <bool CHW_IN, bool NHWC_OUT, bool BF16_OUT>
+__global__ __launch_bounds__(256) void preprocess_u8_mix_kernel(const PrepMixP r) {
+    if ((int)blockIdx.z >= r.B) {
+        mix_targets(r);
+        return;
+    }
+    const int b = blockIdx.z;
+    const PrepP& p = r.p;
+    const BoxSrc own = box_source(p, r.rec[b], r.x_bytes);
+    if (!own.ok) {
+        if (threadIdx.x == 0) atomicOr(p.status, 4u);
+        return;
+    }
+    const mv_preprocess_mix m = r.mix[b];
+    bool bad = own.cut;
+    int pr = m.partner;
+    if (pr < 0 || pr >= r.B || (pr != b && !r.keep)) { pr = b; bad = true; }
+    BoxSrc par = own;
+    if (pr != b) {
+        par = box_source(p, r.rec[pr], r.x_bytes);
+        if (!par.ok) { pr = b; par = own; bad = true; }
+        bad |= par.cut;
+    }
+    const bool mixed = pr != b;
+    const OutRect cut = out_rect(p, m.cy0, m.cx0, m.cy1, m.cx1, bad);
+    const OutRect er_i = out_rect(p, m.ey0, m.ex0, m.ey1, m.ex1, bad);
+    OutRect er_r = er_i;
+    if (mixed) {
+        const mv_preprocess_mix mr = r.mix[pr];
+        er_r = out_rect(p, mr.ey0, mr.ex0, mr.ey1, mr.ex1, bad);
+    }
+    if (bad && threadIdx.x == 0) atomicOr(p.status, 4u);
+    const float lam = m.lam, oml = m.oml;
+
+    const int y0 = blockIdx.y * p.TH, x0 = blockIdx.x * p.TW;
+    const int th = min(p.TH, p.Hout - y0), tw = min(p.TW, p.Wout - x0);
+    const bool need_r = mixed && (lam != 1.f || rect_meets(cut, y0, x0, th, tw));
+    const bool need_i = !(mixed && rect_holds(cut, y0, x0, th, tw));
+    const bool run_r = need_r && !rect_holds(er_r, y0, x0, th, tw);
+    const bool run_i = need_i && !rect_holds(er_i, y0, x0, th, tw);
+
+    auto emit = [&](const int y, const int c, const int x, float vi, float vr) {
+        const int Y = y0 + y, X = x0 + x;
+        if (rect_has(er_i, Y, X)) vi = 0.f;
+        if (rect_has(er_r, Y, X)) vr = 0.f;
+        float o;
+        if (mixed && rect_has(cut, Y, X)) o = vr;
+        else if (!mixed || lam == 1.f) o = vi;
+        else o = mul_add_rn(lam, vi, oml, vr);
+        tile_store<NHWC_OUT, BF16_OUT>(p, b, Y, c, X, o);
+    };
+    const TileLds L = tile_lds<CHW_IN>(p);
+    float* sv = L.swx + p.TW * p.mw;                         // [th][3][TW] of v_r, only where the launch has `keep`
+    auto resample = [&](const BoxSrc& s, auto&& sink) {
+        PrepP q = p;
+        q.Hin = s.Hin; q.Win = s.Win;
+        const TileRect t = tables_generated(q, L, s.top, s.left, s.h, s.w, s.flip, y0, x0, th, tw);
+        tile_rows<CHW_IN, NHWC_OUT>(q, L, t, s.img, th, tw, sink);
+    };
+    if (run_r && run_i) {
+        resample(par, [&](const int y, const int c, const int x, const float v) { sv[(y * 3 + c) * p.TW + x] = v; });
+        __syncthreads();                                     // the tables and sums of the partner's passes are rewritten next
+        resample(own, [&](const int y, const int c, const int x, const float v) { emit(y, c, x, v, sv[(y * 3 + c) * p.TW + x]); });
+    } else if (run_r) {
+        resample(par, [&](const int y, const int c, const int x, const float v) { emit(y, c, x, 0.f, v); });
+    } else if (run_i) {
+        resample(own, [&](const int y, const int c, const int x, const float v) { emit(y, c, x, v, 0.f); });
+    } else {
+        for (int it = threadIdx.x; it < th * 3 * tw; it += 256) {
+            int y, c, x;
+            tile_elem<NHWC_OUT>(it, tw, y, c, x);
+            emit(y, c, x, 0.f, 0.f);
+        }
+    }
 }
 
 // The elements of a th x tw tile outside its valid th_v x tw_v prefix <- v[c], in the store order of tile_passes' step 4.
@@ -380,23 +546,9 @@ __device__ __forceinline__ void tile_fill(const PrepP& p, const int b, const int
                                           const int th_v, const int tw_v, const float v0, const float v1, const float v2) {
     for (int it = threadIdx.x; it < th * 3 * tw; it += 256) {
         int y, c, x;
-        if (NHWC_OUT) {
-            const int yx = it / 3;
-            c = it - yx * 3;
-            y = yx / tw;
-            x = yx - y * tw;
-        } else {
-            const int yc = it / tw;
-            x = it - yc * tw;
-            y = yc / 3;
-            c = yc - y * 3;
-        }
+        tile_elem<NHWC_OUT>(it, tw, y, c, x);
         if (y < th_v && x < tw_v) continue;
-        const float v = c == 0 ? v0 : (c == 1 ? v1 : v2);
-        const size_t o = NHWC_OUT ? (((size_t)b * p.Hout + y0 + y) * p.Wout + x0 + x) * 3 + c
-                                  : (((size_t)b * 3 + c) * p.Hout + y0 + y) * p.Wout + x0 + x;
-        if (BF16_OUT) ((bf16_t*)p.y)[o] = f2bf(v);
-        else ((float*)p.y)[o] = v;
+        tile_store<NHWC_OUT, BF16_OUT>(p, b, y0 + y, c, x0 + x, c == 0 ? v0 : (c == 1 ? v1 : v2));
     }
 }
 
@@ -474,16 +626,45 @@ size_t lds_bytes(int TH, int TW, int rows_cap, int cols_cap, int in_chw, int mh,
 // down-sampling (up to 11.5x, 24 taps) inside the budget; their stores are shorter runs, which such a reduction can afford.
 // caps(TH, TW, &rows, &cols): the input rectangle a TH x TW tile can need.  p.mh / p.mw are read; TH, TW, rows_cap, cols_cap and
 // pitch of the chosen tile (or of the smallest, if none fits) are left in p, its LDS size in *lds.
-template <class F> bool pick_tile(PrepP& p, int in_chw, size_t* lds, F&& caps) {
+// keep: the tile also holds TH x 3 x TW fp32 results behind its tables (mv_preprocess_u8_mix_fwd: the partner's values).
+template <class F> bool pick_tile(PrepP& p, int in_chw, size_t* lds, F&& caps, bool keep = false) {
     static const int tiles[][2] = {{32, 32}, {16, 32}, {16, 16}, {8, 16}, {4, 8}};
     for (const auto& t : tiles) {
         p.TH = t[0];
         p.TW = t[1];
         caps(p.TH, p.TW, &p.rows_cap, &p.cols_cap);
-        *lds = lds_bytes(p.TH, p.TW, p.rows_cap, p.cols_cap, in_chw, p.mh, p.mw, &p.pitch);
+        *lds = lds_bytes(p.TH, p.TW, p.rows_cap, p.cols_cap, in_chw, p.mh, p.mw, &p.pitch) + (keep ? (size_t)p.TH * 3 * p.TW * 4 : 0);
         if (*lds <= 64 * 1024) return true;
     }
     return false;
+}
+
+// The host records of the boxes and the mix entry, in full: image inside x, box non-empty and inside its image, taps within the
+// limit.  *mh, *mw: the most taps any box of the batch needs.
+int check_boxes(const char* who, const mv_preprocess_box* rec_host, int B, int64_t x_bytes, int Hout, int Wout, int* mh, int* mw) {
+    *mh = *mw = 0;
+    for (int i = 0; i < B; ++i) {
+        const mv_preprocess_box& g = rec_host[i];
+        MV_CHECK_ARG(g.Hin > 0 && g.Win > 0, "%s: image %d: bad sizes", who, i);
+        const long long img_bytes = (long long)g.Hin * g.Win * 3;
+        MV_CHECK_ARG(img_bytes < (1LL << 31), "%s: image %d: %dx%d too large", who, i, g.Hin, g.Win);
+        MV_CHECK_ARG(g.offset >= 0 && g.offset <= x_bytes - img_bytes,
+                     "%s: image %d: %lld bytes at offset %lld do not lie inside the buffer of %lld bytes", who, i, img_bytes,
+                     (long long)g.offset, (long long)x_bytes);
+        MV_CHECK_ARG(g.h > 0 && g.w > 0 && g.top >= 0 && g.left >= 0 && (long long)g.top + g.h <= g.Hin &&
+                         (long long)g.left + g.w <= g.Win,
+                     "%s: image %d: box %dx%d at (%d, %d) does not lie inside the image %dx%d", who, i, g.h, g.w, g.top, g.left,
+                     g.Hin, g.Win);
+        const int need_h = taps_needed(g.h, Hout), need_w = taps_needed(g.w, Wout);
+        if (need_h > MV_PREPROCESS_MAX_TAPS || need_w > MV_PREPROCESS_MAX_TAPS) {
+            set_error("%s: image %d: box %dx%d -> %dx%d needs up to %d x %d taps; at most %d per axis (down-sampling by up to %.1f)",
+                      who, i, g.h, g.w, Hout, Wout, need_h, need_w, MV_PREPROCESS_MAX_TAPS, (MV_PREPROCESS_MAX_TAPS - 1) / 2.0);
+            return MV_E_UNSUPPORTED;
+        }
+        *mh = need_h > *mh ? need_h : *mh;
+        *mw = need_w > *mw ? need_w : *mw;
+    }
+    return MV_OK;
 }
 
 // launches KERNEL<in_chw, out_nhwc, out_dtype == MV_BF16> with ARG on (grid, 256 threads, lds, st) of the calling entry
@@ -649,28 +830,7 @@ int mv_preprocess_u8_boxes_fwd(const void* x, int64_t x_bytes, void* y, const mv
         return MV_E_UNSUPPORTED;
     }
     int mh = 0, mw = 0;
-    for (int i = 0; i < B; ++i) {
-        const mv_preprocess_box& g = rec_host[i];
-        MV_CHECK_ARG(g.Hin > 0 && g.Win > 0, "preprocess_u8_boxes: image %d: bad sizes", i);
-        const long long img_bytes = (long long)g.Hin * g.Win * 3;
-        MV_CHECK_ARG(img_bytes < (1LL << 31), "preprocess_u8_boxes: image %d: %dx%d too large", i, g.Hin, g.Win);
-        MV_CHECK_ARG(g.offset >= 0 && g.offset <= x_bytes - img_bytes,
-                     "preprocess_u8_boxes: image %d: %lld bytes at offset %lld do not lie inside the buffer of %lld bytes", i, img_bytes,
-                     (long long)g.offset, (long long)x_bytes);
-        MV_CHECK_ARG(g.h > 0 && g.w > 0 && g.top >= 0 && g.left >= 0 && (long long)g.top + g.h <= g.Hin &&
-                         (long long)g.left + g.w <= g.Win,
-                     "preprocess_u8_boxes: image %d: box %dx%d at (%d, %d) does not lie inside the image %dx%d", i, g.h, g.w, g.top,
-                     g.left, g.Hin, g.Win);
-        const int need_h = taps_needed(g.h, Hout), need_w = taps_needed(g.w, Wout);
-        if (need_h > MV_PREPROCESS_MAX_TAPS || need_w > MV_PREPROCESS_MAX_TAPS) {
-            set_error("preprocess_u8_boxes: image %d: box %dx%d -> %dx%d needs up to %d x %d taps; at most %d per axis (down-sampling "
-                      "by up to %.1f)", i, g.h, g.w, Hout, Wout, need_h, need_w, MV_PREPROCESS_MAX_TAPS,
-                      (MV_PREPROCESS_MAX_TAPS - 1) / 2.0);
-            return MV_E_UNSUPPORTED;
-        }
-        mh = need_h > mh ? need_h : mh;
-        mw = need_w > mw ? need_w : mw;
-    }
+    if (const int rc = check_boxes("preprocess_u8_boxes", rec_host, B, x_bytes, Hout, Wout, &mh, &mw)) return rc;
     const size_t out_bytes = (size_t)B * 3 * Hout * Wout * dsize(out_dtype);
     const uintptr_t xa = (uintptr_t)x, ya = (uintptr_t)y;
     if (xa < ya + out_bytes && ya < xa + (size_t)x_bytes) {
@@ -702,6 +862,89 @@ int mv_preprocess_u8_boxes_fwd(const void* x, int64_t x_bytes, void* y, const mv
     hipStream_t st = (hipStream_t)stream;
     set_kernel_name("preprocess_u8_boxes");
     PREPROCESS_LAUNCH(preprocess_u8_boxes_kernel, r);
+    MV_LAUNCH_CHECK();
+    return MV_OK;
+}
+
+int mv_preprocess_u8_mix_fwd(const void* x, int64_t x_bytes, void* y, const mv_preprocess_box* rec_host,
+                             const mv_preprocess_box* rec_dev, const mv_preprocess_mix* mix_host, const mv_preprocess_mix* mix_dev,
+                             const float* a, const float* b, const int32_t* labels_host, const int32_t* labels_dev, float* targets,
+                             int K, float on, float off, int B, int Hout, int Wout, int in_chw, int out_dtype, int out_nhwc,
+                             mv_stream_t stream) {
+    MV_CHECK_ARG(B > 0 && Hout > 0 && Wout > 0 && x_bytes > 0, "preprocess_u8_mix: bad sizes");
+    MV_CHECK_ARG(out_dtype == MV_F32 || out_dtype == MV_BF16, "preprocess_u8_mix: out_dtype must be MV_F32 or MV_BF16");
+    MV_CHECK_ARG(B <= 32767, "preprocess_u8_mix: batch %d too large", B);
+    if (!x || !y || !rec_host || !rec_dev || !mix_host || !mix_dev || !a || !b) {
+        set_error("preprocess_u8_mix: null buffer");
+        return MV_E_UNSUPPORTED;
+    }
+    MV_CHECK_ARG((labels_dev != nullptr) == (targets != nullptr), "preprocess_u8_mix: labels and targets go together, got %s without %s",
+                 labels_dev ? "labels" : "targets", labels_dev ? "targets" : "labels");
+    MV_CHECK_ARG(!labels_host || labels_dev, "preprocess_u8_mix: a host copy of the labels without the device labels");
+    MV_CHECK_ARG(!labels_dev || (K > 0 && (long long)B * K < (1LL << 31)), "preprocess_u8_mix: %d classes for %d images", K, B);
+    int mh = 0, mw = 0;
+    if (const int rc = check_boxes("preprocess_u8_mix", rec_host, B, x_bytes, Hout, Wout, &mh, &mw)) return rc;
+    auto unit = [](float v) { return std::isfinite(v) && v >= 0.f && v <= 1.f; };
+    auto inside = [&](int y0, int x0, int y1, int x1) {
+        return y0 >= 0 && y0 <= Hout && y1 >= 0 && y1 <= Hout && x0 >= 0 && x0 <= Wout && x1 >= 0 && x1 <= Wout;
+    };
+    bool keep = false;
+    for (int i = 0; i < B; ++i) {
+        const mv_preprocess_mix& m = mix_host[i];
+        MV_CHECK_ARG(m.partner >= 0 && m.partner < B, "preprocess_u8_mix: image %d: partner %d does not lie in [0, %d)", i, m.partner, B);
+        MV_CHECK_ARG(unit(m.lam) && unit(m.oml) && unit(m.lam_t) && unit(m.oml_t),
+                     "preprocess_u8_mix: image %d: lam %g, oml %g, lam_t %g, oml_t %g must be finite and lie in [0, 1]", i,
+                     (double)m.lam, (double)m.oml, (double)m.lam_t, (double)m.oml_t);
+        MV_CHECK_ARG(inside(m.cy0, m.cx0, m.cy1, m.cx1),
+                     "preprocess_u8_mix: image %d: cut rectangle (%d, %d, %d, %d) does not lie inside the output %dx%d", i, m.cy0, m.cx0,
+                     m.cy1, m.cx1, Hout, Wout);
+        MV_CHECK_ARG(inside(m.ey0, m.ex0, m.ey1, m.ex1),
+                     "preprocess_u8_mix: image %d: erase rectangle (%d, %d, %d, %d) does not lie inside the output %dx%d", i, m.ey0,
+                     m.ex0, m.ey1, m.ex1, Hout, Wout);
+        MV_CHECK_ARG(!labels_host || (labels_host[i] >= 0 && labels_host[i] < K),
+                     "preprocess_u8_mix: image %d: label %d does not lie in [0, %d)", i, labels_host ? labels_host[i] : 0, K);
+        keep |= m.partner != i;
+    }
+    // an output may overlap neither the input nor the other output
+    const uintptr_t lo[3] = {(uintptr_t)x, (uintptr_t)y, (uintptr_t)targets};
+    const size_t len[3] = {(size_t)x_bytes, (size_t)B * 3 * Hout * Wout * dsize(out_dtype), targets ? (size_t)B * K * 4 : 0};
+    static const char* const names[3] = {"images", "output", "targets"};
+    for (int o = 1; o < 3; ++o)
+        for (int i = 0; i < o; ++i)
+            if (len[o] && len[i] && lo[i] < lo[o] + len[o] && lo[o] < lo[i] + len[i]) {
+                set_error("preprocess_u8_mix: %s and %s overlap", names[i], names[o]);
+                return MV_E_UNSUPPORTED;
+            }
+
+    // One tile and one LDS size per launch, as in the boxes entry; with a partner anywhere in the batch the tile also keeps the
+    // partner's results (TH x 3 x TW fp32) while its own window is staged.
+    PrepMixP r;
+    PrepP& p = r.p;
+    p.x = (const uint8_t*)x; p.y = y; p.tab_h = nullptr; p.tab_w = nullptr; p.a = a; p.b = b; p.status = nullptr;
+    p.Hin = 0; p.Win = 0; p.Hout = Hout; p.Wout = Wout; p.mh = mh; p.mw = mw;
+    r.rec = rec_dev; r.mix = mix_dev; r.x_bytes = x_bytes; r.labels = labels_dev; r.targets = targets;
+    r.B = B; r.K = K; r.keep = keep; r.on = on; r.off = off;
+    size_t lds = 0;
+    if (!pick_tile(p, in_chw, &lds, [&](int TH, int TW, int* rows, int* cols) {
+            *rows = *cols = 0;
+            for (int i = 0; i < B; ++i) {
+                *rows = std::max(*rows, span_cap(TH, rec_host[i].h, Hout));
+                *cols = std::max(*cols, span_cap(TW, rec_host[i].w, Wout));
+            }
+        }, keep)) {
+        set_error("preprocess_u8_mix: the batch does not fit the LDS tile (%zu bytes for the smallest tile)", lds);
+        return MV_E_UNSUPPORTED;
+    }
+    // target workgroups: whole z-slices of the image grid behind the B images, about four elements per thread, grid-stride
+    const long long per_slice = (long long)((Wout + p.TW - 1) / p.TW) * ((Hout + p.TH - 1) / p.TH) * 256 * 4;
+    const long long slices = targets ? std::min<long long>(((long long)B * K + per_slice - 1) / per_slice, 65535 - B) : 0;
+    const dim3 grid((Wout + p.TW - 1) / p.TW, (Hout + p.TH - 1) / p.TH, B + (unsigned)slices);
+    MV_CHECK_ARG(grid.y <= 65535, "preprocess_u8_mix: %d output rows are too many tiles", Hout);
+    p.status = device_status_word();                         // the first touch of the device: everything above is host work
+    MV_CHECK_ARG(p.status != nullptr, "preprocess_u8_mix: the device status word is not available");
+    hipStream_t st = (hipStream_t)stream;
+    set_kernel_name("preprocess_u8_mix");
+    PREPROCESS_LAUNCH(preprocess_u8_mix_kernel, r);
     MV_LAUNCH_CHECK();
     return MV_OK;
 }

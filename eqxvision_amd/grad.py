@@ -1275,5 +1275,5 @@ def apply_updates(model, updates):
 
 
 from . import _optim                                                      # noqa: E402  (it uses the helpers above)
-from ._optim import (adamw, chain, clip_by_global_norm, constant_schedule, cosine_decay_schedule, sgd,     # noqa: E402,F401
+from ._optim import (adamw, chain, clip_by_global_norm, constant_schedule, cosine_decay_schedule, ema, sgd,     # noqa: E402,F401
                      warmup_cosine_decay_schedule)

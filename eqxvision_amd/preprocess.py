@@ -22,6 +22,13 @@ uploaded on every call.  `mv_preprocess_u8_boxes_fwd` takes one 40-byte record p
 whether to mirror) and generates the filter of each tile in the kernel, in float64, by the formulas of `axis_table`; the host
 only draws the boxes (`random_resized_crop_boxes`, `random_flips`).  `crop_resize_normalize` is the deterministic core.
 
+    x, targets = eqv.preprocess.imagenet_train_mixed(images_u8, labels, key, num_classes)   # ... -> RandomErasing -> Mixup / CutMix
+
+The rest of torchvision's classification recipe rides in the same launch.  `mv_preprocess_u8_mix_fwd` takes the box records and a
+second 52-byte record per image (`MIX`: the partner mixed in, the two weights, a cut rectangle, an erase rectangle, the weights of
+the two labels) and writes the batch and the smoothed soft targets [B, K]; a tile resamples its partner only where it needs it.
+The host draws (`mixup_cutmix_draw`, `random_erasing_draw`); `crop_resize_normalize_mix` is the deterministic core.
+
     x, labels = eqv.preprocess.segmentation_train(images_u8, masks_u8, key)   # RandomResize -> flip -> RandomCrop(pad) -> Normalize
 
 The segmentation preset resizes the WHOLE image to a random size, mirrors it, pads it on the right and bottom up to the crop and
@@ -46,6 +53,7 @@ from . import _lib
 from . import random as _random
 from ._act import DT, TORCH_DT, device, empty, stream_ptr
 from ._act import _tls as _act_tls
+from ._module import DevArray
 
 IMAGENET_MEAN = (0.485, 0.456, 0.406)
 IMAGENET_STD = (0.229, 0.224, 0.225)
@@ -504,6 +512,244 @@ def imagenet_train(images_u8, key, size=224, scale=(0.08, 1.0), ratio=(3.0 / 4.0
     boxes = random_resized_crop_boxes(k_box, sizes, scale, ratio)
     flips = random_flips(k_flip, len(sizes), flip_p)
     return crop_resize_normalize(images_u8, boxes[0] if single else boxes, size, flips, mean, std, dtype, "nchw", channels_last)
+
+
+# ---- the rest of the classification recipe: mixup / cutmix, random erasing, soft targets -> mv_preprocess_u8_mix_fwd, one launch ----
+
+# `mv_preprocess_mix` of include/eqxvision_amd.h, 52 bytes
+MIX = np.dtype([("partner", "<i4"), ("lam", "<f4"), ("oml", "<f4"), ("cy0", "<i4"), ("cx0", "<i4"), ("cy1", "<i4"), ("cx1", "<i4"),
+                ("ey0", "<i4"), ("ex0", "<i4"), ("ey1", "<i4"), ("ex1", "<i4"), ("lam_t", "<f4"), ("oml_t", "<f4")])
+ERASE_ATTEMPTS = 10    # torchvision's RandomErasing.get_params tries ten rectangles before it gives up
+
+
+def mixup_cutmix_draw(key, B, size, mixup_alpha=0.2, cutmix_alpha=1.0, switch_p=0.5):
+    """The batch-level draw of torchvision's reference `RandomMixup` / `RandomCutmix` (references/classification/transforms.py, one
+    of the two chosen per batch) for B images of output `size` (an int or (H, W)).  Host only.  Returns per-image arrays
+    (partner int32 [B], lam fp32 [B], cut_rect int32 [B, 4] of (y0, x0, y1, x1) in output pixels, lam_t fp32 [B]); the draw is
+    one per batch, so every row holds the same numbers.  partner[i] = (i - 1) mod B, which is `batch.roll(1, 0)`.
+    `key` is split in three.  The first decides the branch: cutmix iff random.uniform01 < switch_p when both alphas are positive;
+    an alpha <= 0 disables its branch, both disabled or B == 1 give no mixing (partner[i] = i, lam = lam_t = 1, empty
+    rectangle).  The second gives lam ~ Beta(alpha, alpha) from `random.generator`.  Mixup: no rectangle, lam_t = lam.  Cutmix:
+    the third key gives the centre, r_x = min(int(u0 W), W - 1), r_y = min(int(u1 H), H - 1) from random.uniform01; with
+    r = 0.5 sqrt(1 - lam) the half extents are int(r W), int(r H); the rectangle is clamped to the image,
+    lam_t = 1 - area / (H W), and the pixel weight lam is 1: inside the rectangle the partner, outside the image itself.
+    This is torchvision's DISTRIBUTION, not torch's random stream: the same seed gives other draws than torchvision does."""
+    B = int(B)
+    H, W = _pair(size, "size")
+    if B < 1:
+        raise ValueError(f"preprocess: a batch of {B} images")
+    if not 0.0 <= float(switch_p) <= 1.0:
+        raise ValueError(f"preprocess: switch_p = {switch_p} must lie in [0, 1]")
+    k_choice, k_lam, k_box = _random.split(key, 3)
+    mixup, cutmix = float(mixup_alpha) > 0.0, float(cutmix_alpha) > 0.0
+    own = np.arange(B, dtype=np.int32)
+    if B == 1 or not (mixup or cutmix):
+        return own, np.ones(B, np.float32), np.zeros((B, 4), np.int32), np.ones(B, np.float32)
+    use_cutmix = cutmix and (not mixup or float(_random.uniform01(k_choice, 1)[0]) < float(switch_p))
+    alpha = float(cutmix_alpha if use_cutmix else mixup_alpha)
+    lam = float(_random.generator(k_lam).beta(alpha, alpha))
+    rect = (0, 0, 0, 0)
+    if use_cutmix:
+        u = np.asarray(_random.uniform01(k_box, 2), np.float64)
+        r_x, r_y = min(int(u[0] * W), W - 1), min(int(u[1] * H), H - 1)
+        r = 0.5 * float(np.sqrt(1.0 - lam))
+        hw, hh = int(r * W), int(r * H)
+        x0, y0, x1, y1 = max(r_x - hw, 0), max(r_y - hh, 0), min(r_x + hw, W), min(r_y + hh, H)
+        rect = (y0, x0, y1, x1)
+        lam_t, lam = 1.0 - (x1 - x0) * (y1 - y0) / (H * W), 1.0
+    else:
+        lam_t = lam
+    return ((own - 1) % B).astype(np.int32), np.full(B, lam, np.float32), np.tile(np.asarray(rect, np.int32), (B, 1)), \
+        np.full(B, lam_t, np.float32)
+
+
+def random_erasing_draw(key, B, size, p=0.5, scale=(0.02, 0.33), ratio=(0.3, 3.3)) -> np.ndarray:
+    """torchvision's `RandomErasing(p, scale, ratio, value=0)` for B images of output `size` (an int or (H, W)): int32 [B, 4] of
+    (y0, x0, y1, x1) in output pixels, an empty rectangle (all zeros) where nothing is erased.  Host only.  Image i draws
+    u = random.uniform(random.split(key, B)[i], (1 + 10 * 4,)): it is erased iff u[0] < p; attempt t reads u[1 + 4 t : 5 + 4 t] and
+    takes area = H W (scale0 + u0 (scale1 - scale0)), aspect = exp(log r0 + u1 (log r1 - log r0)), h = int(round(sqrt(area aspect))),
+    w = int(round(sqrt(area / aspect))); the first attempt with h < H and w < W wins and is placed at
+    y0 = min(int(u2 (H - h + 1)), H - h), x0 likewise from u3.  If none fits, nothing is erased (`get_params` returns the image).
+    This is torchvision's DISTRIBUTION, not torch's random stream: the same seed gives other rectangles than torchvision does."""
+    B = int(B)
+    H, W = _pair(size, "size")
+    s0, s1 = (float(v) for v in scale)
+    r0, r1 = (float(v) for v in ratio)
+    if not (0.0 < s0 <= s1) or not (0.0 < r0 <= r1):
+        raise ValueError(f"preprocess: scale {scale} and ratio {ratio} must be positive (min, max) pairs")
+    if B < 1:
+        raise ValueError(f"preprocess: a batch of {B} images")
+    out = np.zeros((B, 4), np.int32)
+    log0, log1 = np.log(np.float64(r0)), np.log(np.float64(r1))
+    for i, k in enumerate(_random.split(key, B)):
+        u = np.asarray(_random.uniform(k, (1 + ERASE_ATTEMPTS * 4,)), np.float64)
+        if not u[0] < p:
+            continue
+        for t in range(ERASE_ATTEMPTS):
+            u0, u1, u2, u3 = u[1 + 4 * t:5 + 4 * t]
+            area = H * W * (s0 + u0 * (s1 - s0))
+            ar = np.exp(log0 + u1 * (log1 - log0))
+            h, w = int(round(float(np.sqrt(area * ar)))), int(round(float(np.sqrt(area / ar))))
+            if h < H and w < W:
+                y0, x0 = min(int(u2 * (H - h + 1)), H - h), min(int(u3 * (W - w + 1)), W - w)
+                out[i] = (y0, x0, y0 + h, x0 + w)
+                break
+    return out
+
+
+def _per_image_array(v, B, tail, kind, what, default):
+    """`v` as an array [B] + tail of integers (kind "i") or floats ("f"); None -> `default`."""
+    if v is None:
+        return default
+    a = np.asarray(v)
+    if a.shape != (B,) + tail or a.dtype.kind not in ("iu" if kind == "i" else "iuf"):
+        want = "integers" if kind == "i" else "numbers"
+        raise ValueError(f"preprocess: {what} must be {want} {list((B,) + tail)}, one entry per image, got {a.dtype} {tuple(a.shape)}")
+    return a.astype(np.int64 if kind == "i" else np.float64)
+
+
+def mix_plan(B, size, partner=None, lam=None, cut=None, erase=None, lam_t=None):
+    """Host half of `crop_resize_normalize_mix`, no device involved: the MIX records [B] of a batch with output `size`.  partner
+    int [B] (None: nobody is mixed), lam [B] (None: 1), cut / erase int [B, 4] of (y0, x0, y1, x1) in output pixels, half-open (None
+    or y1 <= y0 or x1 <= x0: none), lam_t [B] (None: lam).  oml and oml_t are 1 - lam and 1 - lam_t, taken in float64 from the fp32
+    values and rounded once.  Every refusal is a ValueError that names the image."""
+    hout, wout = _pair(size, "size")
+    pa = _per_image_array(partner, B, (), "i", "partner", np.arange(B, dtype=np.int64))
+    la = _per_image_array(lam, B, (), "f", "lam", np.ones(B))
+    lt = _per_image_array(lam_t, B, (), "f", "lam_t", la)
+    ct = _per_image_array(cut, B, (4,), "i", "cut", np.zeros((B, 4), np.int64))
+    er = _per_image_array(erase, B, (4,), "i", "erase", np.zeros((B, 4), np.int64))
+    rec = np.zeros(B, MIX)
+    for i in range(B):
+        who = f"preprocess: image {i}"
+        if not 0 <= pa[i] < B:
+            raise ValueError(f"{who}: partner {int(pa[i])} does not lie in [0, {B})")
+        for name, v in (("lam", la[i]), ("lam_t", lt[i])):
+            if not (np.isfinite(v) and 0.0 <= v <= 1.0):
+                raise ValueError(f"{who}: {name} = {float(v)} must be finite and lie in [0, 1]")
+        for name, (y0, x0, y1, x1) in (("cut", ct[i]), ("erase", er[i])):
+            if not (0 <= y0 <= hout and 0 <= y1 <= hout and 0 <= x0 <= wout and 0 <= x1 <= wout):
+                raise ValueError(f"{who}: {name} rectangle {(int(y0), int(x0), int(y1), int(x1))} does not lie inside the output "
+                                 f"{hout}x{wout}")
+        l32, t32 = np.float32(la[i]), np.float32(lt[i])
+        rec[i] = (pa[i], l32, np.float32(1.0 - np.float64(l32))) + tuple(ct[i]) + tuple(er[i]) + (t32, np.float32(1.0 - np.float64(t32)))
+    return rec
+
+
+def smoothing_values(label_smoothing, num_classes):
+    """(on, off) fp32 of a smoothed one-hot row: on = 1 - eps + eps / K, off = eps / K, computed in float64 and rounded once."""
+    eps, K = float(label_smoothing), int(num_classes)
+    if K < 1:
+        raise ValueError(f"preprocess: num_classes = {num_classes} must be positive")
+    if not 0.0 <= eps < 1.0:
+        raise ValueError(f"preprocess: label_smoothing = {label_smoothing} must lie in [0, 1)")
+    return np.float32(1.0 - eps + eps / K), np.float32(eps / K)
+
+
+def crop_resize_normalize_mix(images_u8, boxes, size, flip=None, labels=None, num_classes=None, partner=None, lam=None, cut=None,
+                              erase=None, lam_t=None, label_smoothing=0.0, mean=IMAGENET_MEAN, std=IMAGENET_STD, dtype="fp32",
+                              layout="nchw", channels_last=None):
+    """`crop_resize_normalize` with the rest of torchvision's classification recipe in the same launch
+    (`mv_preprocess_u8_mix_fwd`).  With v_i the fp32 value `crop_resize_normalize` gives image i before the output is rounded:
+    v_i is 0 inside `erase[i]` = (y0, x0, y1, x1) (output pixels, half-open: RandomErasing(value=0), after Normalize); then, with
+    r = partner[i], the output is v_r inside `cut[i]`, v_i where r == i or lam[i] == 1, else lam[i] v_i + (1 - lam[i]) v_r as two
+    rounded products and one rounded sum.  An image is erased before it is mixed, so its erase rectangle shows in every image it is
+    the partner of.  `labels` (int [B], host or a device int32 tensor) and `num_classes` give soft targets fp32 [B, K],
+    lam_t[i] s(labels[i]) + (1 - lam_t[i]) s(labels[r]) with s the one-hot row smoothed by `label_smoothing` (`smoothing_values`);
+    `lam_t` defaults to `lam`.  Returns (x, targets): x as `crop_resize_normalize` returns it, targets a `DevArray` -- what
+    `optim.softmax_cross_entropy(out, targets)` reads -- or None without labels.  Host labels outside [0, K) are refused; device
+    labels are checked by the kernel (bit 3 of the device status).  `images_u8`: as for `crop_resize_normalize`; a single image
+    has nobody to be mixed with and is refused when `partner` says otherwise.  One launch on the current stream.  The call cannot
+    be recorded by `filter_jit`: the boxes and the draws belong to this one call."""
+    if getattr(_act_tls, "keep", None) is not None:
+        raise ValueError("preprocess: crop_resize_normalize_mix cannot be recorded by filter_jit: its boxes, flips, partners and "
+                         "rectangles belong to this one call, and a replay would apply them to other images; preprocess outside "
+                         "the recorded function")
+    if isinstance(images_u8, (list, tuple)):
+        chw, sizes = _check_list(images_u8, channels_last)
+        batched = True
+    else:
+        x, batched, chw, hin, win = _check_input(images_u8, channels_last)
+        sizes = [(hin, win)] * (int(x.shape[0]) if batched else 1)
+        if batched and len(sizes) == 0:
+            raise ValueError("preprocess: the batch of images is empty")
+        if not batched:
+            if partner is not None and np.any(np.asarray(partner).reshape(-1) != 0):
+                raise ValueError("preprocess: a single image has no partner to be mixed with; give a batch, or partner=None")
+            one = lambda v, n: v if v is None else np.asarray(v).reshape((1,) + ((n,) if n else ()))   # noqa: E731
+            boxes = np.asarray(boxes).reshape(1, -1) if np.asarray(boxes).ndim == 1 else boxes
+            flip = flip if flip is None else np.asarray(flip).reshape(-1)
+            partner, lam, lam_t, cut, erase = one(partner, 0), one(lam, 0), one(lam_t, 0), one(cut, 4), one(erase, 4)
+            if labels is not None and not isinstance(labels, torch.Tensor):
+                labels = np.asarray(labels).reshape(-1)
+    _check_output(dtype, layout)
+    B = len(sizes)
+    rec, (hout, wout) = boxes_plan(sizes, boxes, flip, size)
+    mix = mix_plan(B, (hout, wout), partner, lam, cut, erase, lam_t)
+    lab_host, lab_dev, K, on, off = None, None, 0, np.float32(1.0), np.float32(0.0)
+    if labels is not None:
+        if num_classes is None:
+            raise ValueError("preprocess: labels need num_classes")
+        K = int(num_classes)
+        on, off = smoothing_values(label_smoothing, K)
+        if _is_device_tensor(labels):
+            if labels.dtype != torch.int32 or labels.numel() != B:
+                raise ValueError(f"preprocess: device labels must be an int32 tensor [{B}], got {labels.dtype} {tuple(labels.shape)}")
+        else:
+            lab_host = np.asarray(labels.numpy() if isinstance(labels, torch.Tensor) else labels)
+            if lab_host.dtype.kind not in "iu" or lab_host.shape != (B,):
+                raise ValueError(f"preprocess: labels must be integers [{B}], one label per image, got {lab_host.dtype} "
+                                 f"{tuple(lab_host.shape)}")
+            for i, v in enumerate(lab_host):
+                if not 0 <= int(v) < K:
+                    raise ValueError(f"preprocess: image {i}: label {int(v)} does not lie in [0, {K})")
+            lab_host = np.ascontiguousarray(lab_host, np.int32)
+    affine(mean, std)                                        # validates before the device is touched
+    a, b = _device_affine(mean, std)
+    if isinstance(images_u8, (list, tuple)):
+        t = pack_images(images_u8)
+    else:
+        t = x if isinstance(x, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(x))
+        t = t.to(device(), non_blocking=True).contiguous()
+    rec_dev, mix_dev = torch.from_numpy(rec.view(np.uint8)).to(device()), torch.from_numpy(mix.view(np.uint8)).to(device())
+    y = empty((B, 3, hout, wout) if layout == "nchw" else (B, hout, wout, 3), TORCH_DT[dtype])
+    targets = None
+    if labels is not None:
+        lab_dev = labels.to(device()).contiguous().reshape(B) if lab_host is None else torch.from_numpy(lab_host).to(device())
+        targets = empty((B, K), torch.float32)
+    _lib.call("mv_preprocess_u8_mix_fwd", t.data_ptr(), t.numel(), y.data_ptr(), rec.ctypes.data, rec_dev.data_ptr(), mix.ctypes.data,
+              mix_dev.data_ptr(), a.data_ptr(), b.data_ptr(), None if lab_host is None else lab_host.ctypes.data,
+              None if lab_dev is None else lab_dev.data_ptr(), None if targets is None else targets.data_ptr(), K, float(on), float(off),
+              B, hout, wout, int(chw), DT[dtype], int(layout == "nhwc"), stream_ptr())
+    if batched:
+        return y, None if targets is None else DevArray(targets)
+    return y[0], None if targets is None else DevArray(targets[0])
+
+
+def imagenet_train_mixed(images_u8, labels, key, num_classes, size=224, scale=(0.08, 1.0), ratio=(3.0 / 4.0, 4.0 / 3.0), flip_p=0.5,
+                         mixup_alpha=0.2, cutmix_alpha=1.0, switch_p=0.5, erase_p=0.0, erase_scale=(0.02, 0.33),
+                         erase_ratio=(0.3, 3.3), label_smoothing=0.0, mean=IMAGENET_MEAN, std=IMAGENET_STD, dtype="fp32",
+                         channels_last=None):
+    """torchvision's full classification training recipe on the device, one launch: `imagenet_train`'s RandomResizedCrop ->
+    RandomHorizontalFlip -> ToTensor -> Normalize, then RandomErasing(erase_p, value=0) per image, then one of RandomMixup(mixup_alpha)
+    / RandomCutmix(cutmix_alpha) on the batch, with label smoothing folded into the soft targets.  `key` is split in FOUR:
+    `random_resized_crop_boxes` draws from the first, `random_flips` from the second, `mixup_cutmix_draw` from the third,
+    `random_erasing_draw` from the fourth.  The first two are NOT the halves of `imagenet_train`'s two-way split: the same key gives
+    other boxes and flips here than there.  The same key gives the same bits.  Returns (x [B, 3, size, size] fp32 or bf16, targets
+    `DevArray` fp32 [B, num_classes]), ready for `optim.softmax_cross_entropy(out, targets).mean()`.  `images_u8`: a batch, as for
+    `crop_resize_normalize`; `labels`: int [B], host or a device int32 tensor."""
+    sizes, single = _sizes_of(images_u8, channels_last)
+    if single:
+        raise ValueError("preprocess: imagenet_train_mixed mixes the images of a batch; a single image has no partner to be mixed "
+                         "with (imagenet_train takes one)")
+    B = len(sizes)
+    k_box, k_flip, k_mix, k_erase = _random.split(key, 4)
+    boxes = random_resized_crop_boxes(k_box, sizes, scale, ratio)
+    flips = random_flips(k_flip, B, flip_p)
+    partner, lam, cut, lam_t = mixup_cutmix_draw(k_mix, B, size, mixup_alpha, cutmix_alpha, switch_p)
+    erase = random_erasing_draw(k_erase, B, size, erase_p, erase_scale, erase_ratio) if erase_p > 0.0 else None
+    return crop_resize_normalize_mix(images_u8, boxes, size, flips, labels, num_classes, partner, lam, cut, erase, lam_t,
+                                     label_smoothing, mean, std, dtype, "nchw", channels_last)
 
 
 # ---- segmentation training: resize the whole image, mirror, pad, take a window; image and label map -> mv_preprocess_u8_seg_fwd ----

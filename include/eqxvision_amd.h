@@ -78,7 +78,9 @@ int mv_flags_epoch(void);                        /* hash of this thread's curren
  * HIP context, graph replays and other streams included).  bit 0: a split-K block gave up waiting for its partner's partial sums
  * (dirty / shared scratch; the tile it wrote is incomplete).  bit 1: mv_softmax_xent_map_f32 met a label outside [0, C) on a counted
  * pixel (the pixel was left out; loss, gradient and sums of that call are not those of the labels given).  bit 2: mv_preprocess_u8_fwd / mv_preprocess_u8_ragged_fwd / mv_preprocess_u8_boxes_fwd was given a tap table (or a device record) that points outside the image or
- * outside what its geometry can need (the taps were clamped; the output of that call is not the resize asked for).  Writes the word to *status, clears it if `clear`; SYNCHRONISES the
+ * outside what its geometry can need (the taps were clamped; the output of that call is not the resize asked for); mv_preprocess_u8_mix_fwd
+ * sets it for a device record it had to clamp too.  bit 3: mv_preprocess_u8_mix_fwd met a device label outside [0, K) (it matched no class:
+ * that row of the targets is not the one asked for).  Writes the word to *status, clears it if `clear`; SYNCHRONISES the
  * device -- call it where the host synchronises anyway (after a forward, at the end of a test). */
 int mv_device_status(int clear, unsigned* status);
 /* name of the kernel variant the last call on this thread dispatched to (for tests/bench) */
@@ -625,6 +627,47 @@ int mv_preprocess_u8_boxes_fwd(const void* x, int64_t x_bytes, void* y, const mv
                                const mv_preprocess_box* rec_dev, const float* a, const float* b, int B, int Hout, int Wout,
                                int in_chw, int out_dtype, int out_nhwc, mv_stream_t stream);
 
+/* The rest of the classification recipe in the training launch (torchvision's reference RandomMixup / RandomCutmix on the batch,
+ * RandomErasing(value=0) per image, label smoothing; the random draws made by the caller).  x, rec_host / rec_dev, a, b, the
+ * layouts and the dtypes are those of mv_preprocess_u8_boxes_fwd; image i has a second record, mv_preprocess_mix.  Rectangles are in
+ * OUTPUT pixels, half-open, (y0, x0, y1, x1); y1 <= y0 or x1 <= x0 is empty and means none.
+ *   v_i(p): the fp32 value mv_preprocess_u8_boxes_fwd gives image i at output pixel p with box record i before the output is
+ *           rounded -- same generated filter, tap order, two passes and fma(acc, a[c], b[c]) -- or exactly 0.0f where p lies inside
+ *           image i's OWN erase rectangle (erasing follows Normalize and precedes the mix, so it shows wherever image i is read,
+ *           as itself or as somebody's partner).
+ *   With r = partner[i]:  p inside image i's cut rectangle and r != i: y = v_r(p);  otherwise r == i or lam == 1: y = v_i(p);
+ *           otherwise y = fadd(fmul(lam, v_i(p)), fmul(oml, v_r(p))): two rounded products, one rounded sum, no contraction.
+ *   A bf16 output is rounded once, at the store.
+ * A tile resamples only what it needs, decided per tile from the records: not the partner where lam == 1 and the tile lies outside
+ * the cut rectangle; not itself where the tile lies inside it; neither image where that image's erase rectangle holds the tile.
+ * Targets, by extra workgroups of the same launch: with s(y, k) = (k == y ? on : off),
+ *   targets[i][k] = fadd(fmul(lam_t, s(labels[i], k)), fmul(oml_t, s(labels[r], k))), fp32 [B, K]; the caller passes
+ *   on = fl32(1 - eps + eps / K), off = fl32(eps / K) for label smoothing eps.  labels_dev: int32 [B] in DEVICE memory;
+ *   labels_host: the same in HOST memory or NULL (labels that exist on the device only).  labels_dev == NULL and targets == NULL
+ *   together: no targets.  No atomics on data, nothing shared between workgroups: same bits every run.
+ * rec_host, mix_host and labels_host (HOST memory) are validated in full before anything is launched, each message naming the
+ * image.  MV_E_INVALID: what mv_preprocess_u8_boxes_fwd refuses in a box record; partner outside [0, B); a rectangle coordinate
+ * outside [0, Hout] / [0, Wout]; lam, oml, lam_t or oml_t not finite or outside [0, 1]; a host label outside [0, K); labels without
+ * targets or the reverse.  MV_E_UNSUPPORTED: more than MV_PREPROCESS_MAX_TAPS taps on an axis; x, y and targets overlapping.
+ * The one tile of the launch follows the LDS rule of the ragged entry, with TH x 3 x TW fp32 more when any image has a partner: a
+ * tile that needs both images runs the passes for the partner, keeps its results there, then runs them for itself.
+ * rec_dev / mix_dev / labels_dev (DEVICE memory) are what the kernel reads; it forms no address from them unchecked: box records as
+ * in the boxes entry; a partner outside [0, B), one whose image leaves x, or one in a launch whose host records had no partner is
+ * treated as none; rectangles are clamped to the output; each sets bit 2 of mv_device_status.  A device label outside [0, K)
+ * matches no class (off everywhere) and sets bit 3. */
+typedef struct mv_preprocess_mix {
+    int32_t partner;                 /* index of the image mixed in; == own index: none */
+    float lam, oml;                  /* weights of this image and of the partner in the pixel mix */
+    int32_t cy0, cx0, cy1, cx1;      /* cut rectangle: the partner's pixels replace this image's */
+    int32_t ey0, ex0, ey1, ex1;      /* erase rectangle of THIS image */
+    float lam_t, oml_t;              /* weights of the two labels in the targets */
+} mv_preprocess_mix;                 /* 52 bytes, no padding */
+int mv_preprocess_u8_mix_fwd(const void* x, int64_t x_bytes, void* y, const mv_preprocess_box* rec_host,
+                             const mv_preprocess_box* rec_dev, const mv_preprocess_mix* mix_host, const mv_preprocess_mix* mix_dev,
+                             const float* a, const float* b, const int32_t* labels_host, const int32_t* labels_dev, float* targets,
+                             int K, float on, float off, int B, int Hout, int Wout, int in_chw, int out_dtype, int out_nhwc,
+                             mv_stream_t stream);
+
 /* The segmentation training transform in one launch (torchvision's segmentation preset: RandomResize -> RandomHorizontalFlip ->
  * RandomCrop with pad-if-smaller -> ToTensor -> Normalize, the random draws made by the caller): image i of a packed buffer x and
  * its label map in a packed buffer m (one record each) are resized WHOLE to Hr x Wr, mirrored left-right if flip != 0, padded on
@@ -892,7 +935,7 @@ typedef struct mv_optim_tensor {
     int64_t n;
     int64_t first_block;
 } mv_optim_tensor;                               /* 56 bytes, no padding */
-enum { MV_OPT_SGD = 0, MV_OPT_ADAMW = 1, MV_OPT_APPLY = 2 };
+enum { MV_OPT_SGD = 0, MV_OPT_ADAMW = 1, MV_OPT_APPLY = 2, MV_OPT_EMA = 3 };
 /* Sum of squares of every grad of the set, and optax.clip_by_global_norm's factor.  Two launches: every workgroup writes the sum
  * of its chunk to partial[block] (total_blocks floats; per lane in element order, a fixed butterfly over the wave, the four waves
  * in order through LDS), then one workgroup adds the partials (thread t takes t, t + 256, ... in order, then the same tree) and
@@ -905,7 +948,10 @@ int mv_optim_sqnorm_f32(const mv_optim_tensor* recs, int n_tensors, int64_t tota
  *   MV_OPT_ADAMW (optax.adamw): m = b1 m + one_minus_b1 g, v = b2 v + one_minus_b2 g^2,
  *                out = -lr ((m / bias_corr1) / (sqrt(v / bias_corr2) + eps) + weight_decay param); param may be NULL when
  *                weight_decay == 0.  one_minus_b* and bias_corr* = 1 - b*^t come from the caller (rounded once from float64).
- *   MV_OPT_APPLY (eqx.apply_updates): out = param + grad. */
+ *   MV_OPT_APPLY (eqx.apply_updates): out = param + grad.
+ *   MV_OPT_EMA   (torchvision's ExponentialMovingAverage): out = fadd(fmul(b1, out), fmul(one_minus_b1, grad)) -- out is the
+ *                average, read and written; grad the parameter; b1 the decay -- or, with nesterov != 0, out = grad (the first
+ *                update after init copies).  Two rounded products and one rounded sum, no contraction; scale is not applied. */
 int mv_optim_step_f32(const mv_optim_tensor* recs, int n_tensors, int64_t total_blocks, int kind, int nesterov, float lr, float b1,
                       float b2, float one_minus_b1, float one_minus_b2, float eps, float weight_decay, float bias_corr1,
                       float bias_corr2, const float* scale, mv_stream_t stream);
