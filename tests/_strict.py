@@ -97,34 +97,33 @@ def _conv64(x_nhwc, w_krsc, stride, pad, dil, groups):
     return y.permute(0, 2, 3, 1).contiguous().numpy()
 
 
-def epilogue64(acc, amag, scale, shift, res, act):
-    """(ref, mag) of act(acc * scale + shift + res) with the channel last; `amag` is the contraction of the absolute values."""
-    ref, mag = acc, amag
+def epilogue64(acc, amag, scale, shift, res, act, pre=False):
+    """(ref, mag) of act(acc * scale + shift + res) with the channel last; `amag` is the contraction of the absolute values and `mag`
+    the magnitude of the PRE-activation.  `act` is an MV_ACT_* code or name; pre=True adds the float64 pre-activation, which the
+    bound of an activation beyond none / ReLU is computed from (act_bound)."""
+    p, mag = acc, amag
     if scale is not None:
-        ref = ref * np.asarray(scale, F64)
+        p = p * np.asarray(scale, F64)
         mag = mag * np.abs(np.asarray(scale, F64))
     if shift is not None:
-        ref = ref + np.asarray(shift, F64)
+        p = p + np.asarray(shift, F64)
         mag = mag + np.abs(np.asarray(shift, F64))
     if res is not None:
-        ref = ref + np.asarray(res, F64)
+        p = p + np.asarray(res, F64)
         mag = mag + np.abs(np.asarray(res, F64))
-    if act == 1:
-        ref = np.maximum(ref, 0.0)
-    elif act != 0:
-        raise ValueError("strict instruments cover activation none / ReLU only")
-    return ref, mag
+    ref = act64(p, act_name(act))
+    return (ref, mag, p) if pre else (ref, mag)
 
 
-def conv_ref(x_nhwc, w_krsc, scale, shift, res, act, stride=1, pad=0, dil=1, groups=1):
+def conv_ref(x_nhwc, w_krsc, scale, shift, res, act, stride=1, pad=0, dil=1, groups=1, pre=False):
     acc = _conv64(x_nhwc, w_krsc, stride, pad, dil, groups)
     amag = _conv64(np.abs(x_nhwc), np.abs(w_krsc), stride, pad, dil, groups)
-    return epilogue64(acc, amag, scale, shift, res, act)
+    return epilogue64(acc, amag, scale, shift, res, act, pre)
 
 
-def gemm_ref(x, w, scale, shift, res, act):
+def gemm_ref(x, w, scale, shift, res, act, pre=False):
     x, w = np.asarray(x, F64), np.asarray(w, F64)
-    return epilogue64(x @ w.T, np.abs(x) @ np.abs(w).T, scale, shift, res, act)
+    return epilogue64(x @ w.T, np.abs(x) @ np.abs(w).T, scale, shift, res, act, pre)
 
 
 # ------------------------------------------------------------------------------------------------ instrument 1
@@ -149,12 +148,16 @@ def prove_exact(name, ref, mag, weights, stored=(), hidden=(), out="bf16", min_n
         if out == "bf16" or what not in ("ref", "mag"):
             lim = BF16_INT_MAX if what in ("ref", "mag") else hidden_max
             assert top <= lim, f"{name}: {what} reaches {top} > {lim} (not exact in bf16)"
+    _prove_coverage(name, weights)
+    zeros = float((np.asarray(ref) == 0).mean())
+    assert zeros < 1.0 - min_nonzero, f"{name}: {100 * zeros:.1f} % of the reference outputs are zero (ReLU blanks the test)"
+
+
+def _prove_coverage(name, weights):
     for i, w in enumerate(weights):
         w2 = np.asarray(w).reshape(w.shape[0], -1) != 0
         assert w2.any(axis=0).all(), f"{name}: weights[{i}] leaves {int((~w2.any(axis=0)).sum())} reduction indices unused"
         assert w2.any(axis=1).all(), f"{name}: weights[{i}] has {int((~w2.any(axis=1)).sum())} all-zero output channels"
-    zeros = float((np.asarray(ref) == 0).mean())
-    assert zeros < 1.0 - min_nonzero, f"{name}: {100 * zeros:.1f} % of the reference outputs are zero (ReLU blanks the test)"
 
 
 def check_exact(got, ref):
@@ -241,13 +244,34 @@ def bf16_truncate(a):
     return (a.view(np.uint32) & np.uint32(0xffff0000)).view(np.float32)
 
 
-def emulate(x, w, scale, shift, res, act, store="rne", drop_shift_channel=None, relu_skip_above=None, drop_chunk=None, chunk=16):
-    """y = store_bf16(act(fp32 accumulation of x . w^T in `chunk`-wide steps, * scale + shift + res)) -- what a conv / GEMM kernel
-    of this library promises.  The keyword arguments switch on ONE defect each (the mutants of test_strict_host.py):
-      store="trunc"            the bf16 store truncates
+ACT_DEFECTS = ("skip_tail_vec", "act_before_res", "act_before_shift", "trunc", "erf_gelu", "pair_repeat", "no_clamp6")
+
+
+def emulate(x, w, scale, shift, res, act, store="rne", drop_shift_channel=None, relu_skip_above=None, drop_chunk=None, chunk=16,
+            out="bf16", skip_tail_vec=False, act_before_res=False, act_before_shift=False, erf_gelu=False, pair_repeat=False,
+            no_clamp6=False):
+    """y = store_out(act(fp32 accumulation of x . w^T in `chunk`-wide steps, * scale + shift + res)) -- what a conv / GEMM kernel
+    of this library promises; `act` is an MV_ACT_* code or name (act32).  The keyword arguments switch on ONE defect each (the
+    mutants of test_strict_host.py and test_strict_act_host.py):
+      store="trunc"            the bf16 store truncates (after the activation)
       drop_shift_channel=k     channel k's BatchNorm shift is lost
       relu_skip_above=t        ReLU is skipped for pre-activations in (t, 0)
-      drop_chunk=(c, n0, n1)   reduction chunk c is not accumulated for the output channels n0 .. n1 - 1"""
+      drop_chunk=(c, n0, n1)   reduction chunk c is not accumulated for the output channels n0 .. n1 - 1
+      skip_tail_vec            the activation is skipped on the last 8-wide vector of the output channels (a ragged tile's tail)
+      act_before_res           the activation is applied before the residual add
+      act_before_shift         the activation is applied before the shift (and the residual)
+      erf_gelu                 0.5 v (1 + erf(v / sqrt 2)) instead of the tanh form
+      pair_repeat              the second value of every packed pair repeats the first (gelu_tanh_pack2's lanes)
+      no_clamp6                hard-swish without the clamp at 6: v max(v + 3, 0) / 6"""
+    name = act_name(act)
+
+    def activate(v):
+        if erf_gelu and name == "gelu_tanh":
+            t = torch.from_numpy(np.ascontiguousarray(v, dtype=np.float32))
+            return (np.float32(0.5) * t * (1 + torch.erf(t * np.float32(0.7071067811865476)))).numpy()
+        if no_clamp6 and name == "hard_swish":
+            return v * np.maximum(v + np.float32(3), np.float32(0)) * (np.float32(1) / np.float32(6))
+        return act32(v, name, relu_skip_above)
     x32, w32 = np.asarray(x, np.float32), np.asarray(w, np.float32)
     acc = np.zeros((x32.shape[0], w32.shape[0]), np.float32)
     for c, k0 in enumerate(range(0, x32.shape[1], chunk)):
@@ -258,12 +282,22 @@ def emulate(x, w, scale, shift, res, act, store="rne", drop_shift_channel=None, 
     sh = np.array(shift, np.float32)
     if drop_shift_channel is not None:
         sh[drop_shift_channel] = 0
-    y = acc * np.asarray(scale, np.float32) + sh
-    if res is not None:
-        y = y + np.asarray(res, np.float32)
-    if act == 1:
-        keep = (y > relu_skip_above) if relu_skip_above is not None else np.zeros(y.shape, bool)
-        y = np.where((y > 0) | keep, y, np.float32(0))
+    v = acc if scale is None else acc * np.asarray(scale, np.float32)
+    r = np.float32(0) if res is None else np.asarray(res, np.float32)
+    if act_before_shift:
+        y = (activate(v) + sh) + r
+    elif act_before_res:
+        y = activate(v + sh) + r
+    else:
+        y = activate((v + sh) + r)
+    if skip_tail_vec:
+        y = np.array(y, np.float32)
+        y[:, -8:] = ((v + sh) + r)[:, -8:]
+    if pair_repeat:
+        y = np.array(y, np.float32)
+        y[:, 1::2] = y[:, 0:y.shape[1] - y.shape[1] % 2:2]
+    if out != "bf16":
+        return np.asarray(y, np.float32)
     return bf16_truncate(y) if store == "trunc" else bf(y)
 
 
@@ -272,6 +306,14 @@ def emulate(x, w, scale, shift, res, act, store="rne", drop_shift_channel=None, 
 F32 = np.float32
 SENTINEL = -7.0               # tests/_slices.py: what a destination holds before the launch
 ACT_CODES = {"none": 0, "relu": 1, "gelu_tanh": 2, "hard_swish": 3, "hard_sigmoid": 4, "sigmoid": 5, "silu": 6}
+ACT_NAMES = {v: k for k, v in ACT_CODES.items()}
+
+
+def act_name(act):
+    """An MV_ACT_* code, a name or None -> the name."""
+    return "none" if act is None else (ACT_NAMES[int(act)] if not isinstance(act, str) else act)
+
+
 _LOG2E = F32(1.4426950408889634)
 _GELU_K0 = F32(F32(-2.0) * F32(0.7978845608028654)) * _LOG2E          # common.h: folded in float by the compiler
 _GELU_K1 = _GELU_K0 * F32(0.044715)
@@ -320,13 +362,14 @@ def act64(x, act):
         return np.clip(x + 3.0, 0.0, 6.0) / 6.0
     if act == "hard_swish":
         return x * np.clip(x + 3.0, 0.0, 6.0) / 6.0
-    if act == "sigmoid":
-        return 1.0 / (1.0 + np.exp(-x))
-    if act == "silu":
-        return x / (1.0 + np.exp(-x))
-    if act == "gelu_tanh":
-        u = np.sqrt(2.0 / np.pi) * (x + 0.044715 * x ** 3)
-        return x / (1.0 + np.exp(-2.0 * u))
+    with np.errstate(over="ignore"):                     # exp -> inf gives the limit 0 / -0
+        if act == "sigmoid":
+            return 1.0 / (1.0 + np.exp(-x))
+        if act == "silu":
+            return x / (1.0 + np.exp(-x))
+        if act == "gelu_tanh":
+            u = np.sqrt(2.0 / np.pi) * (x + 0.044715 * x ** 3)
+            return x / (1.0 + np.exp(-2.0 * u))
     raise ValueError(act)
 
 
@@ -1070,3 +1113,251 @@ def swin_bwd64(qkv, bias, dout, heads, ws, shift):
         y = torch.roll(y, (sh[0], sh[1]), (1, 2))
     y.backward(_t(dout))
     return t.grad.numpy(), attn.grad.numpy()
+
+
+# ================================================================================================ fused activations
+# Instruments for the activations fused into the conv / GEMM epilogues and into se_scale (tests/test_strict_act_gpu.py, proofs in
+# tests/test_strict_act_host.py).
+#
+# Exact instrument.  On a lattice of pre-activations every activation has an exactly representable value:
+#     gelu_tanh                multiples of 16    ReLU              |t| = |x (k0 + k1 x^2)| >= 458 at |x| = 16
+#     sigmoid / silu           multiples of 128   step / ReLU       |t| = log2(e) |x| >= 184
+#     hard_sigmoid / _swish    multiples of 3     step / ReLU       fl(1/6) = (1/6)(1 + 2^-25): (6 v) fl(1/6) rounds back to v
+# (step: 0 below 0, 1/2 at 0, 1 above).  Supposed of the hardware and not in the source: v_exp_f32(+-0) = 1, v_rcp_f32(1) = 1,
+# v_rcp_f32(2) = 0.5, exp2 of an argument below -128 is below 2^-25 (1 + e rounds to 1), exp2 of an argument above 128 is +inf
+# (rcp gives 0, and v * 0 = -0 for v < 0, which equals 0).  test_ln_mlp_exact rests on the same suppositions.  A lattice case that
+# fails ONLY at pre-activation 0 for sigmoid / hard_sigmoid is a finding about the first three.
+LATTICE_STEP = {"none": 1, "relu": 1, "gelu_tanh": 16, "hard_swish": 3, "hard_sigmoid": 3, "sigmoid": 128, "silu": 128}
+STEP_ACTS = ("hard_sigmoid", "sigmoid")
+TINY = 2.0 ** -126            # the smallest normal fp32 / bf16 value: what lies below it has no relative precision
+
+
+def lattice_value(p, act):
+    """What the activation is ON its lattice (float64; the caller proves that p is on it)."""
+    p, act = np.asarray(p, F64), act_name(act)
+    if act == "none":
+        return p
+    if act in STEP_ACTS:
+        return np.where(p > 0, 1.0, np.where(p < 0, 0.0, 0.5))
+    return np.maximum(p, 0.0)
+
+
+def prove_lattice(name, pre, mag, act, weights, stored=(), out="bf16", signs=True, out_mag=None):
+    """prove_exact's sibling for an activation beyond ReLU, asserted on the CPU before a launch.  `pre` is the float64
+    pre-activation, `mag` its magnitude (the contraction on absolute values); returns the lattice value, the reference.
+      (a) every pre-activation and every `mag` is a multiple of the activation's lattice step;
+      (b) mag < 2^24 (fp32 accumulation exact in any order), 6 mag < 2^24 for the hard pair (v * h is exact);
+      (c) a bf16 output holds the value: out_mag (default: mag) <= 256 at step 3 (the values 3 k are not all bf16 values beyond
+          that), <= 256 steps at steps 1, 16 and 128; not asked of the step functions, whose values are 0, 1/2, 1;
+      (d) every operand in `stored` is a bf16 value;
+      (e) act64 rounded to the output type IS the lattice value (act64 itself is within 1e-50 of it, not on it);
+      (f) prove_exact's coverage conditions on the weights;
+      (g) signs: >= 5 % of the pre-activations negative, >= 5 % positive, at least one exactly 0."""
+    act = act_name(act)
+    step = LATTICE_STEP[act]
+    pre, mag = np.asarray(pre, F64), np.asarray(mag, F64)
+    for what, a in (("pre-activation", pre), ("mag", mag)):
+        assert np.array_equal(np.rint(a / step) * step, a), f"{name}: {what} leaves the lattice of step {step}"
+    top = float(mag.max())
+    assert top < ACC_INT_MAX, f"{name}: mag reaches {top} >= 2^24"
+    if step == 3:
+        assert 6 * top < ACC_INT_MAX, f"{name}: 6 mag reaches {6 * top} >= 2^24"
+    ref = lattice_value(pre, act)
+    if out == "bf16" and act not in STEP_ACTS:
+        otop = top if out_mag is None else float(np.abs(out_mag).max())
+        lim = BF16_INT_MAX if step == 3 else BF16_INT_MAX * step
+        assert otop <= lim, f"{name}: the output reaches {otop} > {lim} (not exact in bf16 at step {step})"
+    for i, s in enumerate(stored):
+        assert np.array_equal(bf(s), np.asarray(s, np.float32)), f"{name}: stored[{i}] is not a bf16 value"
+    q = bf if out == "bf16" else (lambda a: np.asarray(a, np.float32))
+    assert np.array_equal(q(act64(pre, act)).astype(F64), ref), f"{name}: act64 does not round to the lattice value"
+    _prove_coverage(name, weights)
+    if signs:
+        neg, pos, zero = float((pre < 0).mean()), float((pre > 0).mean()), int((pre == 0).sum())
+        assert neg >= 0.05 and pos >= 0.05 and zero >= 1, f"{name}: {100 * neg:.1f} % negative, {100 * pos:.1f} % positive, {zero} zeros"
+    return ref
+
+
+_LIPSCHITZ = {}
+
+
+def act_lipschitz(act):
+    """L = sup |act'| in float64, computed and not quoted: the analytic derivative (act_grad64) on a grid of step h = 2^-12 over
+    [-12, 12] plus h / 2 max |act''| (from the grid's differences) for what lies between two grid points.  The hard pair is piecewise
+    polynomial with corners at -3 and 3: each piece is taken with its own derivative on its CLOSED interval (1.5 at 3 for
+    hard_swish comes from the middle piece).  Beyond +-12 the derivatives of sigmoid and silu tend monotonically to 0 / 0 and 1.
+    gelu_tanh is tests/_strict_lngemm.py's gelu_lipschitz.  (1.5, 1/6, 0.25, 1.0998, 1.1290 for hard_swish, hard_sigmoid, sigmoid,
+    silu, gelu_tanh: asserted to 1e-3 in tests/test_strict_act_host.py, as a check of this function only.)"""
+    act = act_name(act)
+    if act in _LIPSCHITZ:
+        return _LIPSCHITZ[act]
+    if act in ("none", "relu"):
+        L = 1.0
+    elif act == "gelu_tanh":
+        from tests import _strict_lngemm
+        L = _strict_lngemm.gelu_lipschitz()
+    else:
+        h = 2.0 ** -12
+        if act == "hard_sigmoid":
+            pieces = [(-3.0, 3.0, lambda x: np.full(x.shape, 1.0 / 6.0))]                 # 0 outside
+        elif act == "hard_swish":
+            pieces = [(-3.0, 3.0, lambda x: (2.0 * x + 3.0) / 6.0), (3.0, 12.0, lambda x: np.ones(x.shape))]
+        else:
+            pieces = [(-12.0, 12.0, lambda x: act_grad64(x, act))]
+        L = 0.0
+        for a, b, g in pieces:
+            g1 = g(np.arange(a, b + 0.5 * h, h))
+            L = max(L, float(np.abs(g1).max() + 0.5 * h * np.abs(np.diff(g1)).max() / h))
+        if act in ("sigmoid", "silu"):
+            lo, hi = act_grad64(np.array([-12.0, 12.0]), act)
+            assert abs(lo) < 1e-3 and abs(hi - (act == "silu")) < 1e-3
+    _LIPSCHITZ[act] = L
+    return L
+
+
+def through_act(p, e_p, act, out):
+    """(ref, bound) of out(act(p)) for a float64 pre-activation p known to e_p (tests/_strict_lngemm.py's GELU line, for every
+    activation):
+        pre   = L e_p + n_ops(|p| + e_p) 2^-23 (|act(p)| + L e_p) + 2^-126
+        bound = pre + half_ulp_out(|act(p)| + pre)                                   (out=None: pre alone, nothing is stored)
+    L = act_lipschitz, n_ops = act_n_ops.  none / ReLU: L = 1 and n_ops = 0, so this is elem_bound.  The 2^-126 stands for the
+    exponent range of fp32 (added for act >= 2 only): x rcp(1 + exp2(t)) is 0 once t > 128, where the function itself is below
+    the smallest normal number."""
+    act = act_name(act)
+    p, e_p = np.asarray(p, F64), np.asarray(e_p, F64)
+    L = act_lipschitz(act)
+    ref = act64(p, act)
+    pre = L * e_p + act_n_ops(np.abs(p) + e_p, act) * 2.0 ** -23 * (np.abs(ref) + L * e_p)
+    if act not in ("none", "relu"):
+        pre = pre + TINY
+    return ref, (pre if out is None else pre + half_ulp_out(np.abs(ref) + pre, out))
+
+
+def act_bound(p, mag, kred, act, out):
+    """(ref, bound) of a conv / GEMM epilogue with activation `act`: e_p = (K_red + 4) 2^-23 mag as in elem_bound, then through_act."""
+    return through_act(p, (kred + 4) * 2.0 ** -23 * np.asarray(mag, F64), act, out)
+
+
+def prove_reach(name, p, act):
+    """Gaussian pre-activations must reach the pieces of the function: >= 10 % in each of (-inf, -3), (-3, 3), (3, inf) for the hard
+    pair; >= 10 % on each side of 0 and some |p| > 6 for gelu_tanh / sigmoid / silu."""
+    act, p = act_name(act), np.asarray(p, F64)
+    if act in ("hard_sigmoid", "hard_swish"):
+        fr = [float((p < -3).mean()), float(((p > -3) & (p < 3)).mean()), float((p > 3).mean())]
+        assert min(fr) >= 0.10, f"{name}: the pieces of {act} hold {fr} of the pre-activations"
+    elif act in ("gelu_tanh", "sigmoid", "silu"):
+        fr = [float((p < 0).mean()), float((p > 0).mean())]
+        assert min(fr) >= 0.10 and bool((np.abs(p) > 6).any()), f"{name}: {fr} on the two sides of 0, max |p| {np.abs(p).max():.2f}"
+
+
+# ------------------------------------------------------------------------------------------------ mv_se_scale_fwd (squeeze.hip)
+SE_SHAPES = [(16, 4, 1), (72, 19, 5), (1032, 6, 67), (96, 33, 4 * 85 + 3)]         # (C, S, HW): what each reaches is in the GPU module
+SE_ACTS = [("silu", "sigmoid"), ("relu", "hard_sigmoid"), ("none", "none")]
+SE_N = 3
+
+
+def se_groups(C):
+    """se_scale_kernel's pooling passes: (first channel, end channel, cpb, pl) per group of up to 128 channel vectors."""
+    c8 = C // 8
+    return [(cv0 * 8, (cv0 + min(c8 - cv0, 128)) * 8, min(c8 - cv0, 128), 1024 // min(c8 - cv0, 128)) for cv0 in range(0, c8, 128)]
+
+
+def se_data(mode, C, Sq, HW, act1, act2, bias, seed=80):
+    """(x (3, HW, C), w1 (Sq, C), b1, w2 (C, Sq), b2); b1 = b2 = None without `bias`.
+    gauss: bf16 Gaussians, every channel with an offset of its own so that the mean does not vanish.
+    int:   x = a[n][c] + d[n][p][c], a in [-2, 2], d in [-2, 2] summing to 0 over the pixels (pairs +v, -v in a random order): the
+           lane sums are small integers, the total is HW a, and (HW a) fl(1 / HW) == a is asserted in float32; +-1 rows (pm1_rows)
+           times the lattice step of act1 for w1, +-1 (times the step of act2 unless act1's step is a multiple of it) for w2,
+           biases integers times the step."""
+    rng = rng_of(seed + C + 7 * HW + 1000 * (mode == "int") + ACT_CODES[act1])
+    if mode == "gauss":
+        x = bf(rng.standard_normal((SE_N, HW, C)) + 2.0 * rng.standard_normal((SE_N, 1, C)))
+        w1, w2 = bf(rng.standard_normal((Sq, C)) / np.sqrt(C)), bf(rng.standard_normal((C, Sq)) / np.sqrt(Sq))
+        b1, b2 = (0.5 * rng.standard_normal(Sq)).astype(F32), (2.0 * rng.standard_normal(C)).astype(F32)
+        return x, w1, (b1 if bias else None), w2, (b2 if bias else None)
+    s1, s2 = LATTICE_STEP[act1], LATTICE_STEP[act2]
+    a = int_tensor(rng, (SE_N, 1, C), 2)
+    v = int_tensor(rng, (SE_N, HW // 2, C), 2)
+    d = rng.permuted(np.concatenate([v, -v, np.zeros((SE_N, HW % 2, C), F32)], axis=1), axis=1)
+    x = (a + d).astype(F32)
+    assert np.array_equal((F32(HW) * a[:, 0]) * (F32(1) / F32(HW)), a[:, 0]), "se: (HW a) fl(1 / HW) != a"
+    w1 = F32(s1) * pm1_rows(rng, Sq, C, max(4, -(-C // Sq)))
+    w2 = F32(1 if s1 % s2 == 0 else s2) * pm1_rows(rng, C, Sq, min(Sq, 2))
+    b1, b2 = F32(s1) * int_tensor(rng, (Sq,), 4), F32(s2) * int_tensor(rng, (C,), 4)
+    return x, w1, (b1 if bias else None), w2, (b2 if bias else None)
+
+
+def se_ref(x, w1, b1, w2, b2, act1, act2):
+    """The header's definition in float64 on the operands the kernel gets, with every term of the bound (counted from squeeze.hip):
+      pooling   a lane adds ceil(HW / pl) pixels, min(pl, HW) lane sums are added in order (the other lanes hold exact zeros), the
+                constant 1 / HW and the multiply: (ceil(HW / pl) + min(pl, HW) + 2) 2^-23 mean|x|
+      fc1       ceil(C / 64) fma per lane, 6 shuffle adds, the bias add: (ceil(C / 64) + 7) 2^-23 mag1, plus |w1| . e_pool
+      act1      through_act without a store (h stays in LDS as fp32)
+      fc2       Sq fma starting from b2: Sq 2^-23 mag2, plus |w2| . e_h
+      act2      through_act with the bf16 store.
+    Returns {"q": pre-activation 1, "mq": its mag, "h", "r": pre-activation 2, "mr", "ref", "bound"}."""
+    x, w1, w2 = np.asarray(x, F64), np.asarray(w1, F64), np.asarray(w2, F64)
+    N_, HW, C = x.shape
+    Sq = w1.shape[0]
+    u = 2.0 ** -23
+    p, pm = x.mean(1), np.abs(x).mean(1)
+    n_pool = np.empty(C)
+    for c0, c1, _, pl in se_groups(C):
+        n_pool[c0:c1] = -(-HW // pl) + min(pl, HW) + 2
+    e_pool = n_pool[None, :] * u * pm
+    bb1 = 0.0 if b1 is None else np.asarray(b1, F64)
+    bb2 = 0.0 if b2 is None else np.asarray(b2, F64)
+    q = p @ w1.T + bb1
+    mq = (np.abs(p) + e_pool) @ np.abs(w1).T + np.abs(bb1)
+    e_q = e_pool @ np.abs(w1).T + (-(-C // 64) + 7) * u * mq
+    h, e_h = through_act(q, e_q, act1, None)
+    r = h @ w2.T + bb2
+    mr = (np.abs(h) + e_h) @ np.abs(w2).T + np.abs(bb2)
+    e_r = e_h @ np.abs(w2).T + Sq * u * mr
+    ref, bound = through_act(r, e_r, act2, "bf16")
+    return {"q": q, "mq": mq, "h": h, "r": r, "mr": mr, "ref": ref, "bound": bound}
+
+
+def se_prove_exact(name, x, w1, b1, w2, b2, act1, act2):
+    """Both pre-activations on their lattices (prove_lattice; h lives in LDS as fp32, the scale is stored as bf16 -- the limit of
+    the bf16 store is asked of the reference values, fc2's partial sums are fp32).  Returns the exact reference."""
+    pm = np.asarray(x, F64).mean(1)
+    assert np.array_equal(pm, np.rint(pm)), f"{name}: the pooled means are not integers"
+    q = pm @ np.asarray(w1, F64).T + (0.0 if b1 is None else np.asarray(b1, F64))
+    mq = np.abs(pm) @ np.abs(np.asarray(w1, F64)).T + (0.0 if b1 is None else np.abs(np.asarray(b1, F64)))
+    # 3 Sq hidden pre-activations are too few for the 5 % / exact-zero rule: both signs must occur; the rule is asked of fc2's
+    h = prove_lattice(name + "/fc1", q, mq, act1, [w1], stored=[x, w1, w2], out="fp32", signs=False)
+    assert bool((q < 0).any()) and bool((q > 0).any()), f"{name}: fc1's pre-activations have one sign"
+    r = h @ np.asarray(w2, F64).T + (0.0 if b2 is None else np.asarray(b2, F64))
+    mr = np.abs(h) @ np.abs(np.asarray(w2, F64)).T + (0.0 if b2 is None else np.abs(np.asarray(b2, F64)))
+    ref = prove_lattice(name + "/fc2", r, mr, act2, [np.asarray(w2)], out="bf16", signs=act2 != "none", out_mag=lattice_value(r, act2))
+    return ref
+
+
+def emu_se_scale(x, w1, b1, w2, b2, act1, act2, store_mode="rne", lost_lane=False, w2_untransposed=False):
+    """se_scale_kernel in float32, in its order: per channel group the pl pixel lanes (emu_global_avgpool), fc1 with lane c mod 64
+    accumulating by fma and the xor-shuffle tree, + b1, act1; fc2 by fma from b2 over j, act2, the bf16 store.  Defects:
+      lost_lane           the last pixel lane's sum is not added (the reduction stops at pl - 1)
+      w2_untransposed     w2 is read as handed over by a caller that did not transpose it ([C][Sq] memory indexed as [Sq][C])"""
+    x, w1, w2 = np.asarray(x, F32), np.asarray(w1, F32), np.asarray(w2, F32)
+    N_, HW, C = x.shape
+    Sq = w1.shape[0]
+    pv = np.empty((N_, C), F32)
+    for c0, c1, _, pl in se_groups(C):
+        pv[:, c0:c1] = emu_global_avgpool(x[:, :, c0:c1], "fp32", pl=pl, lost_lane=pl - 1 if lost_lane else None)
+    steps = -(-C // 64)
+    wp, pp = np.zeros((Sq, steps * 64), F32), np.zeros((N_, steps * 64), F32)
+    wp[:, :C], pp[:, :C] = w1, pv
+    t = np.zeros((N_, Sq, 64), F32)
+    for i in range(steps):
+        sl = slice(64 * i, 64 * i + 64)
+        t = (wp[None, :, sl].astype(F64) * pp[:, None, sl].astype(F64) + t.astype(F64)).astype(F32)
+    for o in (32, 16, 8, 4, 2, 1):
+        t = t + t[..., np.arange(64) ^ o]
+    q = t[..., 0] + (F32(0) if b1 is None else np.asarray(b1, F32))
+    h = act32(q, act1)
+    w2t = np.ascontiguousarray(w2).reshape(Sq, C) if w2_untransposed else np.ascontiguousarray(w2.T)
+    t = np.broadcast_to(np.zeros(C, F32) if b2 is None else np.asarray(b2, F32), (N_, C)).astype(F32)
+    for j in range(Sq):
+        t = (w2t[j][None, :].astype(F64) * h[:, j:j + 1].astype(F64) + t.astype(F64)).astype(F32)
+    return store(act32(t, act2), "bf16", store_mode)

@@ -1,12 +1,27 @@
-"""What the strict GPU modules (test_strict_gpu.py, test_strict_mem_gpu.py) share: the module fixture that loads the library and reads the
-device status word before and after, device / host conversions, the sentinel-filled output and the flag scope."""
+"""What the strict GPU modules (test_strict_gpu.py, test_strict_act_gpu.py, test_strict_mem_gpu.py) share: the module fixture that
+loads the library and reads the device status word before and after, device / host conversions, the sentinel-filled output, the
+flag scope, and the operand generators, verdict and runners of the conv / GEMM entries.
+
+The runners take any fused activation (MV_ACT_* code).  none / ReLU: the operands, references and verdicts of test_strict_gpu.py,
+unchanged.  From gelu_tanh on (tests/_strict.py, "fused activations"):
+  mode "int"    BatchNorm scale, shift and residual (or, where the entry has no scale, the weights) are multiplied by the
+                activation's lattice step, so that every pre-activation is on the lattice and the output must EQUAL the lattice
+                value (S.prove_lattice asserts the preconditions first).  The hard pair (step 3) takes x in [-1, 1], shift and
+                residual in [-4, 4]: 3 mag <= 256 must hold for a bf16 output.
+  mode "gauss"  the shift is drawn with standard deviation 4, so that the pre-activations reach every piece of the function
+                (S.prove_reach), and every element must lie within S.act_bound; the rounding bias under the usual conditions.
+"""
+import functools
+
 import numpy as np
 import pytest
 import torch
 
 from eqxvision_amd import _lib
+from tests import _strict as S
 
 DT = {"bf16": _lib.BF16, "fp32": _lib.F32}
+BF, F32 = _lib.BF16, _lib.F32
 
 
 @pytest.fixture(scope="module", autouse=True)
@@ -39,6 +54,20 @@ def _out(shape, dtype="bf16", fill=-7.0):
     return torch.full(shape, fill, dtype=torch.bfloat16 if dtype == "bf16" else torch.float32, device="cuda")
 
 
+GUARD = 4096                  # elements of sentinel behind a guarded destination (tests/_slices.py)
+
+
+def _out_guarded(shape, dtype="bf16"):
+    """(the flat sentinel-filled buffer with GUARD elements behind the destination, the destination as a view of `shape`)."""
+    n = int(np.prod(shape))
+    buf = _out((n + GUARD,), dtype)
+    return buf, buf[:n].view(shape)
+
+
+def _guard_ok(buf):
+    return bool((buf[-GUARD:] == S.SENTINEL).all().item())
+
+
 class _Flags:
     def __init__(self, flags):
         self.flags = [(f.split("=")[0], int(f.split("=")[1]) if "=" in f else 1) for f in flags]
@@ -50,3 +79,232 @@ class _Flags:
     def __exit__(self, *a):
         for k, _ in self.flags:
             _lib.set_flag(k, 0)
+
+
+# ------------------------------------------------------------------------------------------------ operands
+def _x(mode, rng, shape, lim=2, q=S.bf):
+    return S.int_tensor(rng, shape, lim) if mode == "int" else q(rng.standard_normal(shape))
+
+
+def _w(mode, rng, rows, kred, nnz, q=S.bf):
+    return S.pm1_rows(rng, rows, kred, nnz) if mode == "int" else q(rng.standard_normal((rows, kred)) / np.sqrt(kred))
+
+
+def _sc(mode, rng, n, mags=(1, 2)):
+    return S.int_scale(rng, n, mags) if mode == "int" else S.gauss_scale(rng, n)
+
+
+def _sh(mode, rng, n, lim=8):
+    return S.int_tensor(rng, (n,), lim) if mode == "int" else (0.1 * rng.standard_normal(n)).astype(np.float32)
+
+
+def _f32(a):
+    return np.asarray(a, np.float32)
+
+
+def _step(act):
+    """The lattice step of a fused activation (1 for none / ReLU: their operands stay as they were)."""
+    return S.LATTICE_STEP[S.act_name(act)] if act > 1 else 1
+
+
+def _xlim(mode, act, lim):
+    return min(lim, 1) if mode == "int" and _step(act) == 3 else lim
+
+
+def _res_lim(act, lim=16):
+    return 4 if _step(act) == 3 else lim
+
+
+def _sc_act(mode, rng, n, act):
+    sc = _sc(mode, rng, n)
+    return sc * np.float32(_step(act)) if mode == "int" else sc
+
+
+def _sh_act(mode, rng, n, act):
+    """The shift: none / ReLU as ever; beyond, integers times the lattice step (mode int) or a deviation of 4 (mode gauss)."""
+    if act <= 1:
+        return _sh(mode, rng, n)
+    if mode == "int":
+        return _sh(mode, rng, n, 4 if _step(act) == 3 else 8) * np.float32(_step(act))
+    return (4.0 * rng.standard_normal(n)).astype(np.float32)
+
+
+def _judge_ref(name, mode, act, p, ref, mag, kred, weights, stored, out):
+    """What a runner does with the float64 pre-activation: (ref, bound or None).  none / ReLU: prove_exact in mode int, elem_bound
+    later in the verdict; beyond: prove_lattice / prove_reach and act_bound."""
+    if act <= 1:
+        if mode == "int":
+            S.prove_exact(name, ref, mag, weights, stored=stored, out=out)
+        return ref, None
+    if mode == "int":
+        return S.prove_lattice(f"{name}/{S.act_name(act)}", p, mag, act, weights, stored=stored, out=out), None
+    S.prove_reach(f"{name}/{S.act_name(act)}", p, act)
+    return S.act_bound(p, mag, kred, act, out)
+
+
+# ------------------------------------------------------------------------------------------------ verdicts
+def _verdict(tag, kern, expect, mode, parts):
+    """parts: (name, got, ref, mag, kred, out[, bound]).  Prints the figures, then asserts kernel and instruments.  `bound`: the
+    per-element bound of an activation beyond ReLU (S.act_bound) instead of elem_bound(mag, kred)."""
+    infos = []
+    for name, got, ref, mag, kred, out, *rest in parts:
+        bound = rest[0] if rest else None
+        if mode == "int":
+            e = S.check_exact(got, ref)
+            print(f"{tag} [{kern}] {name}: exact {e['ok']} wrong {e.get('nbad')} of {e.get('n')} | bound n/a | bias n/a")
+            infos.append((name, e))
+        else:
+            a = S.check_bound(got, ref, mag, kred, out, bound=bound)
+            # the bias needs K_red <= 1152, a bf16 output and >= 4096 elements with |ref| >= 2^-6 -- a property of the case's
+            # REFERENCE (the issue's 1 x 13 x 10 stride-2 shape has 2240 outputs in all): decided before the output is looked at
+            eligible = int((np.abs(ref) >= 2.0 ** -6).sum())
+            bias_applies = out == "bf16" and kred <= S.BIAS_MAX_KRED and eligible >= S.BIAS_MIN_ELEMS
+            b = S.check_bias(got, ref, out) if bias_applies else {"ok": True, "bias": float("nan"), "n_bias": 0}
+            print(f"{tag} [{kern}] {name}: worst |got-ref|/bound {a.get('worst', float('nan')):.3f} over {a.get('n')} elements, "
+                  f"violations {a.get('nviol')} | bias {b['bias']:+.4f} over {b['n_bias']}")
+            infos.append((name, a))
+            infos.append((name + " bias", b))
+    assert kern == expect, f"{tag}: served by {kern!r}, expected {expect!r}"
+    for name, i in infos:
+        assert i["ok"], f"{tag} {name}: {i}"
+
+
+# ================================================================================================ mv_conv2d_nhwc_fwd / mv_linear_fwd
+@functools.lru_cache(maxsize=None)
+def _conv_data(mode, N, H, W, C, K, R, stride, pad, dil, act, res, dtype, out, nnz, xlim, seed):
+    rng = S.rng_of(seed)
+    q = S.bf if dtype == "bf16" else _f32
+    qo = S.bf if out == "bf16" else _f32
+    x = _x(mode, rng, (N, H, W, C), _xlim(mode, act, xlim), q)
+    w = _w(mode, rng, K, R * R * C, nnz, q).reshape(K, R, R, C)
+    sc, sh = _sc_act(mode, rng, K, act), _sh_act(mode, rng, K, act)
+    Ho = (H + 2 * pad - dil * (R - 1) - 1) // stride + 1
+    Wo = (W + 2 * pad - dil * (R - 1) - 1) // stride + 1
+    r = None
+    if res:
+        r = S.int_tensor(rng, (N, Ho, Wo, K), _res_lim(act)) * np.float32(_step(act)) if mode == "int" else qo(rng.standard_normal((N, Ho, Wo, K)))
+    ref, mag, p = S.conv_ref(x, w, sc, sh, r, act, stride, pad, dil, pre=True)
+    ref, bound = _judge_ref("conv", mode, act, p, ref, mag, R * R * C, [w], [x, w] + ([r] if res else []), out)
+    return x, w, sc, sh, r, ref, mag, bound
+
+
+def _run_conv(tag, mode, shape, expect, act=0, res=False, dtype="bf16", out="bf16", flags=(), linear=False, splitk=False, nnz=32,
+              xlim=2, seed=0):
+    N, H, W, C, K, R, stride, pad, dil = shape
+    x, w, sc, sh, r, ref, mag, bound = _conv_data(mode, N, H, W, C, K, R, stride, pad, dil, act, res, dtype, out, nnz, xlim, seed)
+    xd, wd, scd, shd = _dev(x, dtype), _dev(w, dtype), _dev(sc, "fp32"), _dev(sh, "fp32")
+    rd = None if r is None else _dev(r, out)
+    buf, y = _out_guarded(ref.shape, out)
+
+    def launch():
+        if linear:                                  # (1, M, 1, K_red, N_out, 1, 1, 0, 1)
+            _lib.call("mv_linear_fwd", _p(xd), _p(wd), _p(scd), _p(shd), _p(rd), _p(y), H, K, C, act, DT[dtype], DT[out], _stream())
+        else:
+            _lib.call("mv_conv2d_nhwc_fwd", _p(xd), _p(wd), _p(scd), _p(shd), _p(rd), _p(y), N, H, W, C, K, R, R, stride, stride, pad, pad,
+                      dil, dil, 1, act, DT[dtype], DT[out], _stream())
+    with _Flags(flags):
+        if splitk:                                  # the mv_set_scratch protocol of include/eqxvision_amd.h
+            M = ref.shape[0] * ref.shape[1] * ref.shape[2]
+            nb = int(_lib.load().mv_splitk_scratch_bytes(M, K, R * R * C))
+            assert nb > 0, f"{tag}: not a split shape"
+            ws = torch.zeros(nb, dtype=torch.uint8, device="cuda")
+            _lib.call("mv_set_scratch", _p(ws), nb, _stream())
+        launch()
+        kern = _lib.last_kernel()
+    torch.cuda.synchronize()
+    if splitk:
+        assert bool((ws[:4096] == 0).all().item()), f"{tag}: arrival words not left zero"
+    assert _guard_ok(buf), f"{tag}: guard band behind y touched"
+    _verdict(tag, kern, expect, mode, [("y", _host(y), ref, mag, R * R * C, out, bound)])
+
+
+# ================================================================================================ mv_fc_stream_fwd
+def _run_fc_stream(M, K, N, bias, out, mode, act=1):
+    """The entry has no scale: beyond ReLU the lattice step goes into the weights (+-step is a bf16 value) and the bias."""
+    rng = S.rng_of(21)
+    assert _lib.load().mv_fc_stream_supported(M, N, K, BF, DT[out])
+    x = _x(mode, rng, (M, K), _xlim(mode, act, 2))
+    w = _w(mode, rng, N, K, 32)
+    if mode == "int":
+        w = w * np.float32(_step(act))
+    b = _sh_act(mode, rng, N, act) if bias else None
+    ref, mag, p = S.gemm_ref(x, w, None, b, None, act, pre=True)
+    ref, bound = _judge_ref("fc_stream", mode, act, p, ref, mag, K, [w], [x, w], out)
+    NT = (N + 31) // 32
+    wp = np.zeros((NT * 32, K), np.float32)
+    wp[:N] = w
+    wf = np.ascontiguousarray(wp.reshape(NT, 32, K // 16, 2, 8).transpose(0, 2, 3, 1, 4))          # [tile][step][h][n][e] (header)
+    xd, wd, bd = _dev(x), _dev(wf), (None if b is None else _dev(b, "fp32"))
+    nbytes = int(_lib.load().mv_fc_stream_workspace(M, N, K))
+    ws = torch.empty((nbytes // 4,), dtype=torch.float32, device="cuda")
+    buf, y = _out_guarded((M, N), out)
+    _lib.call("mv_fc_stream_fwd", _p(xd), _p(wd), _p(bd), _p(y), _p(ws), nbytes, M, N, K, act, BF, DT[out], _stream())
+    kern = _lib.last_kernel()
+    torch.cuda.synchronize()
+    assert _guard_ok(buf), "fc_stream: guard band behind y touched"
+    _verdict(f"fc_stream/{M}x{K}x{N}/{S.act_name(act)}/{mode}", kern, "fc_stream_bf16", mode, [("y", _host(y), ref, mag, K, out, bound)])
+
+
+# ================================================================================================ mv_dwconv2d_nhwc_fwd
+DW_ACT_SEED = 142
+
+
+def _run_dwconv(tag, N, H, W, C, R, stride, flag, expect, mode, act=1):
+    rng = S.rng_of(42 if act <= 1 else DW_ACT_SEED)          # (the seed whose 16-channel case reaches every piece of the hard pair)
+    assert _lib.load().mv_dwconv2d_supported(C, C, C, R, R, BF, BF)
+    x = _x(mode, rng, (N, H, W, C), _xlim(mode, act, 2))
+    w = _w(mode, rng, C, R * R, R * R).reshape(C, R, R, 1)                        # every tap +-1 in mode int
+    sc, sh = _sc_act(mode, rng, C, act), _sh_act(mode, rng, C, act)
+    ref, mag, p = S.conv_ref(x, w, sc, sh, None, act, stride, R // 2, 1, C, pre=True)
+    ref, bound = _judge_ref("dwconv", mode, act, p, ref, mag, R * R, [w], [x, w], "bf16")
+    xd, wd, scd, shd = _dev(x), _dev(w[..., 0].transpose(1, 2, 0)), _dev(sc, "fp32"), _dev(sh, "fp32")
+    buf, y = _out_guarded(ref.shape)
+    with _Flags((flag,) if flag else ()):
+        _lib.call("mv_dwconv2d_nhwc_fwd", _p(xd), _p(wd), _p(scd), _p(shd), _p(y), N, H, W, C, R, R, stride, stride, R // 2, R // 2, 1, 1, act, BF, BF,
+                  _stream())
+        kern = _lib.last_kernel()
+    torch.cuda.synchronize()
+    assert _guard_ok(buf), f"dwconv/{tag}: guard band behind y touched"
+    _verdict(f"dwconv/{tag}/{mode}", kern, expect, mode, [("y", _host(y), ref, mag, R * R, "bf16", bound)])
+
+
+# ================================================================================================ mv_conv2d_nchw_fwd (stems)
+def _run_stem_nchw(tag, N, H, W, K, R, stride, pad, act, tokens, expect, mode):
+    """fp32 images; the kernel rounds them to bf16 for the MFMA (header) -- a no-op for integers and for bf16-valued Gaussians.
+    With `tokens` the position rows are added BEFORE the activation (every epilogue of stem.hip): they enter the reference as a
+    residual."""
+    C = 3
+    rng = S.rng_of(51)
+    x = _x(mode, rng, (N, C, H, W), _xlim(mode, act, 2))
+    w = _w(mode, rng, K, C * R * R, 16).reshape(K, C, R, R)
+    sc, sh = _sc_act(mode, rng, K, act), _sh_act(mode, rng, K, act)
+    Ho, Wo = (H + 2 * pad - R) // stride + 1, (W + 2 * pad - R) // stride + 1
+    P = Ho * Wo
+    pos = res = None
+    if tokens:
+        T = P + 1
+        pos = S.int_tensor(rng, (T, K), 4) * np.float32(_step(act)) if mode == "int" else rng.standard_normal((T, K)).astype(np.float32)
+        res = np.broadcast_to(pos[1:].reshape(1, Ho, Wo, K), (N, Ho, Wo, K))
+    ref, mag, p = S.conv_ref(x.transpose(0, 2, 3, 1), w.transpose(0, 2, 3, 1), sc, sh, res, act, stride, pad, 1, pre=True)
+    kred = C * R * R + (1 if tokens else 0)
+    ref, bound = _judge_ref("stem", mode, act, p, ref, mag, kred, [w], [x, w], "bf16")
+    ref, mag = ref.reshape(N, P, K), mag.reshape(N, P, K)
+    bound = None if bound is None else bound.reshape(N, P, K)
+    xd, wd, scd, shd = _dev(x, "fp32"), _dev(w), _dev(sc, "fp32"), _dev(sh, "fp32")
+    if tokens:
+        posd = _dev(pos, "fp32")
+        buf, y = _out_guarded((N, T, K))
+        y[:, 0] = 0.0                                                                 # row 0 (class token) is not this kernel's
+        pad0 = np.zeros((N, 1, K))
+        ref, mag = np.concatenate([pad0, ref], 1), np.concatenate([pad0, mag], 1)
+        bound = None if bound is None else np.concatenate([pad0, bound], 1)
+        targs = (T, 1, _p(posd))
+    else:
+        buf, y = _out_guarded((N, P, K))
+        targs = (0, 0, None)
+    _lib.call("mv_conv2d_nchw_fwd", _p(xd), _p(wd), _p(scd), _p(shd), _p(y), N, C, H, W, K, R, R, stride, stride, pad, pad, act, F32, BF, *targs,
+              _stream())
+    kern = _lib.last_kernel()
+    torch.cuda.synchronize()
+    assert _guard_ok(buf), f"stem/{tag}: guard band behind y touched"
+    _verdict(f"stem/{tag}/{mode}", kern, expect, mode, [("y", _host(y), ref, mag, kred, "bf16", bound)])

@@ -71,7 +71,9 @@ sensitivity, plus ln_ref_bound.  mv_cnblock_dw_fwd: cnb_exact (normalize = 0 in 
 bound).  mv_patch4_ln_fwd: patch4_gauss (emulation 0.005, MI355X 0.006).
 mv_linear_lnout_fwd -> mv_linear_lnin_fwd: check_lnout (hi a correct rounding, |lo|, hi + lo, Chan mean and variance, every element
 and row) and lnin_ref_bound (its docstring states the model); emulation 0.417 / 0.276, MI355X 0.417 / 0.276 at the two cases.
-Still under `_cases._cmp` only: mv_se_scale_fwd.
+mv_se_scale_fwd and the activations fused into the conv / GEMM epilogues have the two instruments in tests/_strict.py ("fused
+activations": S.through_act is the GELU line above for every activation, with this module's gelu_lipschitz) and run in
+tests/test_strict_act_gpu.py.
 """
 from __future__ import annotations
 

@@ -17,8 +17,8 @@ kernels mv_channel_scale_bwd_f32, mv_avgpool_global_bwd_nhwc_f32, mv_bn_dgamma_f
 The moments and BatchNorm fold kernels and the forward LayerNorm kernels (plain, vectorised, slim, post-norm add, patch merge) are in
 test_strict_norm_gpu.py; the GEMMs that normalise their rows on the way in (mv_ln_linear_fwd, mv_ln_mlp*_fwd: exact +-1 rows and a
 composed per-element bound), mv_cnblock_dw_fwd, mv_patch4_ln_fwd and mv_linear_lnout_fwd -> mv_linear_lnin_fwd are in
-test_strict_lngemm_gpu.py.  The dropout / PRNG kernels are compared bit for bit in `_cases`.  Still under `_cases._cmp` only:
-mv_se_scale_fwd.
+test_strict_lngemm_gpu.py.  The dropout / PRNG kernels are compared bit for bit in `_cases`.  mv_se_scale_fwd (exact on the
+activations' lattices and a bound composed from squeeze.hip's roundings) is in test_strict_act_gpu.py.
 mv_maxpool2d_out_nhwc_fwd is exact in test_squeezenet_gpu.py.  The training backward kernels (conv dgrad / wgrad,
 mv_maxpool2d_bwd_nhwc_f32, mv_colsum_f32, the softmax / attention backward, the gathers' adjoints: exact and bounded;
 mv_act_bwd_f32, the LayerNorm backward, the cross-entropy, the Swin window backward: float64 reference at edge shapes) are in
