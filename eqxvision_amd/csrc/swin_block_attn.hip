@@ -710,7 +710,10 @@ __global__ __launch_bounds__(128, 3) void swin_win96_kernel(const SwinBAP p) {
 extern "C" {
 
 // windows per workgroup.  (C = 96 also ran as 4 windows / 8 waves, one workgroup per CU: -4 % on swin_t, removed in round 4.)
-static int swin_block_attn_nwin(int C) { return C == 384 ? 1 : (C == 192 ? 2 : (C == 96 ? 2 : 0)); }
+// C = 96: swin_win96 (the default) runs ONE window per workgroup and takes any window count; only the shared kernel pairs windows.
+static int swin_block_attn_nwin(int C) {
+    return C == 384 ? 1 : (C == 192 ? 2 : (C == 96 ? (mv::get_flag("swin_c96_shared") ? 2 : 1) : 0));
+}
 
 int mv_swin_block_attn_supported(int Hf, int Wf, int C, int heads, int wsh, int wsw, int x_dtype) {
     if (mv::get_flag("no_swin_block_attn")) return 0;

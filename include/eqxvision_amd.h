@@ -321,8 +321,8 @@ int mv_ln_mlp_fwd(const void* x, const void* w1, const float* b1, const void* w2
  *       bqkv[g][t][0..31] = the matching bias slice
  *   wp_f[tile t 0..C/32-1][j][lane][e] = Wproj[32*t + lane%32][16*j + 8*(lane/32) + e];   bp[C]
  *   bias64[heads][64][64] fp32: relative-position bias bias[h][query][key] padded to 64 x 64, -1e30 on key columns >= 49
- * Supported: heads of 32 channels, 7 x 7 windows, C = 384 / 192 / 96 (swin_t / swin_s stages 2 / 1 / 0: one / two / four windows
- * per workgroup; the windows of an image must divide by that). */
+ * Supported: heads of 32 channels, 7 x 7 windows, C = 384 / 192 / 96 (swin_t / swin_s stages 2 / 1 / 0: one / two / one window
+ * per workgroup -- two at C = 96 under the flag swin_c96_shared; the windows of an image must divide by that). */
 int mv_swin_block_attn_supported(int Hf, int Wf, int C, int heads, int wsh, int wsw, int x_dtype);
 int mv_swin_block_attn_fwd(const void* x, const void* wqkv_f, const float* bqkv, const void* wp_f, const float* bp,
                            const float* bias64, void* y, int B, int Hf, int Wf, int C, int heads, int wsh, int wsw, int shh,
