@@ -59,6 +59,7 @@ class Tape:
         self.count = 0
         self.frozen = None      # ids of the leaves a filter spec (filter_value_and_grad's `arg`) marks False; None = no spec
         self.inside = 0         # > 0 while a g_* function runs (its own C-ABI calls are allowed)
+        self.matmul_dtype = "fp32"   # filter_value_and_grad's `matmul_dtype`: "bf16" = g_linear's three products on the bf16 matrix cores
 
 
 class Node:
@@ -190,6 +191,13 @@ def _matmul_nt(x: torch.Tensor, w: torch.Tensor, M: int, N: int, K: int, bias=No
     """y[M,N] = x[M,K] . w[N,K]^T (+ bias): the forward Linear entry."""
     y = _new((M, N))
     _call("mv_linear_fwd", _p(x), _p(w), None, _p(bias), None, _p(y), M, N, K, _lib.ACT_NONE, F32, F32, _S())
+    return y
+
+
+def _matmul_mp_fwd(x: torch.Tensor, w: torch.Tensor, M: int, N: int, K: int, bias=None) -> torch.Tensor:
+    """y[M,N] = r(x[M,K]) . r(w[N,K])^T (+ bias, un-rounded), r = round to bf16: the mixed-precision forward (csrc/linear_mp.hip)."""
+    y = _new((M, N))
+    _call("mv_linear_mp_fwd", _p(x), _p(w), _p(bias), _p(y), M, N, K, _S())
     return y
 
 
@@ -587,7 +595,10 @@ def g_stem_conv_pool(x: Act, conv, bn, act, pool) -> Act:
 
 # ------------------------------------------------------------------------------------------------------------ Linear
 @_op
-def g_linear(x: Act, lin, act=None, residual: Optional[Act] = None, out_fp32: bool = False) -> Act:
+def g_linear(x: Act, lin, act=None, residual: Optional[Act] = None, out_fp32: bool = False, keep_fp32: bool = False) -> Act:
+    """Under filter_value_and_grad(..., matmul_dtype="bf16") the product and its two gradients run on the bf16 matrix cores
+    (mv_linear_mp_*: operands rounded to bf16 on their way into LDS, fp32 accumulation, fp32 results; no transposed copies); the bias,
+    its gradient, the residual and the activation stay fp32.  `keep_fp32` (the classifier head) keeps the fp32 products."""
     _check_act(act)
     if x.kind == "img":
         raise ValueError("Linear on a raw image")
@@ -598,7 +609,8 @@ def g_linear(x: Act, lin, act=None, residual: Optional[Act] = None, out_fp32: bo
     W = _leaf_dev(lin.weight)
     bias = _leaf_dev(lin.bias).reshape(-1) if lin.bias is not None else None
     oshape = tuple(x.t.shape[:-1]) + (N,)
-    z = _matmul_nt(x.t, W, M, N, K, bias).reshape(oshape)
+    mp = tape().matmul_dtype == "bf16" and not keep_fp32
+    z = (_matmul_mp_fwd if mp else _matmul_nt)(x.t, W, M, N, K, bias).reshape(oshape)
     if residual is not None and tuple(residual.t.shape) != oshape:
         raise ValueError(f"residual shape {tuple(residual.t.shape)} != Linear output {oshape}")
     y2 = z if residual is None else _add(z, residual.t)
@@ -612,11 +624,19 @@ def g_linear(x: Act, lin, act=None, residual: Optional[Act] = None, out_fp32: bo
         g2 = _act_bwd(g, y2, act)
         if _trainable(lin.bias):
             _acc_param(lin.bias, _colsum(g2, None, N))
-        if _trainable(lin.weight):
+        if _trainable(lin.weight) and mp:
+            dW = _new((N, K))                                           # dW[N,K] = r(g)^T . r(x), the rows split over blocks
+            _offer_scratch()
+            _call("mv_linear_mp_wgrad", _p(g2), _p(xin), _p(dW), M, N, K, _S())
+            _acc_param(lin.weight, dW)
+        elif _trainable(lin.weight):
             gT, xT = _transpose(g2, M, N), _transpose(xin, M, K)        # dW[N,K] = g^T . x
             _acc_param(lin.weight, _matmul_nt(gT, xT, N, K, M))
         dx = None
-        if need_dx:
+        if need_dx and mp:
+            dx = _new(tuple(xin.shape))                                 # dx[M,K] = r(g) . r(W)
+            _call("mv_linear_mp_dgrad", _p(g2), _p(W), _p(dx), M, N, K, _S())
+        elif need_dx:
             Wt = _leaf_dev(lin.weight, "t", lambda raw: _transpose(raw, N, K))   # [K,N]
             dx = _matmul_nt(g2, Wt, M, K, N).reshape(tuple(xin.shape))         # dx[M,K] = g . W
         return (dx, g2 if residual is not None else None)
@@ -625,7 +645,8 @@ def g_linear(x: Act, lin, act=None, residual: Optional[Act] = None, out_fp32: bo
 
 @_op
 def g_linear_head(x: Act, lin) -> Act:
-    return g_linear.__wrapped__(x, lin)
+    # fp32 under either matmul_dtype: the logits carry no bf16 rounding, as in the inference forward (include/eqxvision_amd.h: mv_linear_fwd)
+    return g_linear.__wrapped__(x, lin, keep_fp32=True)
 
 
 # ------------------------------------------------------------------------------------------------------------ LayerNorm
@@ -1137,16 +1158,27 @@ def _frozen_ids(model, spec) -> set:
     return frozen
 
 
-def filter_value_and_grad(fn: Optional[Callable] = None, *, arg=None) -> Callable:
+MATMUL_DTYPES = ("fp32", "bf16")
+
+
+def filter_value_and_grad(fn: Optional[Callable] = None, *, arg=None, matmul_dtype: str = "fp32") -> Callable:
     """`eqx.filter_value_and_grad`: fn(model, *args) -> scalar loss; returns (loss, grads) with `grads` = the model tree with
     every array leaf replaced by its gradient (zeros where the loss does not depend on it) and every other leaf kept.
 
     `arg` (a keyword, so `functools.partial(filter_value_and_grad, arg=filter_spec)` is the decorator of the reference's
     transfer-learning tutorial): a tree of the model's structure with a bool at every array leaf.  A leaf whose bool is False is
     frozen: its gradient is `None`, no parameter-gradient kernel is launched for it, and a rule with no trainable leaf and no
-    input on the tape records no node (`_mk`), so the backward pass stops where the trainable part of the network starts."""
+    input on the tape records no node (`_mk`), so the backward pass stops where the trainable part of the network starts.
+
+    `matmul_dtype` (a keyword like `arg`): "fp32" (the default) runs every product in fp32.  "bf16" is mixed precision for the Linear
+    layers (`g_linear`: ViT's and Swin's projections and MLPs, the qkv projection, the patch-merging reduction): the forward product,
+    the input gradient and the weight gradient round their operands to bf16 (round-to-nearest-even) and accumulate in fp32 on the
+    bf16 matrix cores; parameters, gradients, biases and their gradients, optimiser state, convolutions, attention's products and
+    the classifier head stay fp32.  Any other value raises ValueError here, when the decorator is applied."""
+    if matmul_dtype not in MATMUL_DTYPES:
+        raise ValueError(f"filter_value_and_grad: matmul_dtype must be one of {MATMUL_DTYPES}, got {matmul_dtype!r}")
     if fn is None:
-        return functools.partial(filter_value_and_grad, arg=arg)
+        return functools.partial(filter_value_and_grad, arg=arg, matmul_dtype=matmul_dtype)
 
     @functools.wraps(fn)
     def wrapped(model, *args, **kwargs):
@@ -1161,6 +1193,7 @@ def filter_value_and_grad(fn: Optional[Callable] = None, *, arg=None) -> Callabl
             raise _lib.MVError("eqxvision_amd needs an MI355X (no HIP device visible); there is no CPU fallback")
         t = _tls.tape = Tape()
         t.frozen = frozen
+        t.matmul_dtype = matmul_dtype
         try:
             with precision("fp32"):
                 loss = fn(model, *args, **kwargs)

@@ -979,6 +979,21 @@ int mv_softmax_xent_map_f32(const float* logits, const int32_t* labels, const ui
 /* y[C][R] = x[R][C]^T, rows of x x_row_stride elements apart (0 = dense). */
 int mv_transpose2d_f32(const float* x, float* y, int R, int C, int64_t x_row_stride, mv_stream_t stream);
 
+/* ---- mixed-precision Linear for the training step (filter_value_and_grad(..., matmul_dtype="bf16"); eqx.nn.Linear under vmap:
+ * vit.py:64,74; mlps.py:60-64; swin.py).  Every tensor is fp32 in memory.  r(.) rounds an operand element to bf16, round-to-nearest-
+ * even, on its way into LDS; products are accumulated in fp32 on v_mfma_f32_32x32x16_bf16 and the result is stored as fp32.  Any
+ * M, N, K >= 1 (N, K <= 2^21); no transposed copy of an operand is made: the operands whose reduction runs along their rows are
+ * read from LDS with the transposed read.  16-byte loads where base and row pitch are 16-byte aligned, 4-byte loads otherwise.
+ *   fwd:    y[M,N]  = r(x[M,K]) . r(w[N,K])^T + bias[n]   (bias may be NULL; it is added in fp32, NOT rounded)
+ *   dgrad:  dx[M,K] = r(g[M,N]) . r(w[N,K])               (reduction over N)
+ *   wgrad:  dw[N,K] = r(g[M,N])^T . r(x[M,K])             (reduction over M).  With scratch on offer (mv_set_scratch: 4096 bytes + at
+ *           least 2 x the gradient's bytes) the rows are split over up to 64 parts of at least 256 rows, which are added in index order
+ *           (bit-reproducible; the first 4096 bytes of the offer stay zero); without it one block walks all of M for its tile (same
+ *           result to within fp32 summation order).  mv_last_kernel tells the two forms apart. */
+int mv_linear_mp_fwd(const float* x, const float* w, const float* bias, float* y, int64_t M, int N, int K, mv_stream_t stream);
+int mv_linear_mp_dgrad(const float* g, const float* w, float* dx, int64_t M, int N, int K, mv_stream_t stream);
+int mv_linear_mp_wgrad(const float* g, const float* x, float* dw, int64_t M, int N, int K, mv_stream_t stream);
+
 /* hipGraph capture of a whole forward (replaces the reference's eqx.filter_jit executable) */
 int mv_graph_begin_capture(mv_stream_t stream);
 int mv_graph_end_capture(mv_stream_t stream, void** graph_exec);
