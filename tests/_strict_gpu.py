@@ -270,7 +270,8 @@ def _run_dwconv(tag, N, H, W, C, R, stride, flag, expect, mode, act=1):
 
 # ================================================================================================ mv_conv2d_nchw_fwd (stems)
 def _run_stem_nchw(tag, N, H, W, K, R, stride, pad, act, tokens, expect, mode):
-    """fp32 images; the kernel rounds them to bf16 for the MFMA (header) -- a no-op for integers and for bf16-valued Gaussians.
+    """fp32 images; the kernel rounds them to bf16 for the MFMA (header) -- a no-op for integers and for bf16-valued Gaussians
+    (images on which that rounding is visible: tests/_strict_entry.py, run by tests/test_strict_entry_gpu.py).
     With `tokens` the position rows are added BEFORE the activation (every epilogue of stem.hip): they enter the reference as a
     residual."""
     C = 3

@@ -819,6 +819,10 @@ def emu_patch4_ln(x, hi, lo, b, g, be, split, eps=EPS, defect=None):
 # two standard deviations (the fold rounds y, not y - mean), GELU.
 LNFOLD_CASES = [(75 * 256 + 1, 320, 256, 640, 0, 0.0), (75 * 256, 512, 512, 1024, 2, 2.0)]
 LNFOLD_EPS = 1e-5
+# The consumer's head-major form (tokens = 197, dh = 64) needs M % 197 == 0, which no row above has: 197 x 97 rows is the smallest
+# multiple at which the producer (D = 320: 2 column tiles x 75 row tiles) and the consumer still take the 256 x 256 tile.  Its own
+# table: tests/test_strict_entry_gpu.py runs the pair on it once (token-major and head-major), test_lnfold_pair keeps its two rows.
+LNFOLD_TOKEN_CASE = (197 * 97, 320, 256, 640, 0, 0.0)
 U24 = 2.0 ** -24
 LNFOLD_STAT_OPS = 24          # roundings of the Chan merges beyond the N - 1 adds: per piece mu, d, the merge's d, d^2, 64 d^2, +, twice, / N
 
