@@ -3,15 +3,26 @@
 // The filter lives in two tap tables the host builds in float64 (eqxvision_amd/preprocess.py: axis_table); the kernel only
 // applies them, so the same entry serves the antialiased ImageNet preset and plain two-tap up-sampling.  HBM-bound gather, no
 // matrix work: every input byte a tile needs is read once into LDS, both passes run out of LDS, every output is stored once.
-// Five entries share the tile body: one image size per launch (mv_preprocess_u8_fwd), one record per image for a packed batch
-// of any sizes (mv_preprocess_u8_ragged_fwd), one box per image that is cropped FIRST and then resized, mirrored or not
-// (mv_preprocess_u8_boxes_fwd: the training transform; its filter is generated in the tile, no tables), and one window per image
-// of the WHOLE image resized, mirrored and padded, with the label map gathered alongside (mv_preprocess_u8_seg_fwd: the
-// segmentation training transform; the same generated filter on the part of a tile that is not padding), and the boxes entry
-// with a partner per image mixed in, rectangles erased or replaced and the soft targets written alongside
-// (mv_preprocess_u8_mix_fwd: mixup / cutmix / random erasing; a tile runs the passes once per image it needs).  A launch has ONE tile
-// and ONE LDS size; the record entries size them for the largest spans and pitches of their batch, so one steeply down-sampled
-// image lowers the occupancy of the whole launch (accepted).
+// Five entries share the tile body (tile_rows); a launch has ONE tile and ONE LDS size, sized for the largest spans and pitches
+// of its batch, so one steeply down-sampled image lowers the occupancy of the whole launch (accepted):
+//   mv_preprocess_u8_fwd         one image size per launch, the two tables of the launch
+//   mv_preprocess_u8_ragged_fwd  adds one record per image: a packed batch of any sizes, every image its own tables
+//   mv_preprocess_u8_boxes_fwd   adds one box per image that is cropped FIRST and then resized, mirrored or not (the training
+//                                transform); its filter is generated in the tile, no tables
+//   mv_preprocess_u8_mix_fwd     adds to the boxes a partner per image mixed in, rectangles erased or replaced and the soft targets
+//                                written alongside (mixup / cutmix / random erasing); a tile runs the passes once per image it needs
+//   mv_preprocess_u8_seg_fwd     one window per image of the WHOLE image resized, mirrored and padded, the label map gathered
+//                                alongside (the segmentation transform); the generated filter on the part of a tile that is not padding
+// On the host every entry is its own argument rules, its loop over the host records, its parameter struct and one call, built from
+//   check_args, check_buffers    B, sizes, dtype; no NULL buffer
+//   check_image                  a record's image lies inside the packed buffer
+//   check_taps                   the tap limit; the largest pitches of the batch
+//   check_disjoint               no output overlaps an input or another output
+//   prep_params, launch_tiles    the common parameters; tile and LDS sizing over the batch, the grid, the device status word, the
+//                                launch.  The status word is fetched LAST in every entry (the three older ones used to fetch it before
+//                                the tile was sized): without a device, a valid call whose geometry does not fit the LDS is told so.
+// On the device the record kernels share image_inside (a record's image lies inside x), tile_of (the workgroup's tile) and the
+// two table sources, tables_from_global and tables_resized.
 #include "common.h"
 
 namespace mv {
@@ -43,6 +54,22 @@ struct PrepRaggedP {
 };
 
 __device__ __forceinline__ int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
+
+// A record's image lies inside x: sizes >= 1, fewer than 2^31 bytes, `offset` within the x_bytes of the buffer.  The records are
+// device data the host cannot see at launch time; a record that fails this forms no address at all.
+template <class Record> __device__ __forceinline__ bool image_inside(const Record& g, long long x_bytes) {
+    const long long img_bytes = (long long)g.Hin * g.Win * 3;
+    return g.Hin >= 1 && g.Win >= 1 && img_bytes < (1LL << 31) && g.offset >= 0 && g.offset <= x_bytes - img_bytes;
+}
+
+// The TH x TW tile of the output this workgroup owns: its first row and column, its extent cut at the output's edge.
+struct Tile {
+    int y0, x0, th, tw;
+};
+__device__ __forceinline__ Tile tile_of(const PrepP& p) {
+    const int y0 = blockIdx.y * p.TH, x0 = blockIdx.x * p.TW;
+    return {y0, x0, min(p.TH, p.Hout - y0), min(p.TW, p.Wout - x0)};
+}
 
 // taps an n_in -> n_out resize can give one output: the open interval of half-width max(1, in / out), no more than the axis
 __host__ __device__ inline int taps_needed(int in, int out_full) {
@@ -166,11 +193,13 @@ __device__ __forceinline__ double axis_weight(const AxisTaps& t, int k) {
 }
 
 // Step 1, generated: the filter of an h x w box at (top, left) of the image resized to Hr x Wr, for rows y0 .. y0 + th - 1 and
-// columns x0 .. x0 + tw - 1 of the resized box; column j of a mirrored result is the unmirrored column Wr - 1 - j (same taps,
-// same tap order).  One thread per row or column of the tile: weights in ascending tap order, their sum accumulated in that
-// order, each quotient rounded once to fp32.  first / last grow with the output, so the rectangle follows from the tile's extreme
-// outputs (with a mirror the two column ends swap).  The caller has clamped the box into the image; counts are clamped to the
-// pitches the launch was sized for.
+// columns x0 .. x0 + tw - 1 of the resized box.  Two uses: a box resized to the output itself, Hr x Wr = Hout x Wout and the tile
+// a tile of the output (boxes, mix); the whole image, box (0, 0, Hin, Win), resized to Hr x Wr, of which the output is a window
+// (seg, through tables_window).  Column j of a mirrored result is the unmirrored column Wr - 1 - j (same taps, same tap order).
+// One thread per row or column of the tile: weights in ascending tap order, their sum accumulated in that order, each quotient
+// rounded once to fp32.  first / last grow with the output, so the rectangle follows from the tile's extreme outputs (with a
+// mirror the two column ends swap).  The caller has clamped the box into the image; counts are clamped to the pitches the launch
+// was sized for.
 __device__ __forceinline__ TileRect tables_resized(const PrepP& p, const TileLds& L, int top, int left, int h, int w, int Hr, int Wr,
                                                    int flip, int y0, int x0, int th, int tw) {
     const int tid = threadIdx.x;
@@ -198,14 +227,9 @@ __device__ __forceinline__ TileRect tables_resized(const PrepP& p, const TileLds
     return t;
 }
 
-// Step 1, source B: a box resized to the output itself (mv_preprocess_u8_boxes_fwd); the tile is a tile of the output.
-__device__ __forceinline__ TileRect tables_generated(const PrepP& p, const TileLds& L, int top, int left, int h, int w, int flip,
-                                                     int y0, int x0, int th, int tw) {
-    return tables_resized(p, L, top, left, h, w, p.Hout, p.Wout, flip, y0, x0, th, tw);
-}
-
-// Step 1, source C: the whole image resized to Hr x Wr, of which the output is a window (mv_preprocess_u8_seg_fwd); r0, q0: the
-// resized row / mirrored column of the tile's first output, th_v x tw_v: the prefix of the tile that lies inside Hr x Wr.
+// The seg kernel's call: r0, q0 the resized row / mirrored column of the tile's first output, th_v x tw_v the prefix of the tile
+// that lies inside Hr x Wr.  A forward, kept on purpose: with the call written out in the seg kernel its eight instantiations
+// take two more VGPRs (the boxes and mix kernels call tables_resized directly at no such cost).
 __device__ __forceinline__ TileRect tables_window(const PrepP& p, const TileLds& L, int Hr, int Wr, int flip, int r0, int q0,
                                                   int th_v, int tw_v) {
     return tables_resized(p, L, 0, 0, p.Hin, p.Win, Hr, Wr, flip, r0, q0, th_v, tw_v);
@@ -330,11 +354,10 @@ __device__ __forceinline__ void tile_passes(const PrepP& p, const TileLds& L, co
 
 template <bool CHW_IN, bool NHWC_OUT, bool BF16_OUT>
 __device__ __forceinline__ void preprocess_tile(const PrepP& p, const uint8_t* img, const int b) {
-    const int y0 = blockIdx.y * p.TH, x0 = blockIdx.x * p.TW;
-    const int th = min(p.TH, p.Hout - y0), tw = min(p.TW, p.Wout - x0);
+    const Tile o = tile_of(p);
     const TileLds L = tile_lds<CHW_IN>(p);
-    const TileRect t = tables_from_global(p, L, y0, x0, th, tw);
-    tile_passes<CHW_IN, NHWC_OUT, BF16_OUT>(p, L, t, img, b, y0, x0, th, tw);
+    const TileRect t = tables_from_global(p, L, o.y0, o.x0, o.th, o.tw);
+    tile_passes<CHW_IN, NHWC_OUT, BF16_OUT>(p, L, t, img, b, o.y0, o.x0, o.th, o.tw);
 }
 
 template <bool CHW_IN, bool NHWC_OUT, bool BF16_OUT>
@@ -352,10 +375,8 @@ __global__ __launch_bounds__(256) void preprocess_u8_ragged_kernel(const PrepRag
     const int b = blockIdx.z;
     const mv_preprocess_image g = r.rec[b];
     PrepP p = r.p;
-    const long long img_bytes = (long long)g.Hin * g.Win * 3;
-    const bool ok = g.Hin >= 1 && g.Win >= 1 && img_bytes < (1LL << 31) && g.offset >= 0 && g.offset <= r.x_bytes - img_bytes &&
-                    g.mh >= 1 && g.mh <= p.mh && g.mw >= 1 && g.mw <= p.mw && g.tab_h >= 0 && g.tab_w >= 0 &&
-                    (long long)g.tab_h + (long long)p.Hout * (2 + g.mh) <= r.tab_words &&
+    const bool ok = image_inside(g, r.x_bytes) && g.mh >= 1 && g.mh <= p.mh && g.mw >= 1 && g.mw <= p.mw &&
+                    g.tab_h >= 0 && g.tab_w >= 0 && (long long)g.tab_h + (long long)p.Hout * (2 + g.mh) <= r.tab_words &&
                     (long long)g.tab_w + (long long)p.Wout * (2 + g.mw) <= r.tab_words;
     if (!ok) {
         if (threadIdx.x == 0) atomicOr(p.status, 4u);
@@ -369,7 +390,7 @@ __global__ __launch_bounds__(256) void preprocess_u8_ragged_kernel(const PrepRag
 
 // The box record is device data too.  A record whose image would leave x forms no address: its tiles store nothing.  A box that
 // leaves its image is clamped into it, and a box that needs more taps than the launch's pitches has its counts clamped (in
-// tables_generated); each of these sets bit 2.  (Uniform over the workgroup, before any barrier.)
+// tables_resized); each of these sets bit 2.  (Uniform over the workgroup, before any barrier.)
 struct BoxSrc {
     const uint8_t* img;
     int Hin, Win, top, left, h, w, flip;
@@ -377,8 +398,7 @@ struct BoxSrc {
 };
 __device__ __forceinline__ BoxSrc box_source(const PrepP& p, const mv_preprocess_box& g, const long long x_bytes) {
     BoxSrc s;
-    const long long img_bytes = (long long)g.Hin * g.Win * 3;
-    s.ok = g.Hin >= 1 && g.Win >= 1 && img_bytes < (1LL << 31) && g.offset >= 0 && g.offset <= x_bytes - img_bytes;
+    s.ok = image_inside(g, x_bytes);
     s.img = p.x + (s.ok ? g.offset : 0);
     s.Hin = g.Hin; s.Win = g.Win; s.flip = g.flip != 0;
     s.top = clampi(g.top, 0, g.Hin - 1); s.left = clampi(g.left, 0, g.Win - 1);
@@ -399,11 +419,10 @@ __global__ __launch_bounds__(256) void preprocess_u8_boxes_kernel(const PrepBoxe
     }
     p.Hin = s.Hin; p.Win = s.Win;
     if (s.cut && threadIdx.x == 0) atomicOr(p.status, 4u);
-    const int y0 = blockIdx.y * p.TH, x0 = blockIdx.x * p.TW;
-    const int th = min(p.TH, p.Hout - y0), tw = min(p.TW, p.Wout - x0);
+    const Tile o = tile_of(p);
     const TileLds L = tile_lds<CHW_IN>(p);
-    const TileRect t = tables_generated(p, L, s.top, s.left, s.h, s.w, s.flip, y0, x0, th, tw);
-    tile_passes<CHW_IN, NHWC_OUT, BF16_OUT>(p, L, t, s.img, b, y0, x0, th, tw);
+    const TileRect t = tables_resized(p, L, s.top, s.left, s.h, s.w, p.Hout, p.Wout, s.flip, o.y0, o.x0, o.th, o.tw);
+    tile_passes<CHW_IN, NHWC_OUT, BF16_OUT>(p, L, t, s.img, b, o.y0, o.x0, o.th, o.tw);
 }
 
 // mv_preprocess_u8_mix_fwd.  The image workgroups (blockIdx.z < B): one tile of image b as in the boxes kernel, where every
@@ -440,12 +459,12 @@ __device__ __forceinline__ OutRect out_rect(const PrepP& p, int y0, int x0, int 
     return r;
 }
 __device__ __forceinline__ bool rect_has(const OutRect& r, int Y, int X) { return Y >= r.y0 && Y < r.y1 && X >= r.x0 && X < r.x1; }
-// the non-empty tile [y0, y0 + th) x [x0, x0 + tw) lies wholly inside r / shares a pixel with r
-__device__ __forceinline__ bool rect_holds(const OutRect& r, int y0, int x0, int th, int tw) {
-    return r.y0 <= y0 && y0 + th <= r.y1 && r.x0 <= x0 && x0 + tw <= r.x1;
+// the non-empty tile t lies wholly inside r / shares a pixel with r
+__device__ __forceinline__ bool rect_holds(const OutRect& r, const Tile& t) {
+    return r.y0 <= t.y0 && t.y0 + t.th <= r.y1 && r.x0 <= t.x0 && t.x0 + t.tw <= r.x1;
 }
-__device__ __forceinline__ bool rect_meets(const OutRect& r, int y0, int x0, int th, int tw) {
-    return max(r.y0, y0) < min(r.y1, y0 + th) && max(r.x0, x0) < min(r.x1, x0 + tw);
+__device__ __forceinline__ bool rect_meets(const OutRect& r, const Tile& t) {
+    return max(r.y0, t.y0) < min(r.y1, t.y0 + t.th) && max(r.x0, t.x0) < min(r.x1, t.x0 + t.tw);
 }
 
 __device__ __forceinline__ void mix_targets(const PrepMixP& r) {
@@ -498,30 +517,29 @@ __global__ __launch_bounds__(256) void preprocess_u8_mix_kernel(const PrepMixP r
     if (bad && threadIdx.x == 0) atomicOr(p.status, 4u);
     const float lam = m.lam, oml = m.oml;
 
-    const int y0 = blockIdx.y * p.TH, x0 = blockIdx.x * p.TW;
-    const int th = min(p.TH, p.Hout - y0), tw = min(p.TW, p.Wout - x0);
-    const bool need_r = mixed && (lam != 1.f || rect_meets(cut, y0, x0, th, tw));
-    const bool need_i = !(mixed && rect_holds(cut, y0, x0, th, tw));
-    const bool run_r = need_r && !rect_holds(er_r, y0, x0, th, tw);
-    const bool run_i = need_i && !rect_holds(er_i, y0, x0, th, tw);
+    const Tile o = tile_of(p);
+    const bool need_r = mixed && (lam != 1.f || rect_meets(cut, o));
+    const bool need_i = !(mixed && rect_holds(cut, o));
+    const bool run_r = need_r && !rect_holds(er_r, o);
+    const bool run_i = need_i && !rect_holds(er_i, o);
 
     auto emit = [&](const int y, const int c, const int x, float vi, float vr) {
-        const int Y = y0 + y, X = x0 + x;
+        const int Y = o.y0 + y, X = o.x0 + x;
         if (rect_has(er_i, Y, X)) vi = 0.f;
         if (rect_has(er_r, Y, X)) vr = 0.f;
-        float o;
-        if (mixed && rect_has(cut, Y, X)) o = vr;
-        else if (!mixed || lam == 1.f) o = vi;
-        else o = mul_add_rn(lam, vi, oml, vr);
-        tile_store<NHWC_OUT, BF16_OUT>(p, b, Y, c, X, o);
+        float v;
+        if (mixed && rect_has(cut, Y, X)) v = vr;
+        else if (!mixed || lam == 1.f) v = vi;
+        else v = mul_add_rn(lam, vi, oml, vr);
+        tile_store<NHWC_OUT, BF16_OUT>(p, b, Y, c, X, v);
     };
     const TileLds L = tile_lds<CHW_IN>(p);
     float* sv = L.swx + p.TW * p.mw;                         // [th][3][TW] of v_r, only where the launch has `keep`
     auto resample = [&](const BoxSrc& s, auto&& sink) {
         PrepP q = p;
         q.Hin = s.Hin; q.Win = s.Win;
-        const TileRect t = tables_generated(q, L, s.top, s.left, s.h, s.w, s.flip, y0, x0, th, tw);
-        tile_rows<CHW_IN, NHWC_OUT>(q, L, t, s.img, th, tw, sink);
+        const TileRect t = tables_resized(q, L, s.top, s.left, s.h, s.w, q.Hout, q.Wout, s.flip, o.y0, o.x0, o.th, o.tw);
+        tile_rows<CHW_IN, NHWC_OUT>(q, L, t, s.img, o.th, o.tw, sink);
     };
     if (run_r && run_i) {
         resample(par, [&](const int y, const int c, const int x, const float v) { sv[(y * 3 + c) * p.TW + x] = v; });
@@ -532,9 +550,9 @@ __global__ __launch_bounds__(256) void preprocess_u8_mix_kernel(const PrepMixP r
     } else if (run_i) {
         resample(own, [&](const int y, const int c, const int x, const float v) { emit(y, c, x, v, 0.f); });
     } else {
-        for (int it = threadIdx.x; it < th * 3 * tw; it += 256) {
+        for (int it = threadIdx.x; it < o.th * 3 * o.tw; it += 256) {
             int y, c, x;
-            tile_elem<NHWC_OUT>(it, tw, y, c, x);
+            tile_elem<NHWC_OUT>(it, o.tw, y, c, x);
             emit(y, c, x, 0.f, 0.f);
         }
     }
@@ -563,7 +581,7 @@ __global__ __launch_bounds__(256) void preprocess_u8_seg_kernel(const PrepSegP r
     const int b = blockIdx.z;
     const mv_preprocess_seg g = r.rec[b];
     PrepP p = r.p;
-    const long long px = (long long)g.Hin * g.Win;
+    const long long px = (long long)g.Hin * g.Win;        // image_inside written out: through it these instantiations lose an SGPR
     const bool ok = g.Hin >= 1 && g.Win >= 1 && px * 3 < (1LL << 31) && g.offset >= 0 && g.offset <= r.x_bytes - px * 3 &&
                     (!r.m || (g.mask_offset >= 0 && g.mask_offset <= r.m_bytes - px));
     if (!ok) {
@@ -577,8 +595,8 @@ __global__ __launch_bounds__(256) void preprocess_u8_seg_kernel(const PrepSegP r
                      taps_needed(g.Win, Wr) > p.mw;
     if (cut && threadIdx.x == 0) atomicOr(p.status, 4u);
     const int flip = g.flip != 0;
-    const int y0 = blockIdx.y * p.TH, x0 = blockIdx.x * p.TW;
-    const int th = min(p.TH, p.Hout - y0), tw = min(p.TW, p.Wout - x0);
+    const Tile o = tile_of(p);
+    const int y0 = o.y0, x0 = o.x0, th = o.th, tw = o.tw;
     const int r0 = top + y0, q0 = left + x0;                 // < max(Hr, Hout), max(Wr, Wout): no overflow
     const int th_v = clampi(Hr - r0, 0, th), tw_v = clampi(Wr - q0, 0, tw);
     if (th_v > 0 && tw_v > 0) {
@@ -639,33 +657,106 @@ template <class F> bool pick_tile(PrepP& p, int in_chw, size_t* lds, F&& caps, b
     return false;
 }
 
+// ---- what the five entries share on the host.  `who` is the entry's name in every message. ----
+
+// The arguments every entry takes: B in (0, max_B], positive sizes (`sizes_ok`: the entry's own), an output dtype.  `image`: the
+// one image size {Hin, Win} of the plain entry, whose "too large" line covers it too.
+int check_args(const char* who, bool sizes_ok, int out_dtype, int B, int max_B, const int* image = nullptr) {
+    MV_CHECK_ARG(B > 0 && sizes_ok, "%s: bad sizes", who);
+    MV_CHECK_ARG(out_dtype == MV_F32 || out_dtype == MV_BF16, "%s: out_dtype must be MV_F32 or MV_BF16", who);
+    if (image)
+        MV_CHECK_ARG(B <= max_B && (long long)image[0] * image[1] * 3 < (1LL << 31), "%s: batch %d or image %dx%d too large", who, B,
+                     image[0], image[1]);
+    else
+        MV_CHECK_ARG(B <= max_B, "%s: batch %d too large", who, B);
+    return MV_OK;
+}
+
+int check_buffers(const char* who, std::initializer_list<const void*> buffers) {
+    for (const void* v : buffers)
+        if (!v) {
+            set_error("%s: null buffer", who);
+            return MV_E_UNSUPPORTED;
+        }
+    return MV_OK;
+}
+
+// Image i of a host record: positive sizes (`sizes_ok`: the record's other ones), fewer than 2^31 bytes, inside the x_bytes of x.
+int check_image(const char* who, int i, int Hin, int Win, bool sizes_ok, int64_t offset, int64_t x_bytes) {
+    MV_CHECK_ARG(Hin > 0 && Win > 0 && sizes_ok, "%s: image %d: bad sizes", who, i);
+    const long long img_bytes = (long long)Hin * Win * 3;
+    MV_CHECK_ARG(img_bytes < (1LL << 31), "%s: image %d: %dx%d too large", who, i, Hin, Win);
+    MV_CHECK_ARG(offset >= 0 && offset <= x_bytes - img_bytes, "%s: image %d: %lld bytes at offset %lld do not lie inside the buffer of %lld bytes",
+                 who, i, img_bytes, (long long)offset, (long long)x_bytes);
+    return MV_OK;
+}
+
+// The tap limit of an in_h x in_w -> out_h x out_w resize (`what`: "" or "box "), of image i or, i < 0, of the launch.  `tables`:
+// the pitches {mh, mw} of tables the caller brought, which obey the limit too and are named in the refusal.  *mh, *mw are
+// raised to what this resize needs: the pitches of its tables, or the taps the kernel will generate.
+int check_taps(const char* who, int i, const char* what, int in_h, int in_w, int out_h, int out_w, const int* tables, int* mh, int* mw) {
+    const int need_h = taps_needed(in_h, out_h), need_w = taps_needed(in_w, out_w);
+    const int pitch_h = tables ? tables[0] : need_h, pitch_w = tables ? tables[1] : need_w;
+    if (std::max(std::max(need_h, need_w), std::max(pitch_h, pitch_w)) > MV_PREPROCESS_MAX_TAPS) {
+        char image[32] = "", brought[48] = "";
+        if (i >= 0) snprintf(image, sizeof(image), "image %d: ", i);
+        if (tables) snprintf(brought, sizeof(brought), " (tables of %d x %d)", pitch_h, pitch_w);
+        set_error("%s: %s%s%dx%d -> %dx%d needs up to %d x %d taps%s; at most %d per axis (down-sampling by up to %.1f)", who, image, what,
+                  in_h, in_w, out_h, out_w, need_h, need_w, brought, MV_PREPROCESS_MAX_TAPS, (MV_PREPROCESS_MAX_TAPS - 1) / 2.0);
+        return MV_E_UNSUPPORTED;
+    }
+    *mh = std::max(*mh, pitch_h);
+    *mw = std::max(*mw, pitch_w);
+    return MV_OK;
+}
+
+// An output (the buffers from `first_out` on) may overlap neither an input nor another output; empty buffers are not there.
+struct Buffer {
+    const char* name;
+    const void* lo;
+    size_t len;
+};
+int check_disjoint(const char* who, std::initializer_list<Buffer> buffers, size_t first_out) {
+    const Buffer* v = buffers.begin();
+    for (size_t o = first_out; o < buffers.size(); ++o)
+        for (size_t i = 0; i < o; ++i) {
+            const uintptr_t a = (uintptr_t)v[i].lo, b = (uintptr_t)v[o].lo;
+            if (v[o].len && v[i].len && a < b + v[o].len && b < a + v[i].len) {
+                set_error("%s: %s and %s overlap", who, v[i].name, v[o].name);
+                return MV_E_UNSUPPORTED;
+            }
+        }
+    return MV_OK;
+}
+
 // The host records of the boxes and the mix entry, in full: image inside x, box non-empty and inside its image, taps within the
 // limit.  *mh, *mw: the most taps any box of the batch needs.
 int check_boxes(const char* who, const mv_preprocess_box* rec_host, int B, int64_t x_bytes, int Hout, int Wout, int* mh, int* mw) {
-    *mh = *mw = 0;
     for (int i = 0; i < B; ++i) {
         const mv_preprocess_box& g = rec_host[i];
-        MV_CHECK_ARG(g.Hin > 0 && g.Win > 0, "%s: image %d: bad sizes", who, i);
-        const long long img_bytes = (long long)g.Hin * g.Win * 3;
-        MV_CHECK_ARG(img_bytes < (1LL << 31), "%s: image %d: %dx%d too large", who, i, g.Hin, g.Win);
-        MV_CHECK_ARG(g.offset >= 0 && g.offset <= x_bytes - img_bytes,
-                     "%s: image %d: %lld bytes at offset %lld do not lie inside the buffer of %lld bytes", who, i, img_bytes,
-                     (long long)g.offset, (long long)x_bytes);
+        if (const int rc = check_image(who, i, g.Hin, g.Win, true, g.offset, x_bytes)) return rc;
         MV_CHECK_ARG(g.h > 0 && g.w > 0 && g.top >= 0 && g.left >= 0 && (long long)g.top + g.h <= g.Hin &&
                          (long long)g.left + g.w <= g.Win,
                      "%s: image %d: box %dx%d at (%d, %d) does not lie inside the image %dx%d", who, i, g.h, g.w, g.top, g.left,
                      g.Hin, g.Win);
-        const int need_h = taps_needed(g.h, Hout), need_w = taps_needed(g.w, Wout);
-        if (need_h > MV_PREPROCESS_MAX_TAPS || need_w > MV_PREPROCESS_MAX_TAPS) {
-            set_error("%s: image %d: box %dx%d -> %dx%d needs up to %d x %d taps; at most %d per axis (down-sampling by up to %.1f)",
-                      who, i, g.h, g.w, Hout, Wout, need_h, need_w, MV_PREPROCESS_MAX_TAPS, (MV_PREPROCESS_MAX_TAPS - 1) / 2.0);
-            return MV_E_UNSUPPORTED;
-        }
-        *mh = need_h > *mh ? need_h : *mh;
-        *mw = need_w > *mw ? need_w : *mw;
+        if (const int rc = check_taps(who, i, "box ", g.h, g.w, Hout, Wout, nullptr, mh, mw)) return rc;
     }
     return MV_OK;
 }
+
+// The parameters every kernel takes; tab_h / tab_w stay NULL where the filter is generated, Hin / Win are the plain entry's alone
+// (the record kernels fill them per image), the status word and the tile come from launch_tiles.
+PrepP prep_params(const void* x, void* y, const float* a, const float* b, int Hout, int Wout, int mh, int mw) {
+    PrepP p = {};
+    p.x = (const uint8_t*)x; p.y = y; p.a = a; p.b = b;
+    p.Hout = Hout; p.Wout = Wout; p.mh = mh; p.mw = mw;
+    return p;
+}
+
+// One resize of a launch, per axis: input extent -> full output extent (before any crop or window).
+struct Resize {
+    int rows_in, rows_out, cols_in, cols_out;
+};
 
 // launches KERNEL<in_chw, out_nhwc, out_dtype == MV_BF16> with ARG on (grid, 256 threads, lds, st) of the calling entry
 #define PREPROCESS_GO(KERNEL, ARG, CHW, NHWC, BF) hipLaunchKernelGGL((KERNEL<CHW, NHWC, BF>), grid, dim3(256), lds, st, ARG)
@@ -681,6 +772,41 @@ int check_boxes(const char* who, const mv_preprocess_box* rec_host, int B, int64
         }                                                                                                                     \
     } while (0)
 
+// The end of every entry.  One tile and one LDS size per launch: the staged rectangle is the largest any of the n resizes of the
+// launch needs per axis (resize(i), i < n; p.mh / p.mw hold the largest pitches), so one steeply down-sampled image shrinks the
+// tile -- and the occupancy -- of the whole launch.  Accepted: the result of an image does not depend on the tile it was computed
+// in.  `what` names what did not fit; `keep`: see pick_tile.  The grid is tiles x tiles x B images, and for extra_elems > 0
+// further z-slices behind the images whose workgroups stride over that many elements, about four per thread (the mix entry's
+// targets).  The status word is fetched LAST: it is the first touch of the device, everything before it is host work.  Then
+// launch(grid, lds, st), which is PREPROCESS_LAUNCH on the entry's kernel and parameters (p lives inside them).
+template <class ResizeOf, class Launch>
+int launch_tiles(const char* who, PrepP& p, int in_chw, int B, int n, ResizeOf&& resize, const char* what, bool keep, long long extra_elems,
+                 mv_stream_t stream, Launch&& launch) {
+    size_t lds = 0;
+    if (!pick_tile(p, in_chw, &lds, [&](int TH, int TW, int* rows, int* cols) {
+            *rows = *cols = 0;
+            for (int i = 0; i < n; ++i) {
+                const Resize g = resize(i);
+                *rows = std::max(*rows, span_cap(TH, g.rows_in, g.rows_out));
+                *cols = std::max(*cols, span_cap(TW, g.cols_in, g.cols_out));
+            }
+        }, keep)) {
+        set_error("%s: %s does not fit the LDS tile (%zu bytes for the smallest tile)", who, what, lds);
+        return MV_E_UNSUPPORTED;
+    }
+    const unsigned gx = (p.Wout + p.TW - 1) / p.TW, gy = (p.Hout + p.TH - 1) / p.TH;
+    const long long per_slice = (long long)gx * gy * 256 * 4;
+    const long long slices = extra_elems > 0 ? std::min<long long>((extra_elems + per_slice - 1) / per_slice, 65535 - B) : 0;
+    const dim3 grid(gx, gy, B + (unsigned)slices);
+    MV_CHECK_ARG(grid.y <= 65535, "%s: %d output rows are too many tiles", who, p.Hout);
+    p.status = device_status_word();
+    MV_CHECK_ARG(p.status != nullptr, "%s: the device status word is not available", who);
+    set_kernel_name(who);
+    launch(grid, lds, (hipStream_t)stream);
+    MV_LAUNCH_CHECK();
+    return MV_OK;
+}
+
 }  // namespace
 
 }  // namespace mv
@@ -692,178 +818,80 @@ extern "C" {
 int mv_preprocess_u8_fwd(const void* x, void* y, const void* tab_h, const void* tab_w, const float* a, const float* b, int B, int Hin,
                          int Win, int Hr, int Wr, int top, int left, int Hout, int Wout, int taps_h, int taps_w, int in_chw,
                          int out_dtype, int out_nhwc, mv_stream_t stream) {
-    MV_CHECK_ARG(B > 0 && Hin > 0 && Win > 0 && Hr > 0 && Wr > 0 && Hout > 0 && Wout > 0 && taps_h > 0 && taps_w > 0,
-                 "preprocess_u8: bad sizes");
-    MV_CHECK_ARG(out_dtype == MV_F32 || out_dtype == MV_BF16, "preprocess_u8: out_dtype must be MV_F32 or MV_BF16");
-    MV_CHECK_ARG(B <= 65535 && (long long)Hin * Win * 3 < (1LL << 31), "preprocess_u8: batch %d or image %dx%d too large", B, Hin, Win);
-    if (!x || !y || !tab_h || !tab_w || !a || !b) {
-        set_error("preprocess_u8: null buffer");
-        return MV_E_UNSUPPORTED;
-    }
+    const char* who = "preprocess_u8";
+    const int image[2] = {Hin, Win}, tables[2] = {taps_h, taps_w};
+    if (const int rc = check_args(who, Hin > 0 && Win > 0 && Hr > 0 && Wr > 0 && Hout > 0 && Wout > 0 && taps_h > 0 && taps_w > 0, out_dtype,
+                                  B, 65535, image))
+        return rc;
+    if (const int rc = check_buffers(who, {x, y, tab_h, tab_w, a, b})) return rc;
     if (top < 0 || left < 0 || (long long)top + Hout > Hr || (long long)left + Wout > Wr) {
         set_error("preprocess_u8: crop %dx%d at (%d, %d) does not lie inside the resized image %dx%d", Hout, Wout, top, left, Hr, Wr);
         return MV_E_UNSUPPORTED;
     }
-    const int need_h = taps_needed(Hin, Hr), need_w = taps_needed(Win, Wr);
-    if (taps_h > MV_PREPROCESS_MAX_TAPS || taps_w > MV_PREPROCESS_MAX_TAPS || need_h > MV_PREPROCESS_MAX_TAPS ||
-        need_w > MV_PREPROCESS_MAX_TAPS) {
-        set_error("preprocess_u8: %dx%d -> %dx%d needs up to %d x %d taps (tables of %d x %d); at most %d per axis (down-sampling by "
-                  "up to %.1f)", Hin, Win, Hr, Wr, need_h, need_w, taps_h, taps_w, MV_PREPROCESS_MAX_TAPS,
-                  (MV_PREPROCESS_MAX_TAPS - 1) / 2.0);
-        return MV_E_UNSUPPORTED;
-    }
-    const size_t in_bytes = (size_t)B * Hin * Win * 3, out_bytes = (size_t)B * 3 * Hout * Wout * dsize(out_dtype);
-    const uintptr_t xa = (uintptr_t)x, ya = (uintptr_t)y;
-    if (xa < ya + out_bytes && ya < xa + in_bytes) {
-        set_error("preprocess_u8: input and output overlap");
-        return MV_E_UNSUPPORTED;
-    }
-    unsigned* status = device_status_word();
-    MV_CHECK_ARG(status != nullptr, "preprocess_u8: the device status word is not available");
+    int mh = 0, mw = 0;
+    if (const int rc = check_taps(who, -1, "", Hin, Win, Hr, Wr, tables, &mh, &mw)) return rc;
+    if (const int rc = check_disjoint(who, {{"input", x, (size_t)B * Hin * Win * 3}, {"output", y, (size_t)B * 3 * Hout * Wout * dsize(out_dtype)}}, 1))
+        return rc;
 
-    PrepP p;
-    p.x = (const uint8_t*)x; p.y = y; p.tab_h = (const int*)tab_h; p.tab_w = (const int*)tab_w; p.a = a; p.b = b; p.status = status;
-    p.Hin = Hin; p.Win = Win; p.Hout = Hout; p.Wout = Wout; p.mh = taps_h; p.mw = taps_w;
-    size_t lds = 0;
-    if (!pick_tile(p, in_chw, &lds, [&](int TH, int TW, int* rows, int* cols) {
-            *rows = span_cap(TH, Hin, Hr);
-            *cols = span_cap(TW, Win, Wr);
-        })) {
-        set_error("preprocess_u8: %dx%d -> %dx%d does not fit the LDS tile (%zu bytes for the smallest tile)", Hin, Win, Hr, Wr, lds);
-        return MV_E_UNSUPPORTED;
-    }
-    const dim3 grid((Wout + p.TW - 1) / p.TW, (Hout + p.TH - 1) / p.TH, B);
-    MV_CHECK_ARG(grid.y <= 65535, "preprocess_u8: %d output rows are too many tiles", Hout);
-    hipStream_t st = (hipStream_t)stream;
-    set_kernel_name("preprocess_u8");
-    PREPROCESS_LAUNCH(preprocess_u8_kernel, p);
-    MV_LAUNCH_CHECK();
-    return MV_OK;
+    PrepP p = prep_params(x, y, a, b, Hout, Wout, mh, mw);
+    p.tab_h = (const int*)tab_h; p.tab_w = (const int*)tab_w; p.Hin = Hin; p.Win = Win;
+    char what[64];
+    snprintf(what, sizeof(what), "%dx%d -> %dx%d", Hin, Win, Hr, Wr);
+    return launch_tiles(who, p, in_chw, B, 1, [&](int) { return Resize{Hin, Hr, Win, Wr}; }, what, false, 0, stream,
+                        [&](dim3 grid, size_t lds, hipStream_t st) { PREPROCESS_LAUNCH(preprocess_u8_kernel, p); });
 }
 
 int mv_preprocess_u8_ragged_fwd(const void* x, int64_t x_bytes, void* y, const mv_preprocess_image* rec_host,
                                 const mv_preprocess_image* rec_dev, const void* tab, int64_t tab_words, const float* a,
                                 const float* b, int B, int Hout, int Wout, int in_chw, int out_dtype, int out_nhwc,
                                 mv_stream_t stream) {
-    MV_CHECK_ARG(B > 0 && Hout > 0 && Wout > 0 && x_bytes > 0 && tab_words > 0, "preprocess_u8_ragged: bad sizes");
-    MV_CHECK_ARG(out_dtype == MV_F32 || out_dtype == MV_BF16, "preprocess_u8_ragged: out_dtype must be MV_F32 or MV_BF16");
-    MV_CHECK_ARG(B <= 65535, "preprocess_u8_ragged: batch %d too large", B);
-    if (!x || !y || !rec_host || !rec_dev || !tab || !a || !b) {
-        set_error("preprocess_u8_ragged: null buffer");
-        return MV_E_UNSUPPORTED;
-    }
+    const char* who = "preprocess_u8_ragged";
+    if (const int rc = check_args(who, Hout > 0 && Wout > 0 && x_bytes > 0 && tab_words > 0, out_dtype, B, 65535)) return rc;
+    if (const int rc = check_buffers(who, {x, y, rec_host, rec_dev, tab, a, b})) return rc;
     int mh = 0, mw = 0;
     for (int i = 0; i < B; ++i) {
         const mv_preprocess_image& g = rec_host[i];
-        MV_CHECK_ARG(g.Hin > 0 && g.Win > 0 && g.Hr > 0 && g.Wr > 0 && g.mh > 0 && g.mw > 0, "preprocess_u8_ragged: image %d: bad sizes", i);
-        const long long img_bytes = (long long)g.Hin * g.Win * 3;
-        MV_CHECK_ARG(img_bytes < (1LL << 31), "preprocess_u8_ragged: image %d: %dx%d too large", i, g.Hin, g.Win);
-        MV_CHECK_ARG(g.offset >= 0 && g.offset <= x_bytes - img_bytes,
-                     "preprocess_u8_ragged: image %d: %lld bytes at offset %lld do not lie inside the buffer of %lld bytes", i, img_bytes,
-                     (long long)g.offset, (long long)x_bytes);
+        if (const int rc = check_image(who, i, g.Hin, g.Win, g.Hr > 0 && g.Wr > 0 && g.mh > 0 && g.mw > 0, g.offset, x_bytes)) return rc;
         if (g.top < 0 || g.left < 0 || (long long)g.top + Hout > g.Hr || (long long)g.left + Wout > g.Wr) {
             set_error("preprocess_u8_ragged: image %d: crop %dx%d at (%d, %d) does not lie inside the resized image %dx%d", i, Hout, Wout,
                       g.top, g.left, g.Hr, g.Wr);
             return MV_E_UNSUPPORTED;
         }
-        const int need_h = taps_needed(g.Hin, g.Hr), need_w = taps_needed(g.Win, g.Wr);
-        if (g.mh > MV_PREPROCESS_MAX_TAPS || g.mw > MV_PREPROCESS_MAX_TAPS || need_h > MV_PREPROCESS_MAX_TAPS ||
-            need_w > MV_PREPROCESS_MAX_TAPS) {
-            set_error("preprocess_u8_ragged: image %d: %dx%d -> %dx%d needs up to %d x %d taps (tables of %d x %d); at most %d per axis "
-                      "(down-sampling by up to %.1f)", i, g.Hin, g.Win, g.Hr, g.Wr, need_h, need_w, g.mh, g.mw, MV_PREPROCESS_MAX_TAPS,
-                      (MV_PREPROCESS_MAX_TAPS - 1) / 2.0);
-            return MV_E_UNSUPPORTED;
-        }
+        const int tables[2] = {g.mh, g.mw};
+        if (const int rc = check_taps(who, i, "", g.Hin, g.Win, g.Hr, g.Wr, tables, &mh, &mw)) return rc;
         MV_CHECK_ARG(g.tab_h >= 0 && g.tab_w >= 0 && (long long)g.tab_h + (long long)Hout * (2 + g.mh) <= tab_words &&
                          (long long)g.tab_w + (long long)Wout * (2 + g.mw) <= tab_words,
                      "preprocess_u8_ragged: image %d: tables at words %d and %d do not lie inside the table buffer of %lld words", i,
                      g.tab_h, g.tab_w, (long long)tab_words);
-        mh = g.mh > mh ? g.mh : mh;
-        mw = g.mw > mw ? g.mw : mw;
     }
-    const size_t out_bytes = (size_t)B * 3 * Hout * Wout * dsize(out_dtype);
-    const uintptr_t xa = (uintptr_t)x, ya = (uintptr_t)y;
-    if (xa < ya + out_bytes && ya < xa + (size_t)x_bytes) {
-        set_error("preprocess_u8_ragged: input and output overlap");
-        return MV_E_UNSUPPORTED;
-    }
-    unsigned* status = device_status_word();
-    MV_CHECK_ARG(status != nullptr, "preprocess_u8_ragged: the device status word is not available");
+    if (const int rc = check_disjoint(who, {{"input", x, (size_t)x_bytes}, {"output", y, (size_t)B * 3 * Hout * Wout * dsize(out_dtype)}}, 1))
+        return rc;
 
-    // One tile and one LDS size per launch: the rectangle and the table pitches are the largest any image of the batch needs, per
-    // axis, so one steeply down-sampled image shrinks the tile (and the occupancy) of the whole launch.  Accepted: the result of an
-    // image does not depend on the tile it was computed in.
     PrepRaggedP r;
-    PrepP& p = r.p;
-    p.x = (const uint8_t*)x; p.y = y; p.tab_h = (const int*)tab; p.tab_w = nullptr; p.a = a; p.b = b; p.status = status;
-    p.Hin = 0; p.Win = 0; p.Hout = Hout; p.Wout = Wout; p.mh = mh; p.mw = mw;
+    r.p = prep_params(x, y, a, b, Hout, Wout, mh, mw);
+    r.p.tab_h = (const int*)tab;
     r.rec = rec_dev; r.x_bytes = x_bytes; r.tab_words = tab_words;
-    size_t lds = 0;
-    if (!pick_tile(p, in_chw, &lds, [&](int TH, int TW, int* rows, int* cols) {
-            *rows = *cols = 0;
-            for (int i = 0; i < B; ++i) {
-                const mv_preprocess_image& g = rec_host[i];
-                *rows = std::max(*rows, span_cap(TH, g.Hin, g.Hr));
-                *cols = std::max(*cols, span_cap(TW, g.Win, g.Wr));
-            }
-        })) {
-        set_error("preprocess_u8_ragged: the batch does not fit the LDS tile (%zu bytes for the smallest tile)", lds);
-        return MV_E_UNSUPPORTED;
-    }
-    const dim3 grid((Wout + p.TW - 1) / p.TW, (Hout + p.TH - 1) / p.TH, B);
-    MV_CHECK_ARG(grid.y <= 65535, "preprocess_u8_ragged: %d output rows are too many tiles", Hout);
-    hipStream_t st = (hipStream_t)stream;
-    set_kernel_name("preprocess_u8_ragged");
-    PREPROCESS_LAUNCH(preprocess_u8_ragged_kernel, r);
-    MV_LAUNCH_CHECK();
-    return MV_OK;
+    return launch_tiles(who, r.p, in_chw, B, B, [&](int i) { return Resize{rec_host[i].Hin, rec_host[i].Hr, rec_host[i].Win, rec_host[i].Wr}; },
+                        "the batch", false, 0, stream,
+                        [&](dim3 grid, size_t lds, hipStream_t st) { PREPROCESS_LAUNCH(preprocess_u8_ragged_kernel, r); });
 }
 
 int mv_preprocess_u8_boxes_fwd(const void* x, int64_t x_bytes, void* y, const mv_preprocess_box* rec_host,
                                const mv_preprocess_box* rec_dev, const float* a, const float* b, int B, int Hout, int Wout,
                                int in_chw, int out_dtype, int out_nhwc, mv_stream_t stream) {
-    MV_CHECK_ARG(B > 0 && Hout > 0 && Wout > 0 && x_bytes > 0, "preprocess_u8_boxes: bad sizes");
-    MV_CHECK_ARG(out_dtype == MV_F32 || out_dtype == MV_BF16, "preprocess_u8_boxes: out_dtype must be MV_F32 or MV_BF16");
-    MV_CHECK_ARG(B <= 65535, "preprocess_u8_boxes: batch %d too large", B);
-    if (!x || !y || !rec_host || !rec_dev || !a || !b) {
-        set_error("preprocess_u8_boxes: null buffer");
-        return MV_E_UNSUPPORTED;
-    }
+    const char* who = "preprocess_u8_boxes";
+    if (const int rc = check_args(who, Hout > 0 && Wout > 0 && x_bytes > 0, out_dtype, B, 65535)) return rc;
+    if (const int rc = check_buffers(who, {x, y, rec_host, rec_dev, a, b})) return rc;
     int mh = 0, mw = 0;
-    if (const int rc = check_boxes("preprocess_u8_boxes", rec_host, B, x_bytes, Hout, Wout, &mh, &mw)) return rc;
-    const size_t out_bytes = (size_t)B * 3 * Hout * Wout * dsize(out_dtype);
-    const uintptr_t xa = (uintptr_t)x, ya = (uintptr_t)y;
-    if (xa < ya + out_bytes && ya < xa + (size_t)x_bytes) {
-        set_error("preprocess_u8_boxes: input and output overlap");
-        return MV_E_UNSUPPORTED;
-    }
-    unsigned* status = device_status_word();
-    MV_CHECK_ARG(status != nullptr, "preprocess_u8_boxes: the device status word is not available");
+    if (const int rc = check_boxes(who, rec_host, B, x_bytes, Hout, Wout, &mh, &mw)) return rc;
+    if (const int rc = check_disjoint(who, {{"input", x, (size_t)x_bytes}, {"output", y, (size_t)B * 3 * Hout * Wout * dsize(out_dtype)}}, 1))
+        return rc;
 
-    // One tile and one LDS size per launch, as in the ragged entry: the largest spans and tap counts any box of the batch needs.
     PrepBoxesP r;
-    PrepP& p = r.p;
-    p.x = (const uint8_t*)x; p.y = y; p.tab_h = nullptr; p.tab_w = nullptr; p.a = a; p.b = b; p.status = status;
-    p.Hin = 0; p.Win = 0; p.Hout = Hout; p.Wout = Wout; p.mh = mh; p.mw = mw;
+    r.p = prep_params(x, y, a, b, Hout, Wout, mh, mw);
     r.rec = rec_dev; r.x_bytes = x_bytes;
-    size_t lds = 0;
-    if (!pick_tile(p, in_chw, &lds, [&](int TH, int TW, int* rows, int* cols) {
-            *rows = *cols = 0;
-            for (int i = 0; i < B; ++i) {
-                *rows = std::max(*rows, span_cap(TH, rec_host[i].h, Hout));
-                *cols = std::max(*cols, span_cap(TW, rec_host[i].w, Wout));
-            }
-        })) {
-        set_error("preprocess_u8_boxes: the batch does not fit the LDS tile (%zu bytes for the smallest tile)", lds);
-        return MV_E_UNSUPPORTED;
-    }
-    const dim3 grid((Wout + p.TW - 1) / p.TW, (Hout + p.TH - 1) / p.TH, B);
-    MV_CHECK_ARG(grid.y <= 65535, "preprocess_u8_boxes: %d output rows are too many tiles", Hout);
-    hipStream_t st = (hipStream_t)stream;
-    set_kernel_name("preprocess_u8_boxes");
-    PREPROCESS_LAUNCH(preprocess_u8_boxes_kernel, r);
-    MV_LAUNCH_CHECK();
-    return MV_OK;
+    return launch_tiles(who, r.p, in_chw, B, B, [&](int i) { return Resize{rec_host[i].h, Hout, rec_host[i].w, Wout}; }, "the batch", false, 0,
+                        stream, [&](dim3 grid, size_t lds, hipStream_t st) { PREPROCESS_LAUNCH(preprocess_u8_boxes_kernel, r); });
 }
 
 int mv_preprocess_u8_mix_fwd(const void* x, int64_t x_bytes, void* y, const mv_preprocess_box* rec_host,
@@ -871,19 +899,15 @@ int mv_preprocess_u8_mix_fwd(const void* x, int64_t x_bytes, void* y, const mv_p
                              const float* a, const float* b, const int32_t* labels_host, const int32_t* labels_dev, float* targets,
                              int K, float on, float off, int B, int Hout, int Wout, int in_chw, int out_dtype, int out_nhwc,
                              mv_stream_t stream) {
-    MV_CHECK_ARG(B > 0 && Hout > 0 && Wout > 0 && x_bytes > 0, "preprocess_u8_mix: bad sizes");
-    MV_CHECK_ARG(out_dtype == MV_F32 || out_dtype == MV_BF16, "preprocess_u8_mix: out_dtype must be MV_F32 or MV_BF16");
-    MV_CHECK_ARG(B <= 32767, "preprocess_u8_mix: batch %d too large", B);
-    if (!x || !y || !rec_host || !rec_dev || !mix_host || !mix_dev || !a || !b) {
-        set_error("preprocess_u8_mix: null buffer");
-        return MV_E_UNSUPPORTED;
-    }
+    const char* who = "preprocess_u8_mix";
+    if (const int rc = check_args(who, Hout > 0 && Wout > 0 && x_bytes > 0, out_dtype, B, 32767)) return rc;
+    if (const int rc = check_buffers(who, {x, y, rec_host, rec_dev, mix_host, mix_dev, a, b})) return rc;
     MV_CHECK_ARG((labels_dev != nullptr) == (targets != nullptr), "preprocess_u8_mix: labels and targets go together, got %s without %s",
                  labels_dev ? "labels" : "targets", labels_dev ? "targets" : "labels");
     MV_CHECK_ARG(!labels_host || labels_dev, "preprocess_u8_mix: a host copy of the labels without the device labels");
     MV_CHECK_ARG(!labels_dev || (K > 0 && (long long)B * K < (1LL << 31)), "preprocess_u8_mix: %d classes for %d images", K, B);
     int mh = 0, mw = 0;
-    if (const int rc = check_boxes("preprocess_u8_mix", rec_host, B, x_bytes, Hout, Wout, &mh, &mw)) return rc;
+    if (const int rc = check_boxes(who, rec_host, B, x_bytes, Hout, Wout, &mh, &mw)) return rc;
     auto unit = [](float v) { return std::isfinite(v) && v >= 0.f && v <= 1.f; };
     auto inside = [&](int y0, int x0, int y1, int x1) {
         return y0 >= 0 && y0 <= Hout && y1 >= 0 && y1 <= Hout && x0 >= 0 && x0 <= Wout && x1 >= 0 && x1 <= Wout;
@@ -905,75 +929,37 @@ int mv_preprocess_u8_mix_fwd(const void* x, int64_t x_bytes, void* y, const mv_p
                      "preprocess_u8_mix: image %d: label %d does not lie in [0, %d)", i, labels_host ? labels_host[i] : 0, K);
         keep |= m.partner != i;
     }
-    // an output may overlap neither the input nor the other output
-    const uintptr_t lo[3] = {(uintptr_t)x, (uintptr_t)y, (uintptr_t)targets};
-    const size_t len[3] = {(size_t)x_bytes, (size_t)B * 3 * Hout * Wout * dsize(out_dtype), targets ? (size_t)B * K * 4 : 0};
-    static const char* const names[3] = {"images", "output", "targets"};
-    for (int o = 1; o < 3; ++o)
-        for (int i = 0; i < o; ++i)
-            if (len[o] && len[i] && lo[i] < lo[o] + len[o] && lo[o] < lo[i] + len[i]) {
-                set_error("preprocess_u8_mix: %s and %s overlap", names[i], names[o]);
-                return MV_E_UNSUPPORTED;
-            }
+    if (const int rc = check_disjoint(who, {{"images", x, (size_t)x_bytes}, {"output", y, (size_t)B * 3 * Hout * Wout * dsize(out_dtype)},
+                                            {"targets", targets, targets ? (size_t)B * K * 4 : 0}}, 1))
+        return rc;
 
-    // One tile and one LDS size per launch, as in the boxes entry; with a partner anywhere in the batch the tile also keeps the
-    // partner's results (TH x 3 x TW fp32) while its own window is staged.
+    // with a partner anywhere in the batch the tile also keeps the partner's results (TH x 3 x TW fp32) while its own window is staged
     PrepMixP r;
-    PrepP& p = r.p;
-    p.x = (const uint8_t*)x; p.y = y; p.tab_h = nullptr; p.tab_w = nullptr; p.a = a; p.b = b; p.status = nullptr;
-    p.Hin = 0; p.Win = 0; p.Hout = Hout; p.Wout = Wout; p.mh = mh; p.mw = mw;
+    r.p = prep_params(x, y, a, b, Hout, Wout, mh, mw);
     r.rec = rec_dev; r.mix = mix_dev; r.x_bytes = x_bytes; r.labels = labels_dev; r.targets = targets;
     r.B = B; r.K = K; r.keep = keep; r.on = on; r.off = off;
-    size_t lds = 0;
-    if (!pick_tile(p, in_chw, &lds, [&](int TH, int TW, int* rows, int* cols) {
-            *rows = *cols = 0;
-            for (int i = 0; i < B; ++i) {
-                *rows = std::max(*rows, span_cap(TH, rec_host[i].h, Hout));
-                *cols = std::max(*cols, span_cap(TW, rec_host[i].w, Wout));
-            }
-        }, keep)) {
-        set_error("preprocess_u8_mix: the batch does not fit the LDS tile (%zu bytes for the smallest tile)", lds);
-        return MV_E_UNSUPPORTED;
-    }
-    // target workgroups: whole z-slices of the image grid behind the B images, about four elements per thread, grid-stride
-    const long long per_slice = (long long)((Wout + p.TW - 1) / p.TW) * ((Hout + p.TH - 1) / p.TH) * 256 * 4;
-    const long long slices = targets ? std::min<long long>(((long long)B * K + per_slice - 1) / per_slice, 65535 - B) : 0;
-    const dim3 grid((Wout + p.TW - 1) / p.TW, (Hout + p.TH - 1) / p.TH, B + (unsigned)slices);
-    MV_CHECK_ARG(grid.y <= 65535, "preprocess_u8_mix: %d output rows are too many tiles", Hout);
-    p.status = device_status_word();                         // the first touch of the device: everything above is host work
-    MV_CHECK_ARG(p.status != nullptr, "preprocess_u8_mix: the device status word is not available");
-    hipStream_t st = (hipStream_t)stream;
-    set_kernel_name("preprocess_u8_mix");
-    PREPROCESS_LAUNCH(preprocess_u8_mix_kernel, r);
-    MV_LAUNCH_CHECK();
-    return MV_OK;
+    return launch_tiles(who, r.p, in_chw, B, B, [&](int i) { return Resize{rec_host[i].h, Hout, rec_host[i].w, Wout}; }, "the batch", keep,
+                        targets ? (long long)B * K : 0, stream,
+                        [&](dim3 grid, size_t lds, hipStream_t st) { PREPROCESS_LAUNCH(preprocess_u8_mix_kernel, r); });
 }
 
 int mv_preprocess_u8_seg_fwd(const void* x, int64_t x_bytes, const void* m, int64_t m_bytes, void* y, int32_t* labels,
                              const mv_preprocess_seg* rec_host, const mv_preprocess_seg* rec_dev, const float* a, const float* b,
                              int B, int Hout, int Wout, int image_fill, int mask_fill, int in_chw, int out_dtype, int out_nhwc,
                              mv_stream_t stream) {
-    MV_CHECK_ARG(B > 0 && Hout > 0 && Wout > 0 && x_bytes > 0, "preprocess_u8_seg: bad sizes");
-    MV_CHECK_ARG(out_dtype == MV_F32 || out_dtype == MV_BF16, "preprocess_u8_seg: out_dtype must be MV_F32 or MV_BF16");
-    MV_CHECK_ARG(B <= 65535, "preprocess_u8_seg: batch %d too large", B);
+    const char* who = "preprocess_u8_seg";
+    if (const int rc = check_args(who, Hout > 0 && Wout > 0 && x_bytes > 0, out_dtype, B, 65535)) return rc;
     MV_CHECK_ARG((m != nullptr) == (labels != nullptr), "preprocess_u8_seg: masks and labels go together, got %s without %s",
                  m ? "masks" : "labels", m ? "labels" : "masks");
     MV_CHECK_ARG(!m || m_bytes > 0, "preprocess_u8_seg: bad sizes");
     MV_CHECK_ARG(image_fill >= 0 && image_fill <= 255 && mask_fill >= 0 && mask_fill <= 255,
                  "preprocess_u8_seg: image_fill %d and mask_fill %d must lie in [0, 255]", image_fill, mask_fill);
-    if (!x || !y || !rec_host || !rec_dev || !a || !b) {
-        set_error("preprocess_u8_seg: null buffer");
-        return MV_E_UNSUPPORTED;
-    }
+    if (const int rc = check_buffers(who, {x, y, rec_host, rec_dev, a, b})) return rc;
     int mh = 0, mw = 0;
     for (int i = 0; i < B; ++i) {
         const mv_preprocess_seg& g = rec_host[i];
-        MV_CHECK_ARG(g.Hin > 0 && g.Win > 0 && g.Hr > 0 && g.Wr > 0, "preprocess_u8_seg: image %d: bad sizes", i);
+        if (const int rc = check_image(who, i, g.Hin, g.Win, g.Hr > 0 && g.Wr > 0, g.offset, x_bytes)) return rc;
         const long long px = (long long)g.Hin * g.Win;
-        MV_CHECK_ARG(px * 3 < (1LL << 31), "preprocess_u8_seg: image %d: %dx%d too large", i, g.Hin, g.Win);
-        MV_CHECK_ARG(g.offset >= 0 && g.offset <= x_bytes - px * 3,
-                     "preprocess_u8_seg: image %d: %lld bytes at offset %lld do not lie inside the buffer of %lld bytes", i, px * 3,
-                     (long long)g.offset, (long long)x_bytes);
         MV_CHECK_ARG(!m || (g.mask_offset >= 0 && g.mask_offset <= m_bytes - px),
                      "preprocess_u8_seg: image %d: mask of %lld bytes at offset %lld does not lie inside the buffer of %lld bytes", i, px,
                      (long long)g.mask_offset, (long long)m_bytes);
@@ -981,54 +967,20 @@ int mv_preprocess_u8_seg_fwd(const void* x, int64_t x_bytes, const void* m, int6
         MV_CHECK_ARG(g.top >= 0 && g.left >= 0 && (long long)g.top + Hout <= Hp && (long long)g.left + Wout <= Wp,
                      "preprocess_u8_seg: image %d: window %dx%d at (%d, %d) does not lie inside the padded image %dx%d", i, Hout, Wout,
                      g.top, g.left, Hp, Wp);
-        const int need_h = taps_needed(g.Hin, g.Hr), need_w = taps_needed(g.Win, g.Wr);
-        if (need_h > MV_PREPROCESS_MAX_TAPS || need_w > MV_PREPROCESS_MAX_TAPS) {
-            set_error("preprocess_u8_seg: image %d: %dx%d -> %dx%d needs up to %d x %d taps; at most %d per axis (down-sampling by up "
-                      "to %.1f)", i, g.Hin, g.Win, g.Hr, g.Wr, need_h, need_w, MV_PREPROCESS_MAX_TAPS, (MV_PREPROCESS_MAX_TAPS - 1) / 2.0);
-            return MV_E_UNSUPPORTED;
-        }
-        mh = need_h > mh ? need_h : mh;
-        mw = need_w > mw ? need_w : mw;
+        if (const int rc = check_taps(who, i, "", g.Hin, g.Win, g.Hr, g.Wr, nullptr, &mh, &mw)) return rc;
     }
-    // an output may overlap neither an input nor the other output (x and m are only read)
-    const size_t px_out = (size_t)B * Hout * Wout;
-    const uintptr_t lo[4] = {(uintptr_t)x, (uintptr_t)m, (uintptr_t)y, (uintptr_t)labels};
-    const size_t len[4] = {(size_t)x_bytes, m ? (size_t)m_bytes : 0, px_out * 3 * dsize(out_dtype), labels ? px_out * 4 : 0};
-    static const char* const names[4] = {"images", "masks", "output", "labels"};
-    for (int o = 2; o < 4; ++o)
-        for (int i = 0; i < o; ++i)
-            if (len[o] && len[i] && lo[i] < lo[o] + len[o] && lo[o] < lo[i] + len[i]) {
-                set_error("preprocess_u8_seg: %s and %s overlap", names[i], names[o]);
-                return MV_E_UNSUPPORTED;
-            }
+    const size_t px_out = (size_t)B * Hout * Wout;       // x and m are only read
+    if (const int rc = check_disjoint(who, {{"images", x, (size_t)x_bytes}, {"masks", m, m ? (size_t)m_bytes : 0},
+                                            {"output", y, px_out * 3 * dsize(out_dtype)}, {"labels", labels, labels ? px_out * 4 : 0}}, 2))
+        return rc;
 
-    // One tile and one LDS size per launch, as in the ragged entry: the largest spans and tap counts any resize of the batch needs.
     PrepSegP r;
-    PrepP& p = r.p;
-    p.x = (const uint8_t*)x; p.y = y; p.tab_h = nullptr; p.tab_w = nullptr; p.a = a; p.b = b; p.status = nullptr;
-    p.Hin = 0; p.Win = 0; p.Hout = Hout; p.Wout = Wout; p.mh = mh; p.mw = mw;
+    r.p = prep_params(x, y, a, b, Hout, Wout, mh, mw);
     r.rec = rec_dev; r.m = (const uint8_t*)m; r.labels = labels; r.x_bytes = x_bytes; r.m_bytes = m ? m_bytes : 0;
     r.image_fill = image_fill; r.mask_fill = mask_fill;
-    size_t lds = 0;
-    if (!pick_tile(p, in_chw, &lds, [&](int TH, int TW, int* rows, int* cols) {
-            *rows = *cols = 0;
-            for (int i = 0; i < B; ++i) {
-                *rows = std::max(*rows, span_cap(TH, rec_host[i].Hin, rec_host[i].Hr));
-                *cols = std::max(*cols, span_cap(TW, rec_host[i].Win, rec_host[i].Wr));
-            }
-        })) {
-        set_error("preprocess_u8_seg: the batch does not fit the LDS tile (%zu bytes for the smallest tile)", lds);
-        return MV_E_UNSUPPORTED;
-    }
-    const dim3 grid((Wout + p.TW - 1) / p.TW, (Hout + p.TH - 1) / p.TH, B);
-    MV_CHECK_ARG(grid.y <= 65535, "preprocess_u8_seg: %d output rows are too many tiles", Hout);
-    p.status = device_status_word();                         // the first touch of the device: everything above is host work
-    MV_CHECK_ARG(p.status != nullptr, "preprocess_u8_seg: the device status word is not available");
-    hipStream_t st = (hipStream_t)stream;
-    set_kernel_name("preprocess_u8_seg");
-    PREPROCESS_LAUNCH(preprocess_u8_seg_kernel, r);
-    MV_LAUNCH_CHECK();
-    return MV_OK;
+    return launch_tiles(who, r.p, in_chw, B, B, [&](int i) { return Resize{rec_host[i].Hin, rec_host[i].Hr, rec_host[i].Win, rec_host[i].Wr}; },
+                        "the batch", false, 0, stream,
+                        [&](dim3 grid, size_t lds, hipStream_t st) { PREPROCESS_LAUNCH(preprocess_u8_seg_kernel, r); });
 }
 
 }  // extern "C"

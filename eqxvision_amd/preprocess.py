@@ -45,6 +45,7 @@ offer one; `resize_crop_normalize(layout="nhwc")` returns a plain tensor for oth
 from __future__ import annotations
 
 import functools
+from typing import NamedTuple
 
 import numpy as np
 import torch
@@ -191,6 +192,87 @@ def _check_output(dtype, layout):
         raise ValueError(f"preprocess: layout must be 'nchw' or 'nhwc', got {layout!r}")
 
 
+# ---- what the record calls share on the host: intake, refusals, the trip to the device ------------------------------------------
+
+class _Intake(NamedTuple):
+    """Any accepted form of input.  listed: a list of images, else one array `x`; batched: False for one image without the batch
+    axis; sizes: [(Hin, Win)] per image; x: what `_one_buffer` uploads."""
+    listed: bool
+    batched: bool
+    chw: bool
+    sizes: list
+    x: object
+
+
+def _intake(images_u8, channels_last) -> _Intake:
+    if isinstance(images_u8, (list, tuple)):
+        chw, sizes = _check_list(images_u8, channels_last)
+        return _Intake(True, True, chw, sizes, images_u8)
+    x, batched, chw, hin, win = _check_input(images_u8, channels_last)
+    sizes = [(hin, win)] * (int(x.shape[0]) if batched else 1)
+    if len(sizes) == 0:
+        raise ValueError("preprocess: the batch of images is empty")
+    return _Intake(False, batched, chw, sizes, x)
+
+
+def _refuse_recording(who, what_belongs, advice=""):
+    """The geometry of a record call belongs to that call: inside a `filter_jit` recording it is refused."""
+    if getattr(_act_tls, "keep", None) is not None:
+        raise ValueError(f"preprocess: {who} cannot be recorded by filter_jit: its {what_belongs} belong to this one call, and a "
+                         f"replay would apply them to other images; preprocess outside the recorded function{advice}")
+
+
+def _rows_of_one(v, width):
+    """A per-image argument of an un-batched image as a batch of one: a scalar (`width` 0) becomes [1], a row of `width` numbers
+    [1, width]; None and an argument that already has its batch axis stay."""
+    if v is None:
+        return None
+    a = np.asarray(v)
+    return a.reshape(-1) if width == 0 else (a.reshape(1, -1) if a.ndim == 1 else a)
+
+
+def _int_rows(v, B, width, what, fields):
+    a = np.asarray(v)
+    if a.dtype.kind not in "iu" or a.shape != (B, width):
+        raise ValueError(f"preprocess: {what} must be integers [{B}, {width}] of {fields} per image, got {a.dtype} {tuple(a.shape)}")
+    return a
+
+
+def _flags(flip, B):
+    fl = np.zeros(B, bool) if flip is None else np.asarray(flip)
+    if fl.shape != (B,):
+        raise ValueError(f"preprocess: flip must hold one flag per image ({B}), got shape {tuple(fl.shape)}")
+    return fl
+
+
+def _pair(v, what):
+    hw = (int(v), int(v)) if isinstance(v, (int, np.integer)) else tuple(int(s) for s in v)
+    if len(hw) != 2 or hw[0] < 1 or hw[1] < 1:
+        raise ValueError(f"preprocess: {what} {v!r} must be a positive int or (height, width)")
+    return hw
+
+
+def _affine_on_device(mean, std):
+    affine(mean, std)                                        # validates before the device is touched
+    return _device_affine(mean, std)
+
+
+def _one_buffer(v):
+    """A list -> `pack_images` (which packs any uint8 arrays, planes included); an array -> itself on the device, contiguous."""
+    if isinstance(v, (list, tuple)):
+        return pack_images(v)
+    t = v if isinstance(v, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(v))
+    return t.to(device(), non_blocking=True).contiguous()
+
+
+def _records_to_device(rec):
+    return torch.from_numpy(rec.view(np.uint8)).to(device())
+
+
+def _new_output(B, h, w, dtype, layout):
+    return empty((B, 3, h, w) if layout == "nchw" else (B, h, w, 3), TORCH_DT[dtype])
+
+
 # ---- batches of differently sized images: a list of images -> mv_preprocess_u8_ragged_fwd, one launch ----------------------------
 
 # `mv_preprocess_image` of include/eqxvision_amd.h, 48 bytes
@@ -301,19 +383,15 @@ def pack_images(images) -> torch.Tensor:
 
 
 def _ragged(images, resized_hw, crop_box, mean, std, dtype, layout, channels_last):
-    if getattr(_act_tls, "keep", None) is not None:
-        raise ValueError("preprocess: a list of differently sized images cannot be recorded by filter_jit: its sizes and offsets "
-                         "belong to this one call, and a replay would apply them to other images; preprocess outside the "
-                         "recorded function, or give one array of equally sized images")
+    _refuse_recording("a list of differently sized images", "sizes and offsets", ", or give one array of equally sized images")
     chw, sizes = _check_list(images, channels_last)
     _check_output(dtype, layout)
     rec, tables, (hout, wout) = ragged_plan(sizes, resized_hw, crop_box)
-    affine(mean, std)                                        # validates before the device is touched
-    a, b = _device_affine(mean, std)
-    x = pack_images(images)
-    tab, rec_dev = torch.from_numpy(tables).to(device()), torch.from_numpy(rec.view(np.uint8)).to(device())
+    a, b = _affine_on_device(mean, std)
+    x = _one_buffer(images)
+    tab, rec_dev = torch.from_numpy(tables).to(device()), _records_to_device(rec)
     B = len(images)
-    y = empty((B, 3, hout, wout) if layout == "nchw" else (B, hout, wout, 3), TORCH_DT[dtype])
+    y = _new_output(B, hout, wout, dtype, layout)
     _lib.call("mv_preprocess_u8_ragged_fwd", x.data_ptr(), x.numel(), y.data_ptr(), rec.ctypes.data, rec_dev.data_ptr(),
               tab.data_ptr(), tab.numel(), a.data_ptr(), b.data_ptr(), B, hout, wout, int(chw), DT[dtype], int(layout == "nhwc"),
               stream_ptr())
@@ -339,10 +417,9 @@ def resize_crop_normalize(images_u8, resized_hw, crop_box, mean=IMAGENET_MEAN, s
     affine(mean, std)                                        # validates before the device is touched
     tab_h, tab_w, mh, mw = _device_tables(hin, win, hr, wr, top, left, hout, wout)
     a, b = _device_affine(mean, std)
-    t = x if isinstance(x, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(x))
-    t = t.to(device(), non_blocking=True).contiguous()
+    t = _one_buffer(x)
     B = t.shape[0] if batched else 1
-    y = empty((B, 3, hout, wout) if layout == "nchw" else (B, hout, wout, 3), TORCH_DT[dtype])
+    y = _new_output(B, hout, wout, dtype, layout)
     _lib.call("mv_preprocess_u8_fwd", t.data_ptr(), y.data_ptr(), tab_h.data_ptr(), tab_w.data_ptr(), a.data_ptr(), b.data_ptr(),
               B, hin, win, hr, wr, top, left, hout, wout, mh, mw, int(chw), DT[dtype], int(layout == "nhwc"), stream_ptr())
     keep = getattr(_act_tls, "keep", None)
@@ -429,16 +506,8 @@ def boxes_plan(sizes, boxes, flip, size):
     [B, 4] of (top, left, h, w), `flip` None or [B].  Returns (records, (Hout, Wout)), `records` a BOX array [B]; every refusal is
     a ValueError that names the image."""
     B = len(sizes)
-    hout, wout = (int(size), int(size)) if isinstance(size, (int, np.integer)) else (int(size[0]), int(size[1]))
-    if hout < 1 or wout < 1:
-        raise ValueError(f"preprocess: output size {(hout, wout)} must be positive")
-    bx = np.asarray(boxes)
-    if bx.dtype.kind not in "iu" or bx.shape != (B, 4):
-        raise ValueError(f"preprocess: boxes must be integers [{B}, 4] of (top, left, h, w), one box per image, got "
-                         f"{bx.dtype} {tuple(bx.shape)}")
-    fl = np.zeros(B, bool) if flip is None else np.asarray(flip)
-    if fl.shape != (B,):
-        raise ValueError(f"preprocess: flip must hold one flag per image ({B}), got shape {tuple(fl.shape)}")
+    hout, wout = _pair(size, "output size")
+    bx, fl = _int_rows(boxes, B, 4, "boxes", "(top, left, h, w), one box"), _flags(flip, B)
     rec = np.zeros(B, BOX)
     offset = 0
     for i, (hin, win) in enumerate(sizes):
@@ -462,36 +531,19 @@ def crop_resize_normalize(images_u8, boxes, size, flip=None, mean=IMAGENET_MEAN,
     `pack_images`); numpy or torch, host or device.  One launch of `mv_preprocess_u8_boxes_fwd` on the current stream for every
     form: the kernel generates the filter of each box itself, so a fresh random box per image and step costs one 40-byte record.
     The call cannot be recorded by `filter_jit`: the boxes belong to this one call."""
-    if getattr(_act_tls, "keep", None) is not None:
-        raise ValueError("preprocess: crop_resize_normalize cannot be recorded by filter_jit: its boxes, flips and offsets belong "
-                         "to this one call, and a replay would apply them to other images; preprocess outside the recorded "
-                         "function")
-    if isinstance(images_u8, (list, tuple)):
-        chw, sizes = _check_list(images_u8, channels_last)
-        batched = True
-    else:
-        x, batched, chw, hin, win = _check_input(images_u8, channels_last)
-        sizes = [(hin, win)] * (int(x.shape[0]) if batched else 1)
-        if batched and len(sizes) == 0:
-            raise ValueError("preprocess: the batch of images is empty")
-        if not batched:
-            boxes = np.asarray(boxes).reshape(1, -1) if np.asarray(boxes).ndim == 1 else boxes
-            flip = flip if flip is None else np.asarray(flip).reshape(-1)
+    _refuse_recording("crop_resize_normalize", "boxes, flips and offsets")
+    it = _intake(images_u8, channels_last)
+    if not it.batched:
+        boxes, flip = _rows_of_one(boxes, 4), _rows_of_one(flip, 0)
     _check_output(dtype, layout)
-    rec, (hout, wout) = boxes_plan(sizes, boxes, flip, size)
-    affine(mean, std)                                        # validates before the device is touched
-    a, b = _device_affine(mean, std)
-    if isinstance(images_u8, (list, tuple)):
-        t = pack_images(images_u8)
-    else:
-        t = x if isinstance(x, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(x))
-        t = t.to(device(), non_blocking=True).contiguous()
-    rec_dev = torch.from_numpy(rec.view(np.uint8)).to(device())
-    B = len(sizes)
-    y = empty((B, 3, hout, wout) if layout == "nchw" else (B, hout, wout, 3), TORCH_DT[dtype])
+    rec, (hout, wout) = boxes_plan(it.sizes, boxes, flip, size)
+    a, b = _affine_on_device(mean, std)
+    t, rec_dev = _one_buffer(it.x), _records_to_device(rec)
+    B = len(it.sizes)
+    y = _new_output(B, hout, wout, dtype, layout)
     _lib.call("mv_preprocess_u8_boxes_fwd", t.data_ptr(), t.numel(), y.data_ptr(), rec.ctypes.data, rec_dev.data_ptr(),
-              a.data_ptr(), b.data_ptr(), B, hout, wout, int(chw), DT[dtype], int(layout == "nhwc"), stream_ptr())
-    return y if batched else y[0]
+              a.data_ptr(), b.data_ptr(), B, hout, wout, int(it.chw), DT[dtype], int(layout == "nhwc"), stream_ptr())
+    return y if it.batched else y[0]
 
 
 def imagenet_train(images_u8, key, size=224, scale=(0.08, 1.0), ratio=(3.0 / 4.0, 4.0 / 3.0), flip_p=0.5, mean=IMAGENET_MEAN,
@@ -500,14 +552,7 @@ def imagenet_train(images_u8, key, size=224, scale=(0.08, 1.0), ratio=(3.0 / 4.0
     -> ToTensor -> Normalize, one launch.  `key` is split in two: `random_resized_crop_boxes` draws the boxes from the first
     half, `random_flips` the flips from the second; the same key gives the same tensor.  Returns [B, 3, size, size], fp32 or
     bf16: what `eqv.vmap(net)` reads.  `images_u8`: as for `crop_resize_normalize`."""
-    if isinstance(images_u8, (list, tuple)):
-        _, sizes = _check_list(images_u8, channels_last)
-        single = False
-    else:
-        x, batched, _, hin, win = _check_input(images_u8, channels_last)
-        sizes, single = [(hin, win)] * (int(x.shape[0]) if batched else 1), not batched
-        if len(sizes) == 0:
-            raise ValueError("preprocess: the batch of images is empty")
+    sizes, single = _sizes_of(images_u8, channels_last)
     k_box, k_flip = _random.split(key, 2)
     boxes = random_resized_crop_boxes(k_box, sizes, scale, ratio)
     flips = random_flips(k_flip, len(sizes), flip_p)
@@ -661,27 +706,16 @@ def crop_resize_normalize_mix(images_u8, boxes, size, flip=None, labels=None, nu
     labels are checked by the kernel (bit 3 of the device status).  `images_u8`: as for `crop_resize_normalize`; a single image
     has nobody to be mixed with and is refused when `partner` says otherwise.  One launch on the current stream.  The call cannot
     be recorded by `filter_jit`: the boxes and the draws belong to this one call."""
-    if getattr(_act_tls, "keep", None) is not None:
-        raise ValueError("preprocess: crop_resize_normalize_mix cannot be recorded by filter_jit: its boxes, flips, partners and "
-                         "rectangles belong to this one call, and a replay would apply them to other images; preprocess outside "
-                         "the recorded function")
-    if isinstance(images_u8, (list, tuple)):
-        chw, sizes = _check_list(images_u8, channels_last)
-        batched = True
-    else:
-        x, batched, chw, hin, win = _check_input(images_u8, channels_last)
-        sizes = [(hin, win)] * (int(x.shape[0]) if batched else 1)
-        if batched and len(sizes) == 0:
-            raise ValueError("preprocess: the batch of images is empty")
-        if not batched:
-            if partner is not None and np.any(np.asarray(partner).reshape(-1) != 0):
-                raise ValueError("preprocess: a single image has no partner to be mixed with; give a batch, or partner=None")
-            one = lambda v, n: v if v is None else np.asarray(v).reshape((1,) + ((n,) if n else ()))   # noqa: E731
-            boxes = np.asarray(boxes).reshape(1, -1) if np.asarray(boxes).ndim == 1 else boxes
-            flip = flip if flip is None else np.asarray(flip).reshape(-1)
-            partner, lam, lam_t, cut, erase = one(partner, 0), one(lam, 0), one(lam_t, 0), one(cut, 4), one(erase, 4)
-            if labels is not None and not isinstance(labels, torch.Tensor):
-                labels = np.asarray(labels).reshape(-1)
+    _refuse_recording("crop_resize_normalize_mix", "boxes, flips, partners and rectangles")
+    it = _intake(images_u8, channels_last)
+    sizes, batched, chw = it.sizes, it.batched, it.chw
+    if not batched:
+        if partner is not None and np.any(np.asarray(partner).reshape(-1) != 0):
+            raise ValueError("preprocess: a single image has no partner to be mixed with; give a batch, or partner=None")
+        boxes, cut, erase = _rows_of_one(boxes, 4), _rows_of_one(cut, 4), _rows_of_one(erase, 4)
+        flip, partner, lam, lam_t = _rows_of_one(flip, 0), _rows_of_one(partner, 0), _rows_of_one(lam, 0), _rows_of_one(lam_t, 0)
+        if not isinstance(labels, torch.Tensor):
+            labels = _rows_of_one(labels, 0)
     _check_output(dtype, layout)
     B = len(sizes)
     rec, (hout, wout) = boxes_plan(sizes, boxes, flip, size)
@@ -704,15 +738,9 @@ def crop_resize_normalize_mix(images_u8, boxes, size, flip=None, labels=None, nu
                 if not 0 <= int(v) < K:
                     raise ValueError(f"preprocess: image {i}: label {int(v)} does not lie in [0, {K})")
             lab_host = np.ascontiguousarray(lab_host, np.int32)
-    affine(mean, std)                                        # validates before the device is touched
-    a, b = _device_affine(mean, std)
-    if isinstance(images_u8, (list, tuple)):
-        t = pack_images(images_u8)
-    else:
-        t = x if isinstance(x, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(x))
-        t = t.to(device(), non_blocking=True).contiguous()
-    rec_dev, mix_dev = torch.from_numpy(rec.view(np.uint8)).to(device()), torch.from_numpy(mix.view(np.uint8)).to(device())
-    y = empty((B, 3, hout, wout) if layout == "nchw" else (B, hout, wout, 3), TORCH_DT[dtype])
+    a, b = _affine_on_device(mean, std)
+    t, rec_dev, mix_dev = _one_buffer(it.x), _records_to_device(rec), _records_to_device(mix)
+    y = _new_output(B, hout, wout, dtype, layout)
     targets = None
     if labels is not None:
         lab_dev = labels.to(device()).contiguous().reshape(B) if lab_host is None else torch.from_numpy(lab_host).to(device())
@@ -757,13 +785,6 @@ def imagenet_train_mixed(images_u8, labels, key, num_classes, size=224, scale=(0
 # `mv_preprocess_seg` of include/eqxvision_amd.h, 48 bytes
 SEG = np.dtype([("offset", "<i8"), ("mask_offset", "<i8"), ("Hin", "<i4"), ("Win", "<i4"), ("Hr", "<i4"), ("Wr", "<i4"),
                 ("top", "<i4"), ("left", "<i4"), ("flip", "<i4"), ("pad", "<i4")])
-
-
-def _pair(v, what):
-    hw = (int(v), int(v)) if isinstance(v, (int, np.integer)) else tuple(int(s) for s in v)
-    if len(hw) != 2 or hw[0] < 1 or hw[1] < 1:
-        raise ValueError(f"preprocess: {what} {v!r} must be a positive int or (height, width)")
-    return hw
 
 
 def random_resize_sizes(key, sizes, min_size, max_size) -> np.ndarray:
@@ -816,15 +837,8 @@ def seg_plan(sizes, resized, origins, flip, crop):
     the image."""
     B = len(sizes)
     hc, wc = _pair(crop, "crop")
-    rs, og = np.asarray(resized), np.asarray(origins)
-    if rs.dtype.kind not in "iu" or rs.shape != (B, 2):
-        raise ValueError(f"preprocess: resized must be integers [{B}, 2] of (Hr, Wr), one size per image, got {rs.dtype} {tuple(rs.shape)}")
-    if og.dtype.kind not in "iu" or og.shape != (B, 2):
-        raise ValueError(f"preprocess: origins must be integers [{B}, 2] of (top, left), one origin per image, got {og.dtype} "
-                         f"{tuple(og.shape)}")
-    fl = np.zeros(B, bool) if flip is None else np.asarray(flip)
-    if fl.shape != (B,):
-        raise ValueError(f"preprocess: flip must hold one flag per image ({B}), got shape {tuple(fl.shape)}")
+    rs, og = _int_rows(resized, B, 2, "resized", "(Hr, Wr), one size"), _int_rows(origins, B, 2, "origins", "(top, left), one origin")
+    fl = _flags(flip, B)
     rec = np.zeros(B, SEG)
     offset = 0
     for i, (hin, win) in enumerate(sizes):
@@ -862,14 +876,6 @@ def _check_masks(masks, sizes, listed, batched):
             raise ValueError(f"preprocess: image {i}: mask of shape {tuple(m.shape)} for an image of {hw[0]}x{hw[1]}")
 
 
-def _one_buffer(v):
-    """A list -> `pack_images` (which packs any uint8 arrays, planes included); an array -> itself on the device, contiguous."""
-    if isinstance(v, (list, tuple)):
-        return pack_images(v)
-    t = v if isinstance(v, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(v))
-    return t.to(device(), non_blocking=True).contiguous()
-
-
 def resize_pad_crop_pair(images_u8, masks_u8, resized, origins, crop, flip=None, mean=IMAGENET_MEAN, std=IMAGENET_STD, dtype="fp32",
                          layout="nchw", image_fill=0, mask_fill=255, channels_last=None):
     """Resize image i WHOLE to `resized[i]` = (Hr, Wr) with the antialiased triangle filter of `crop_resize_normalize`, mirror it
@@ -883,41 +889,28 @@ def resize_pad_crop_pair(images_u8, masks_u8, resized, origins, crop, flip=None,
     axis, sizes matching, or None (then labels is None).  One launch of `mv_preprocess_u8_seg_fwd` on the current stream for
     every form; lists are packed with `pack_images`, one upload each.  The call cannot be recorded by `filter_jit`: the sizes and
     origins belong to this one call."""
-    if getattr(_act_tls, "keep", None) is not None:
-        raise ValueError("preprocess: resize_pad_crop_pair cannot be recorded by filter_jit: its sizes, origins, flips and offsets "
-                         "belong to this one call, and a replay would apply them to other images; preprocess outside the recorded "
-                         "function")
-    listed = isinstance(images_u8, (list, tuple))
-    if listed:
-        chw, sizes = _check_list(images_u8, channels_last)
-        batched = True
-    else:
-        x, batched, chw, hin, win = _check_input(images_u8, channels_last)
-        sizes = [(hin, win)] * (int(x.shape[0]) if batched else 1)
-        if len(sizes) == 0:
-            raise ValueError("preprocess: the batch of images is empty")
-        if not batched:
-            resized = np.asarray(resized).reshape(1, -1) if np.asarray(resized).ndim == 1 else resized
-            origins = np.asarray(origins).reshape(1, -1) if np.asarray(origins).ndim == 1 else origins
-            flip = flip if flip is None else np.asarray(flip).reshape(-1)
+    _refuse_recording("resize_pad_crop_pair", "sizes, origins, flips and offsets")
+    it = _intake(images_u8, channels_last)
+    sizes, batched = it.sizes, it.batched
+    if not batched:
+        resized, origins, flip = _rows_of_one(resized, 2), _rows_of_one(origins, 2), _rows_of_one(flip, 0)
     if masks_u8 is not None:
-        _check_masks(masks_u8, sizes, listed, batched)
+        _check_masks(masks_u8, sizes, it.listed, batched)
     _check_output(dtype, layout)
     for name, v in (("image_fill", image_fill), ("mask_fill", mask_fill)):
         if not isinstance(v, (int, np.integer)) or not 0 <= int(v) <= 255:
             raise ValueError(f"preprocess: {name} must be an integer in [0, 255], got {v!r}")
     rec, (hc, wc) = seg_plan(sizes, resized, origins, flip, crop)
-    affine(mean, std)                                        # validates before the device is touched
-    a, b = _device_affine(mean, std)
-    t = _one_buffer(images_u8)
+    a, b = _affine_on_device(mean, std)
+    t = _one_buffer(it.x)
     m = None if masks_u8 is None else _one_buffer(masks_u8)
-    rec_dev = torch.from_numpy(rec.view(np.uint8)).to(device())
+    rec_dev = _records_to_device(rec)
     B = len(sizes)
-    y = empty((B, 3, hc, wc) if layout == "nchw" else (B, hc, wc, 3), TORCH_DT[dtype])
+    y = _new_output(B, hc, wc, dtype, layout)
     labels = None if m is None else empty((B, hc, wc), torch.int32)
     _lib.call("mv_preprocess_u8_seg_fwd", t.data_ptr(), t.numel(), None if m is None else m.data_ptr(), 0 if m is None else m.numel(),
               y.data_ptr(), None if m is None else labels.data_ptr(), rec.ctypes.data, rec_dev.data_ptr(), a.data_ptr(), b.data_ptr(),
-              B, hc, wc, int(image_fill), int(mask_fill), int(chw), DT[dtype], int(layout == "nhwc"), stream_ptr())
+              B, hc, wc, int(image_fill), int(mask_fill), int(it.chw), DT[dtype], int(layout == "nhwc"), stream_ptr())
     if batched:
         return y, labels
     return y[0], None if labels is None else labels[0]
@@ -925,13 +918,8 @@ def resize_pad_crop_pair(images_u8, masks_u8, resized, origins, crop, flip=None,
 
 def _sizes_of(images_u8, channels_last):
     """-> ([(Hin, Win)] per image, single): the sizes of any accepted form of input."""
-    if isinstance(images_u8, (list, tuple)):
-        return _check_list(images_u8, channels_last)[1], False
-    x, batched, _, hin, win = _check_input(images_u8, channels_last)
-    sizes = [(hin, win)] * (int(x.shape[0]) if batched else 1)
-    if len(sizes) == 0:
-        raise ValueError("preprocess: the batch of images is empty")
-    return sizes, not batched
+    it = _intake(images_u8, channels_last)
+    return it.sizes, not it.batched
 
 
 def segmentation_train(images_u8, masks_u8, key, base_size=520, crop_size=480, flip_p=0.5, mean=IMAGENET_MEAN, std=IMAGENET_STD,
