@@ -60,6 +60,7 @@ class Tape:
         self.frozen = None      # ids of the leaves a filter spec (filter_value_and_grad's `arg`) marks False; None = no spec
         self.inside = 0         # > 0 while a g_* function runs (its own C-ABI calls are allowed)
         self.matmul_dtype = "fp32"   # filter_value_and_grad's `matmul_dtype`: "bf16" = g_linear's three products on the bf16 matrix cores
+        self.conv_dtype = "fp32"     # filter_value_and_grad's `conv_dtype`: "bf16" = g_conv2d's three products (groups == 1) likewise
 
 
 class Node:
@@ -537,6 +538,11 @@ def _conv_w(conv) -> torch.Tensor:
 
 @_op
 def g_conv2d(x: Act, conv, bn=None, act=None, residual: Optional[Act] = None) -> Act:
+    """Under filter_value_and_grad(..., conv_dtype="bf16") a convolution with groups == 1 runs its forward product, its input gradient
+    and its weight gradient on the bf16 matrix cores (operands rounded to bf16 on their way into LDS, fp32 accumulation, fp32 results):
+    a pointwise filter with stride 1 and no padding is a Linear on the [N H W, C] rows and goes through mv_linear_mp_*, every other
+    geometry through mv_conv2d_mp_* (csrc/conv_mp.hip).  The bias, its gradient, BatchNorm, the residual and the activation stay fp32,
+    and so does a grouped or depthwise convolution: a reduction of 9 taps has nothing for the matrix cores."""
     _check_act(act)
     G = conv.groups
     x = g_as_map.__wrapped__(x)
@@ -552,8 +558,16 @@ def g_conv2d(x: Act, conv, bn=None, act=None, residual: Optional[Act] = None) ->
     w = _conv_w(conv)
     bias = _leaf_dev(conv.bias).reshape(-1) if conv.bias is not None else None
     z = _new((B, Ho, Wo, K))
-    _call("mv_conv2d_nhwc_fwd", _p(x.t), _p(w), None, _p(bias), None, _p(z), B, H, W, C, K, kh, kw, sh, sw, ph, pw, dh, dw, G,
-          _lib.ACT_NONE, F32, F32, _S())
+    mp = tape().conv_dtype == "bf16" and G == 1
+    as_linear = mp and (kh, kw, sh, sw, ph, pw) == (1, 1, 1, 1, 0, 0)      # x is [B H W, C] rows, the KRSC filter is [K, C]
+    geom = (B, H, W, C, K, kh, kw, sh, sw, ph, pw, dh, dw)
+    if as_linear:
+        _call("mv_linear_mp_fwd", _p(x.t), _p(w), _p(bias), _p(z), B * H * W, K, C, _S())
+    elif mp:
+        _call("mv_conv2d_mp_fwd", _p(x.t), _p(w), _p(bias), _p(z), *geom, _S())
+    else:
+        _call("mv_conv2d_nhwc_fwd", _p(x.t), _p(w), None, _p(bias), None, _p(z), B, H, W, C, K, kh, kw, sh, sw, ph, pw, dh, dw, G,
+              _lib.ACT_NONE, F32, F32, _S())
     y1, saved = (z, None) if bn is None else _bn_forward(bn, z, "map", x.batched)
     r = None
     if residual is not None:
@@ -572,17 +586,30 @@ def g_conv2d(x: Act, conv, bn=None, act=None, residual: Optional[Act] = None) ->
         dz = g2 if bn is None else _bn_backward(bn, z, g2, saved)
         if _trainable(conv.bias):
             _acc_param(conv.bias, _colsum(dz, None, K))
-        if _trainable(conv.weight):
+        if _trainable(conv.weight) and as_linear:
+            dwo = _new((K, C))                                          # dW[K,C] is the leaf's (K, C, 1, 1) memory
+            _offer_scratch()
+            _call("mv_linear_mp_wgrad", _p(dz), _p(xin), _p(dwo), B * H * W, K, C, _S())
+            _acc_param(conv.weight, dwo)
+        elif _trainable(conv.weight):
             dwk = _new((K, kh, kw, C // G))
             _offer_scratch()
-            _call("mv_conv2d_wgrad_nhwc_f32", _p(xin), _p(dz), _p(dwk), B, H, W, C, K, kh, kw, sh, sw, ph, pw, dh, dw, G, _S())
+            if mp:
+                _call("mv_conv2d_mp_wgrad", _p(xin), _p(dz), _p(dwk), *geom, _S())
+            else:
+                _call("mv_conv2d_wgrad_nhwc_f32", _p(xin), _p(dz), _p(dwk), B, H, W, C, K, kh, kw, sh, sw, ph, pw, dh, dw, G, _S())
             dwo = _new((K, C // G, kh, kw))
             _call("mv_nhwc_to_nchw", _p(dwk), _p(dwo), K, C // G, kh, kw, F32, F32, _S())   # KRSC -> OIHW, the leaf's layout
             _acc_param(conv.weight, dwo)
         dx = None
         if need_dx:
             dx = _new((B, H, W, C))
-            _call("mv_conv2d_dgrad_nhwc_f32", _p(dz), _p(w), _p(dx), B, H, W, C, K, kh, kw, sh, sw, ph, pw, dh, dw, G, _S())
+            if as_linear:
+                _call("mv_linear_mp_dgrad", _p(dz), _p(w), _p(dx), B * H * W, K, C, _S())
+            elif mp:
+                _call("mv_conv2d_mp_dgrad", _p(dz), _p(w), _p(dx), *geom, _S())
+            else:
+                _call("mv_conv2d_dgrad_nhwc_f32", _p(dz), _p(w), _p(dx), B, H, W, C, K, kh, kw, sh, sw, ph, pw, dh, dw, G, _S())
         return (dx, g2 if r is not None else None)
     return _mk(y, "map", x.batched, [_node(x), _node(r)], backward,
                leaves=(conv.weight, conv.bias) + ((bn.weight, bn.bias) if bn is not None else ()))
@@ -1159,9 +1186,10 @@ def _frozen_ids(model, spec) -> set:
 
 
 MATMUL_DTYPES = ("fp32", "bf16")
+CONV_DTYPES = ("fp32", "bf16")
 
 
-def filter_value_and_grad(fn: Optional[Callable] = None, *, arg=None, matmul_dtype: str = "fp32") -> Callable:
+def filter_value_and_grad(fn: Optional[Callable] = None, *, arg=None, matmul_dtype: str = "fp32", conv_dtype: str = "fp32") -> Callable:
     """`eqx.filter_value_and_grad`: fn(model, *args) -> scalar loss; returns (loss, grads) with `grads` = the model tree with
     every array leaf replaced by its gradient (zeros where the loss does not depend on it) and every other leaf kept.
 
@@ -1174,11 +1202,19 @@ def filter_value_and_grad(fn: Optional[Callable] = None, *, arg=None, matmul_dty
     layers (`g_linear`: ViT's and Swin's projections and MLPs, the qkv projection, the patch-merging reduction): the forward product,
     the input gradient and the weight gradient round their operands to bf16 (round-to-nearest-even) and accumulate in fp32 on the
     bf16 matrix cores; parameters, gradients, biases and their gradients, optimiser state, convolutions, attention's products and
-    the classifier head stay fp32.  Any other value raises ValueError here, when the decorator is applied."""
+    the classifier head stay fp32.  Any other value raises ValueError here, when the decorator is applied.
+
+    `conv_dtype` (a keyword, independent of `matmul_dtype`: each governs its own layer type): "fp32" (the default) launches what it
+    always did.  "bf16" is the same mixed precision for every Conv2d with groups == 1 (`g_conv2d`: forward, input gradient and weight
+    gradient round their operands to bf16 and accumulate in fp32; a pointwise stride-1 convolution runs as a Linear on its rows).
+    Grouped and depthwise convolutions, the bias and its gradient, BatchNorm, residual adds, activations, the patch embedding and
+    everything in memory stay fp32.  Any other value raises ValueError here, when the decorator is applied."""
     if matmul_dtype not in MATMUL_DTYPES:
         raise ValueError(f"filter_value_and_grad: matmul_dtype must be one of {MATMUL_DTYPES}, got {matmul_dtype!r}")
+    if conv_dtype not in CONV_DTYPES:
+        raise ValueError(f"filter_value_and_grad: conv_dtype must be one of {CONV_DTYPES}, got {conv_dtype!r}")
     if fn is None:
-        return functools.partial(filter_value_and_grad, arg=arg, matmul_dtype=matmul_dtype)
+        return functools.partial(filter_value_and_grad, arg=arg, matmul_dtype=matmul_dtype, conv_dtype=conv_dtype)
 
     @functools.wraps(fn)
     def wrapped(model, *args, **kwargs):
@@ -1194,6 +1230,7 @@ def filter_value_and_grad(fn: Optional[Callable] = None, *, arg=None, matmul_dty
         t = _tls.tape = Tape()
         t.frozen = frozen
         t.matmul_dtype = matmul_dtype
+        t.conv_dtype = conv_dtype
         try:
             with precision("fp32"):
                 loss = fn(model, *args, **kwargs)

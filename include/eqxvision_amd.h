@@ -994,6 +994,30 @@ int mv_linear_mp_fwd(const float* x, const float* w, const float* bias, float* y
 int mv_linear_mp_dgrad(const float* g, const float* w, float* dx, int64_t M, int N, int K, mv_stream_t stream);
 int mv_linear_mp_wgrad(const float* g, const float* x, float* dw, int64_t M, int N, int K, mv_stream_t stream);
 
+/* ---- mixed-precision Conv2d, groups == 1, for the training step (filter_value_and_grad(..., conv_dtype="bf16"); eqx.nn.Conv2d).
+ * Implicit GEMMs, no im2col buffer.  Maps are NHWC fp32, filters KRSC fp32 (w[k][r][s][c]); every tensor is fp32 in memory.  r(.)
+ * rounds an operand element to bf16, round-to-nearest-even, on its way into LDS; products are accumulated in fp32 on
+ * v_mfma_f32_32x32x16_bf16 and the result is stored as fp32.  Any R, S and any stride / padding / dilation (h and w independent).
+ * Ho = (H + 2 ph - dh (R - 1) - 1) / sh + 1, Wo likewise; an empty output is MV_E_INVALID.
+ *   fwd:    y[n,ho,wo,k]  = sum over r, s, c of r(x[n, ho sh - ph + r dh, wo sw - pw + s dw, c]) r(w[k,r,s,c]) + bias[k]
+ *           (padding reads as zeros; bias may be NULL; it is added in fp32, NOT rounded)
+ *   dgrad:  dx[n,hi,wi,c] = sum over k and over the taps (r, s) for which sh divides hi + ph - r dh and sw divides wi + pw - s dw with
+ *           both quotients (ho, wo) inside the output map, of r(dy[n,ho,wo,k]) r(w[k,r,s,c]); every dx element is written
+ *   wgrad:  dw[k,r,s,c]   = sum over the output positions (n, ho, wo) of r(dy[n,ho,wo,k]) r(x[n, ho sh - ph + r dh, wo sw - pw + s dw, c]).
+ *           With scratch on offer (mv_set_scratch: 4096 bytes + at least 2 x the gradient's bytes) the positions are split over up to
+ *           64 parts of at least 256 positions, which are added in index order (bit-reproducible; the first 4096 bytes of the offer
+ *           stay zero); without it, or with room for fewer than two parts, one block walks all positions for its tile and writes dw
+ *           directly.  mv_last_kernel tells the two forms apart (conv_mp_wgrad_bf16 / conv_mp_wgrad_split_bf16).
+ * Limits: C, K and R S C at most 2^21; x and y / dy at most 2^29 - 4 elements each (the gathered map is addressed with 32-bit byte
+ * offsets from its base): a larger map is refused with MV_E_UNSUPPORTED, never wrapped.  16-byte loads where base and channel count
+ * allow (16-byte aligned base, C resp. K a multiple of 4), 4-byte loads otherwise. */
+int mv_conv2d_mp_fwd(const float* x, const float* w_krsc, const float* bias, float* y, int N, int H, int W, int C, int K, int R, int S,
+                     int sh, int sw, int ph, int pw, int dh, int dw, mv_stream_t stream);
+int mv_conv2d_mp_dgrad(const float* dy, const float* w_krsc, float* dx, int N, int H, int W, int C, int K, int R, int S, int sh, int sw,
+                       int ph, int pw, int dh, int dw, mv_stream_t stream);
+int mv_conv2d_mp_wgrad(const float* x, const float* dy, float* dw_krsc, int N, int H, int W, int C, int K, int R, int S, int sh, int sw,
+                       int ph, int pw, int dh, int dw, mv_stream_t stream);
+
 /* hipGraph capture of a whole forward (replaces the reference's eqx.filter_jit executable) */
 int mv_graph_begin_capture(mv_stream_t stream);
 int mv_graph_end_capture(mv_stream_t stream, void** graph_exec);
