@@ -107,6 +107,11 @@ int get_flag(const char* name);
 // at least `need` bytes, else nullptr
 void* take_scratch(hipStream_t stream, size_t need);            // (SCRATCH_SYNC_BYTES, the head of every offer: route.h)
 void* peek_scratch(hipStream_t stream, size_t* bytes);
+// the partial sums of a split reduction, `part_elems` floats each, from that offer: min(want, what fits) parts if that is at least
+// `least`, else 0 and *part = nullptr (the offer stays on offer).  runtime.hip says where in the offer they lie and why.
+long long take_scratch_parts(hipStream_t stream, long long want, long long least, long long part_elems, float** part);
+// out[i] = part[0][i] + part[1][i] + ... + part[parts - 1][i] in index order, for i < n (train_bwd.hip)
+void sum_parts(hipStream_t stream, const float* part, float* out, long long n, int parts);
 size_t splitk_scratch_bytes(long long M, long long N, long long kred);       // igemm8.hip
 const void* zero_page(hipStream_t stream);  // >= 4 KiB of device zeros for the current device
 

@@ -12,10 +12,11 @@
 // the output map; every other tap contributes nothing to that position ("the stride divides").
 // A step never straddles two taps; channels / filters past the end of the last chunk of a tap read as zeros.
 //
-// Tile, pipeline, LDS images, fragment reads and the MFMA step are linear_mp.hip's (linear_mp_tile.h): 128 x 128 outputs per workgroup
-// of 4 waves, 32 reduction elements per step, LDS double-buffered with the next step's loads in registers, one barrier per step.  The
-// plain operand is loaded with lmp_gload as it is; only the gathered operand has loaders of its own (cmp_gload_rows / cmp_gload_red),
-// which produce the same register patch, so lmp_lstore / lmp_frag serve both.
+// Tile, LDS images, fragment reads, the MFMA step, the double-buffered loop (lmp_reduce), the store of a tile (lmp_store_tile) and the
+// weight gradient's split rule (lmp_wgrad_split) are linear_mp.hip's, all in linear_mp_tile.h: 128 x 128 outputs per workgroup of 4 waves,
+// 32 reduction elements per step, the next step's loads in registers, one barrier per step.  Here: the tile decoding, the walk over
+// (tap, chunk), the loaders and the output base.  The plain operand is loaded with lmp_gload as it is; only the gathered operand has
+// loaders of its own (cmp_gload_rows / cmp_gload_red), which produce the same register patch, so lmp_lstore / lmp_frag serve both.
 // Deviations from linear_mp.hip, and why:
 //   * wgrad's grid is (filter tiles x taps x channel tiles): the source row of a position depends on the tap, so a tile holds one tap.
 //     With C = 3 (the stems) 125 of a tile's 128 columns are padding; the entry is correct there, not fast.
@@ -24,11 +25,14 @@
 //   * the gathered operand has ONE buffer descriptor at the tensor's base (a tile's rows cross image boundaries), so the gathered map is
 //     limited to 2^31 bytes; the entries refuse a larger one.  The plain operand is re-based per tile / per step as in linear_mp.hip.
 //
-// Resources (hipcc -O3 --offload-arch=gfx950, 256 threads, LDS 40960 bytes each; no spills, no scratch):
-//   conv_mp_fwd_bf16             (cmp_kernel<0>)   VGPR  90  AGPR 64   3 waves / SIMD by registers
+// Resources (hipcc -O3 --offload-arch=gfx950, -Rpass-analysis=kernel-resource-usage; 256 threads, LDS 40960 bytes each; no spills, no scratch):
+//   conv_mp_fwd_bf16             (cmp_kernel<0>)   VGPR  90  AGPR 64   3 waves / SIMD
 //   conv_mp_dgrad_bf16           (cmp_kernel<1>)   VGPR 108  AGPR 64   2 waves / SIMD
 //   conv_mp_wgrad[_split]_bf16   (cmp_kernel<2>)   VGPR  98  AGPR 64   3 waves / SIMD
-// (the 64 accumulator registers live in AGPRs; LDS allows 3 workgroups of 4 waves per CU, i.e. 3 waves per SIMD)
+// (the 64 accumulator registers live in AGPRs; LDS allows 3 workgroups of 4 waves per CU, i.e. 3 waves per SIMD.  For comparison,
+// linear_mp.hip's lmp_kernel: fwd 80, dgrad 98 -- 3 waves / SIMD --, wgrad 112 VGPRs -- 2 waves / SIMD --, 64 AGPRs each.)
+// The loader is a lambda lmp_reduce calls once per step: it keeps (tap, chunk) and the step in its own counters -- taking the step from
+// the loop instead costs wgrad 8 VGPRs and its third wave.
 #include "linear_mp_tile.h"
 
 namespace mv {
@@ -115,7 +119,7 @@ template <int MODE> __global__ __launch_bounds__(256) void cmp_kernel(const CmpP
     constexpr bool TA = MODE == CMP_WGRAD;            // A = the row operand of the product, B = the column operand
     constexpr bool TB = MODE != CMP_FWD;
     __shared__ __attribute__((aligned(16))) char lds[2][2][LMP_IMG];
-    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    const int t = threadIdx.x;
     const int taps = p.R * p.S;
     const brsrc_t rs_g = make_brsrc(p.a);
 
@@ -164,10 +168,10 @@ template <int MODE> __global__ __launch_bounds__(256) void cmp_kernel(const CmpP
     }
     const int wtap_r = tap / p.S, wtap_s = tap - wtap_r * p.S;        // wgrad's tap
 
-    float4 va[4], vb[4];
-    int g_r = 0, g_s = 0, g_c0 = 0;              // fwd / dgrad: the (tap, chunk) the next gload stages; calls come in step order
-    int g_step = 0;
-    auto gload = [&]() {
+    int g_r = 0, g_s = 0, g_c0 = 0;              // fwd / dgrad: the (tap, chunk) the next load stages; lmp_reduce calls in step order
+    int g_step = 0;                              // wgrad: the step it stages
+    f32x16 acc[2][2];
+    lmp_reduce<TA, TB>(acc, lds, steps, t, [&](float4 (&va)[4], float4 (&vb)[4]) {
         if (MODE == CMP_FWD) {
             const int left = red - g_c0 < LMP_S ? red - g_c0 : LMP_S;
             cmp_gload_rows<CMP_FWD>(va, rs_g, p, rn, ra, rb, g_r, g_s, g_c0, p.C, p.vec_a, t);
@@ -188,53 +192,12 @@ template <int MODE> __global__ __launch_bounds__(256) void cmp_kernel(const CmpP
             g_c0 = 0;
             if (++g_s == p.S) { g_s = 0; ++g_r; }
         }
-    };
+    });
 
-    f32x16 acc[2][2];
-#pragma unroll
-    for (int a = 0; a < 2; ++a)
-#pragma unroll
-        for (int b = 0; b < 2; ++b)
-#pragma unroll
-            for (int e = 0; e < 16; ++e) acc[a][b][e] = 0.f;
-
-    const int wr = (wave >> 1) * 64, wc = (wave & 1) * 64;
-    if (steps > 0) {
-        gload();
-        lmp_lstore<TA>(lds[0][0], va, t);
-        lmp_lstore<TB>(lds[0][1], vb, t);
-    }
-    __syncthreads();
-    for (int s = 0; s < steps; ++s) {
-        const int cur = s & 1;
-        const bool more = s + 1 < steps;
-        if (more) gload();
-        lmp_mma_step<TA, TB>(acc, lds[cur][0], lds[cur][1], wr, wc, lane);
-        if (more) {                          // the other buffer was last read in step s - 1, a barrier ago
-            lmp_lstore<TA>(lds[cur ^ 1][0], va, t);
-            lmp_lstore<TB>(lds[cur ^ 1][1], vb, t);
-        }
-        __syncthreads();
-    }
-
-    // C/D map of the 32x32 MFMA: column = lane & 31, row = (e & 3) + 8 (e >> 2) + 4 (lane >> 5).  fwd / dgrad: c[i][J]; wgrad: the tile's
-    // tap of dw[k][taps][C], in part blockIdx.y.
+    // fwd / dgrad: c[i][J]; wgrad: the tile's tap of dw[k][taps][C], in part blockIdx.y
     const long long ldc = MODE == CMP_WGRAD ? (long long)taps * p.C : (long long)J;
     float* cbase = p.c + (MODE == CMP_WGRAD ? (long long)blockIdx.y * p.K * ldc + (long long)tap * p.C : 0LL);
-#pragma unroll
-    for (int b = 0; b < 2; ++b) {
-        const int j = j0 + wc + 32 * b + (lane & 31);
-        const bool jok = j < J;
-        const float bj = (MODE == CMP_FWD && p.bias && jok) ? p.bias[j] : 0.f;
-#pragma unroll
-        for (int a = 0; a < 2; ++a) {
-#pragma unroll
-            for (int e = 0; e < 16; ++e) {
-                const unsigned i = i0 + (unsigned)(wr + 32 * a + (e & 3) + 8 * (e >> 2) + 4 * (lane >> 5));
-                if (jok && i < I) cbase[(long long)i * ldc + j] = acc[a][b][e] + bj;
-            }
-        }
-    }
+    lmp_store_tile(acc, cbase + (long long)i0 * ldc, (unsigned)ldc, rows_i, j0, J, MODE == CMP_FWD ? p.bias : nullptr, t);
 }
 
 // the gathered map is addressed from ONE descriptor at its base with 32-bit byte offsets
@@ -332,39 +295,16 @@ int mv_conv2d_mp_wgrad(const float* x, const float* dy, float* dw_krsc, int N, i
         set_error("conv2d_mp_wgrad: %lld output tiles do not fit the grid", tiles);
         return MV_E_UNSUPPORTED;
     }
-    // positions split over blocks: ~4 workgroups per CU, every part at least 256 positions (8 steps), at most 64 parts
-    const long long steps = (g.P + LMP_S - 1) / LMP_S;
-    long long split = tiles >= 1024 ? 1 : (1024 + tiles - 1) / tiles;
-    if (split > steps / 8) split = steps / 8;
-    if (split > 64) split = 64;
-    float* part = dw_krsc;
-    if (split > 1) {
-        // the parts live BEHIND the first 4096 bytes of the offer (the arrival words of the forward's split-K protocol, which stay zero)
-        size_t have = 0;
-        void* sc = peek_scratch((hipStream_t)stream, &have);
-        have = have > SCRATCH_SYNC_BYTES ? have - SCRATCH_SYNC_BYTES : 0;
-        const long long fit = sc ? (long long)(have / ((size_t)out_elems * 4)) : 0;
-        if (fit < 2) split = 1;
-        else {
-            if (split > fit) split = fit;
-            part = (float*)((char*)take_scratch((hipStream_t)stream, SCRATCH_SYNC_BYTES + (size_t)split * out_elems * 4) + SCRATCH_SYNC_BYTES);
-        }
-    }
-    if (split < 1) split = 1;
-    const long long chunk = ((steps + split - 1) / split) * LMP_S;
-    split = (g.P + chunk - 1) / chunk;                           // no empty part
-    if (split <= 1) part = dw_krsc;
+    const LmpSplit sp = lmp_wgrad_split(tiles, g.P, out_elems, (hipStream_t)stream, dw_krsc);        // the P positions split over blocks
     CmpP p = cmp_params(g);
-    p.a = x; p.b = dy; p.bias = nullptr; p.c = part;
+    p.a = x; p.b = dy; p.bias = nullptr; p.c = sp.part;
     p.vec_a = lmp_vec_ok(x, C);
     p.vec_b = lmp_vec_ok(dy, K);
-    p.chunk = (unsigned)chunk;
+    p.chunk = (unsigned)sp.chunk;
     p.tiles_j = (C + LMP_T - 1) / LMP_T;
-    set_kernel_name(split > 1 ? "conv_mp_wgrad_split_bf16" : "conv_mp_wgrad_bf16");
-    hipLaunchKernelGGL((cmp_kernel<CMP_WGRAD>), dim3((unsigned)tiles, (unsigned)split), dim3(256), 0, (hipStream_t)stream, p);
-    if (split > 1)
-        hipLaunchKernelGGL(lmp_sum_parts_kernel, dim3((unsigned)((out_elems + 255) / 256)), dim3(256), 0, (hipStream_t)stream, part, dw_krsc,
-                           out_elems, (int)split);
+    set_kernel_name(sp.split > 1 ? "conv_mp_wgrad_split_bf16" : "conv_mp_wgrad_bf16");
+    hipLaunchKernelGGL((cmp_kernel<CMP_WGRAD>), dim3((unsigned)tiles, (unsigned)sp.split), dim3(256), 0, (hipStream_t)stream, p);
+    if (sp.split > 1) sum_parts((hipStream_t)stream, sp.part, dw_krsc, out_elems, (int)sp.split);
     MV_LAUNCH_CHECK();
     return MV_OK;
 }

@@ -14,7 +14,9 @@
 // Tile: 128 x 128 outputs per workgroup of 4 waves (64 x 64 per wave = 2 x 2 MFMA tiles), 32 reduction elements per step, LDS
 // double-buffered with the next step's global loads in flight in registers (one barrier per step).
 //
-// The LDS images, the staging helpers, the fragment reads and the MFMA step are linear_mp_tile.h (shared with conv_mp.hip).
+// The LDS images, the staging helpers, the fragment reads, the MFMA step, that loop (lmp_reduce), the store of a tile and the weight
+// gradient's split rule are linear_mp_tile.h (shared with conv_mp.hip); the parts of a split are taken from the scratch offer by
+// take_scratch_parts (runtime.hip) and added by sum_parts (train_bwd.hip).  Here: the tile decoding, the reduction range, the loaders.
 //
 // Bounds: rows / columns / reduction elements outside the tensors are never read -- their buffer offset is BUF_OOB, which the buffer
 // unit answers with zeros (mfma_common.h) -- and contribute exact zeros to the sums; stores are predicated.  16-byte loads are used
@@ -39,7 +41,7 @@ struct LmpP {
 
 template <bool TA, bool TB> __global__ __launch_bounds__(256) void lmp_kernel(const LmpP p) {
     __shared__ __attribute__((aligned(16))) char lds[2][2][LMP_IMG];
-    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    const int t = threadIdx.x;
     const long long tile_i = blockIdx.x / p.tiles_j;
     const int tile_j = (int)(blockIdx.x - tile_i * p.tiles_j);
     const long long i0 = tile_i * LMP_T;
@@ -53,59 +55,18 @@ template <bool TA, bool TB> __global__ __launch_bounds__(256) void lmp_kernel(co
     const float* abase = TA ? p.a + i0 : p.a + i0 * p.lda;
     const float* bbase = TB ? p.b + j0 : p.b + (long long)j0 * p.ldb;
 
-    float4 va[4], vb[4];
-    auto gload = [&](int s) {
-        const long long r0 = rbeg + (long long)s * LMP_S;
+    long long r0 = rbeg;                     // first reduction element of the step the next load stages
+    f32x16 acc[2][2];
+    lmp_reduce<TA, TB>(acc, lds, steps, t, [&](float4 (&va)[4], float4 (&vb)[4]) {
         const int left = (int)(rend - r0 < LMP_S ? rend - r0 : LMP_S);
         if (TA) lmp_gload<true>(va, abase + r0 * p.lda, p.lda, p.vec_a, rows_a, 0, left, t);
         else    lmp_gload<false>(va, abase, p.lda, p.vec_a, rows_a, (int)r0, left, t);
         if (TB) lmp_gload<true>(vb, bbase + r0 * p.ldb, p.ldb, p.vec_b, rows_b, 0, left, t);
         else    lmp_gload<false>(vb, bbase, p.ldb, p.vec_b, rows_b, (int)r0, left, t);
-    };
-
-    f32x16 acc[2][2];
-#pragma unroll
-    for (int a = 0; a < 2; ++a)
-#pragma unroll
-        for (int b = 0; b < 2; ++b)
-#pragma unroll
-            for (int e = 0; e < 16; ++e) acc[a][b][e] = 0.f;
-
-    const int wr = (wave >> 1) * 64, wc = (wave & 1) * 64;
-    if (steps > 0) {
-        gload(0);
-        lmp_lstore<TA>(lds[0][0], va, t);
-        lmp_lstore<TB>(lds[0][1], vb, t);
-    }
-    __syncthreads();
-    for (int s = 0; s < steps; ++s) {
-        const int cur = s & 1;
-        const bool more = s + 1 < steps;
-        if (more) gload(s + 1);
-        lmp_mma_step<TA, TB>(acc, lds[cur][0], lds[cur][1], wr, wc, lane);
-        if (more) {                          // the other buffer was last read in step s - 1, a barrier ago
-            lmp_lstore<TA>(lds[cur ^ 1][0], va, t);
-            lmp_lstore<TB>(lds[cur ^ 1][1], vb, t);
-        }
-        __syncthreads();
-    }
-
-    // C/D map of the 32x32 MFMA: column = lane & 31, row = (e & 3) + 8 (e >> 2) + 4 (lane >> 5): a register is one 128-byte row segment
-    float* cpart = p.c + (long long)blockIdx.y * p.I * p.J;
-#pragma unroll
-    for (int b = 0; b < 2; ++b) {
-        const int j = j0 + wc + 32 * b + (lane & 31);
-        const bool jok = j < p.J;
-        const float bj = (p.bias && jok) ? p.bias[j] : 0.f;
-#pragma unroll
-        for (int a = 0; a < 2; ++a) {
-#pragma unroll
-            for (int e = 0; e < 16; ++e) {
-                const long long i = i0 + wr + 32 * a + (e & 3) + 8 * (e >> 2) + 4 * (lane >> 5);
-                if (jok && i < p.I) cpart[i * p.J + j] = acc[a][b][e] + bj;
-            }
-        }
-    }
+        r0 += LMP_S;
+    });
+    // part blockIdx.y of a split reduction, the tile's first row (64-bit: I is not bounded)
+    lmp_store_tile(acc, p.c + ((long long)blockIdx.y * p.I + i0) * p.J, (unsigned)p.J, rows_a, j0, p.J, p.bias, t);
 }
 
 template <bool TA, bool TB> int lmp_launch(LmpP& p, int split, hipStream_t st) {
@@ -156,35 +117,12 @@ int mv_linear_mp_wgrad(const float* g, const float* x, float* dw, int64_t M, int
     MV_CHECK_ARG(N <= LMP_MAX_DIM && K <= LMP_MAX_DIM, "linear_mp_wgrad: N = %d / K = %d above %d", N, K, LMP_MAX_DIM);
     const long long out_elems = (long long)N * K;
     const long long tiles = (((long long)N + LMP_T - 1) / LMP_T) * (((long long)K + LMP_T - 1) / LMP_T);
-    // rows split over blocks: ~4 workgroups per CU, every part at least 256 rows (8 steps), at most 64 parts
-    const long long steps = ((long long)M + LMP_S - 1) / LMP_S;
-    long long split = tiles >= 1024 ? 1 : (1024 + tiles - 1) / tiles;
-    if (split > steps / 8) split = steps / 8;
-    if (split > 64) split = 64;
-    float* part = dw;
-    if (split > 1) {
-        // the parts live BEHIND the first 4096 bytes of the offer (the arrival words of the forward's split-K protocol, which stay zero)
-        size_t have = 0;
-        void* sc = peek_scratch((hipStream_t)stream, &have);
-        have = have > SCRATCH_SYNC_BYTES ? have - SCRATCH_SYNC_BYTES : 0;
-        const long long fit = sc ? (long long)(have / ((size_t)out_elems * 4)) : 0;
-        if (fit < 2) split = 1;
-        else {
-            if (split > fit) split = fit;
-            part = (float*)((char*)take_scratch((hipStream_t)stream, SCRATCH_SYNC_BYTES + (size_t)split * out_elems * 4) + SCRATCH_SYNC_BYTES);
-        }
-    }
-    if (split < 1) split = 1;
-    long long chunk = ((steps + split - 1) / split) * LMP_S;
-    split = ((long long)M + chunk - 1) / chunk;                  // no empty part
-    if (split <= 1) part = dw;
-    LmpP p = {g, x, nullptr, part, (long long)N, (long long)M, K, (long long)N, (long long)K, lmp_vec_ok(g, N), lmp_vec_ok(x, K), chunk, 0};
-    set_kernel_name(split > 1 ? "linear_mp_wgrad_split_bf16" : "linear_mp_wgrad_bf16");
-    const int rc = lmp_launch<true, true>(p, (int)split, (hipStream_t)stream);
+    const LmpSplit sp = lmp_wgrad_split(tiles, M, out_elems, (hipStream_t)stream, dw);               // the M rows split over blocks
+    LmpP p = {g, x, nullptr, sp.part, (long long)N, (long long)M, K, (long long)N, (long long)K, lmp_vec_ok(g, N), lmp_vec_ok(x, K), sp.chunk, 0};
+    set_kernel_name(sp.split > 1 ? "linear_mp_wgrad_split_bf16" : "linear_mp_wgrad_bf16");
+    const int rc = lmp_launch<true, true>(p, (int)sp.split, (hipStream_t)stream);
     if (rc != MV_OK) return rc;
-    if (split > 1)
-        hipLaunchKernelGGL(lmp_sum_parts_kernel, dim3((unsigned)((out_elems + 255) / 256)), dim3(256), 0, (hipStream_t)stream, part, dw,
-                           out_elems, (int)split);
+    if (sp.split > 1) sum_parts((hipStream_t)stream, sp.part, dw, out_elems, (int)sp.split);
     MV_LAUNCH_CHECK();
     return MV_OK;
 }

@@ -1,6 +1,8 @@
 // The 128 x 128 x 32 bf16 tile of the mixed-precision training kernels (linear_mp.hip, conv_mp.hip): staging of an fp32 operand patch
-// through registers into its bf16 LDS image, the MFMA fragments read back from it, one k-step of 32 on v_mfma_f32_32x32x16_bf16, and
-// the in-order sum of the parts of a split reduction.
+// through registers into its bf16 LDS image, the MFMA fragments read back from it, one k-step of 32 on v_mfma_f32_32x32x16_bf16, the
+// double-buffered loop over a tile's reduction (lmp_reduce), the store of a tile (lmp_store_tile) and, on the host, how a weight
+// gradient splits its reduction over parts (lmp_wgrad_split).  A kernel keeps what is its own: which tile a block computes, its range of
+// the reduction, how its two patches are loaded and where its output lies.
 //
 // LDS images (bf16), both 10240 bytes per operand and buffer:
 //   contiguous operand  [128 rows][32 k] with 80-byte rows: a lane's fragment is one ds_read_b128 at row * 80 + 32 * ks + 16 * h; the
@@ -101,19 +103,89 @@ __device__ __forceinline__ void lmp_mma_step(f32x16 (&acc)[2][2], const char* im
     }
 }
 
-// out[i] = part[0][i] + part[1][i] + ... in index order: the split weight gradient is bit-reproducible
-__global__ void lmp_sum_parts_kernel(const float* __restrict__ part, float* __restrict__ out, long long n, int parts) {
-    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    float acc = part[i];
-    for (int s = 1; s < parts; ++s) acc += part[(long long)s * n + i];
-    out[i] = acc;
+// The reduction of one 128 x 128 tile over `steps` steps of 32: LDS double-buffered with the next step's patches in flight in registers,
+// one barrier per step.  load(va, vb) fills the two patches of the next step: it is called exactly once per step, in step order, and keeps
+// its own place in the reduction between calls.  Clears acc; wave w of the 4 owns rows 64 (w >> 1) .., columns 64 (w & 1) .. .
+template <bool TA, bool TB, class Load>
+__device__ __forceinline__ void lmp_reduce(f32x16 (&acc)[2][2], char (&lds)[2][2][LMP_IMG], int steps, int t, Load&& load) {
+    const int lane = t & 63, wave = t >> 6;
+    const int wr = (wave >> 1) * 64, wc = (wave & 1) * 64;
+#pragma unroll
+    for (int a = 0; a < 2; ++a)
+#pragma unroll
+        for (int b = 0; b < 2; ++b)
+#pragma unroll
+            for (int e = 0; e < 16; ++e) acc[a][b][e] = 0.f;
+
+    float4 va[4], vb[4];
+    if (steps > 0) {
+        load(va, vb);
+        lmp_lstore<TA>(lds[0][0], va, t);
+        lmp_lstore<TB>(lds[0][1], vb, t);
+    }
+    __syncthreads();
+    for (int s = 0; s < steps; ++s) {
+        const int cur = s & 1;
+        const bool more = s + 1 < steps;
+        if (more) load(va, vb);
+        lmp_mma_step<TA, TB>(acc, lds[cur][0], lds[cur][1], wr, wc, lane);
+        if (more) {                          // the other buffer was last read in step s - 1, a barrier ago
+            lmp_lstore<TA>(lds[cur ^ 1][0], va, t);
+            lmp_lstore<TB>(lds[cur ^ 1][1], vb, t);
+        }
+        __syncthreads();
+    }
+}
+
+// Stores a tile (+ bias[j], fp32, if given).  C/D map of the 32x32 MFMA: column = lane & 31, row = (e & 3) + 8 (e >> 2) + 4 (lane >> 5): a
+// register is one 128-byte row segment.  `ctile` points at column 0 of the tile's first row, `rows` (<= 128) of which exist; the columns
+// are j0 .. below J.  Offsets from ctile are 32-bit: 128 rows of a pitch of at most LMP_MAX_DIM stay below 2^28 elements, whatever the
+// number of rows of the whole output.
+__device__ __forceinline__ void lmp_store_tile(const f32x16 (&acc)[2][2], float* ctile, unsigned ldc, int rows, int j0, int J,
+                                               const float* bias, int t) {
+    const int lane = t & 63, wave = t >> 6;
+    const int wc = (wave & 1) * 64, row = (wave >> 1) * 64 + 4 * (lane >> 5);          // this lane's first row
+#pragma unroll
+    for (int b = 0; b < 2; ++b) {
+        const int j = j0 + wc + 32 * b + (lane & 31);
+        const bool jok = j < J;
+        const float bj = (bias && jok) ? bias[j] : 0.f;
+        const unsigned off = (unsigned)row * ldc + (unsigned)j;
+#pragma unroll
+        for (int a = 0; a < 2; ++a) {
+#pragma unroll
+            for (int e = 0; e < 16; ++e) {
+                const int up = 32 * a + (e & 3) + 8 * (e >> 2);                        // the same for every lane: a scalar base
+                if (jok && row + up < rows) (ctile + (size_t)up * ldc)[off] = acc[a][b][e] + bj;
+            }
+        }
+    }
 }
 
 inline int lmp_vec_ok(const float* ptr, long long pitch) { return ((uintptr_t)ptr & 15) == 0 && (pitch & 3) == 0; }
 
 // the largest pitch of a contiguous operand whose 128-row tile stays below 2^31 bytes from its descriptor's base
 constexpr int LMP_MAX_DIM = 1 << 21;
+
+// How a weight gradient of `tiles` output tiles splits its reduction of `red` elements: about 1024 workgroups (~4 per CU), every part at
+// least 8 steps, at most 64 parts, no more than the scratch on offer holds (none below two: take_scratch_parts), then no empty part.
+// `part`: where the kernel writes -- the parts [split][out_elems] in the scratch, or `direct` when it does not split.
+struct LmpSplit {
+    float* part;
+    long long split, chunk;                  // parts; reduction elements per part (a multiple of LMP_S)
+};
+inline LmpSplit lmp_wgrad_split(long long tiles, long long red, long long out_elems, hipStream_t stream, float* direct) {
+    const long long steps = (red + LMP_S - 1) / LMP_S;
+    long long split = tiles >= 1024 ? 1 : (1024 + tiles - 1) / tiles;
+    if (split > steps / 8) split = steps / 8;
+    if (split > 64) split = 64;
+    float* part = nullptr;
+    if (split > 1) split = take_scratch_parts(stream, split, 2, out_elems, &part);
+    if (split < 1) split = 1;
+    const long long chunk = ((steps + split - 1) / split) * LMP_S;
+    split = (red + chunk - 1) / chunk;
+    return {split > 1 ? part : direct, split, chunk};
+}
 
 }  // namespace
 }  // namespace mv

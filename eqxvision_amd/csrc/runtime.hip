@@ -45,6 +45,20 @@ void* peek_scratch(hipStream_t stream, size_t* bytes) {       // what is on offe
     if (bytes) *bytes = g_scratch.bytes;
     return g_scratch.ptr;
 }
+// Bytes [0, SCRATCH_SYNC_BYTES) of every offer are the arrival words of the forward's split-K protocol (header: mv_set_scratch) and must
+// stay zero between launches.  The parts of a split reduction therefore live BEHIND them: an offer such an entry takes, or leaves
+// unused, can never hand a later split-K launch a dirty sync area.
+long long take_scratch_parts(hipStream_t stream, long long want, long long least, long long part_elems, float** part) {
+    *part = nullptr;
+    size_t have = 0;
+    void* sc = peek_scratch(stream, &have);
+    have = have > SCRATCH_SYNC_BYTES ? have - SCRATCH_SYNC_BYTES : 0;
+    const long long fit = sc ? (long long)(have / ((size_t)part_elems * 4)) : 0;
+    const long long parts = want < fit ? want : fit;
+    if (parts < least || parts < 1) return 0;
+    *part = (float*)((char*)take_scratch(stream, SCRATCH_SYNC_BYTES + (size_t)parts * part_elems * 4) + SCRATCH_SYNC_BYTES);
+    return parts;
+}
 int get_flag(const char* name) {
     if (g_flags.empty()) return 0;
     auto it = g_flags.find(name);

@@ -228,13 +228,16 @@ __global__ __launch_bounds__(256) void colsum_part_kernel(const float* __restric
     __syncthreads();
     if (rg == 0 && c < C) part[(long long)blockIdx.y * C + c] = (sh[0][cl] + sh[1][cl]) + (sh[2][cl] + sh[3][cl]);
 }
-// out[i] = part[0][i] + part[1][i] + ... (fixed order: bit-reproducible)
+// out[i] = 0 + part[0][i] + part[1][i] + ... in index order: a split reduction is bit-reproducible.  Starting from +0 and not from
+// part[0][i] changes no bit of a sum whose parts are never -0: under round-to-nearest x + y is -0 only when both are -0, and a part of
+// the bf16 weight gradients (linear_mp.hip, conv_mp.hip) is an MFMA accumulation that itself started from +0.  Grid-stride: blocks_for
+// caps the grid at 65535 * 16 blocks of 256, and those two entries allow more outputs than that.
 __global__ void sum_parts_kernel(const float* __restrict__ part, float* __restrict__ out, long long n, int parts) {
-    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    float acc = 0.f;
-    for (int s = 0; s < parts; ++s) acc += part[(long long)s * n + i];
-    out[i] = acc;
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
+        float acc = 0.f;
+        for (int s = 0; s < parts; ++s) acc += part[(long long)s * n + i];
+        out[i] = acc;
+    }
 }
 
 // Weight gradient on the fp32 matrix cores: for one filter tap (r, s), dW[k][c] = sum over output positions of dy[pos][k] * x[pos @ (r, s)][c]
@@ -605,6 +608,10 @@ inline unsigned blocks_for(long long n, int per) {
 
 }  // namespace
 
+void sum_parts(hipStream_t stream, const float* part, float* out, long long n, int parts) {
+    hipLaunchKernelGGL(sum_parts_kernel, dim3(blocks_for(n, 256)), dim3(256), 0, stream, part, out, n, parts);
+}
+
 }  // namespace mv
 
 extern "C" {
@@ -650,28 +657,14 @@ int mv_conv2d_wgrad_nhwc_f32(const float* x, const float* dy, float* dw_krsc, in
         long long split = tiles >= 2048 ? 1 : (4096 + tiles - 1) / tiles;
         if (split > (P + 127) / 128) split = (P + 127) / 128;
         if (split > 1024) split = 1024;
-        float* part = dw_krsc;
-        if (split > 1) {
-            // partial sums live BEHIND the first 4096 bytes of the offer: those are the arrival words of the forward's split-K
-            // protocol (header: mv_set_scratch) and stay zero, so an offer this entry leaves unused can never hand a later
-            // split-K launch a dirty sync area
-            size_t have = 0;
-            void* sc = peek_scratch((hipStream_t)stream, &have);
-            have = have > SCRATCH_SYNC_BYTES ? have - SCRATCH_SYNC_BYTES : 0;
-            const long long fit = sc ? (long long)(have / ((size_t)out_elems * 4)) : 0;
-            if (fit < 2) split = 1;
-            else {
-                if (split > fit) split = fit;
-                part = (float*)((char*)take_scratch((hipStream_t)stream, SCRATCH_SYNC_BYTES + (size_t)split * out_elems * 4) + SCRATCH_SYNC_BYTES);
-            }
-        }
+        float* part = nullptr;
+        if (split > 1) split = take_scratch_parts((hipStream_t)stream, split, 2, out_elems, &part);
+        if (split <= 1) { split = 1; part = dw_krsc; }
         const long long chunk = ((P + split - 1) / split + 1) & ~1LL;                 // even: a pair of positions never straddles two chunks
         set_kernel_name("conv_wgrad_mfma_f32");
         hipLaunchKernelGGL(conv_wgrad_mfma_kernel, dim3((unsigned)tiles, (unsigned)split), dim3(64), 0, (hipStream_t)stream, x, dy, part, N, H,
                            W, C, K, R, S, Ho, Wo, sh, sw, ph, pw, dh, dw, groups, P, chunk, ktiles, ctiles);
-        if (split > 1)
-            hipLaunchKernelGGL(sum_parts_kernel, dim3(blocks_for(out_elems, 256)), dim3(256), 0, (hipStream_t)stream, part, dw_krsc,
-                               out_elems, (int)split);
+        if (split > 1) sum_parts((hipStream_t)stream, part, dw_krsc, out_elems, (int)split);
         MV_LAUNCH_CHECK();
         return MV_OK;
     }
@@ -717,19 +710,15 @@ int mv_colsum_f32(const float* a, const float* b, float* out, int64_t M, int C, 
     // many rows, few columns (bias / BatchNorm gradients over a feature map): rows split over blocks, parts in the caller's scratch
     long long split = M >= 512 ? (M + 255) / 256 : 1;
     if (split > 512) split = 512;
-    if (split > 1) {
-        char* sc = (char*)take_scratch((hipStream_t)stream, SCRATCH_SYNC_BYTES + (size_t)split * C * 4);
-        float* part = sc ? (float*)(sc + SCRATCH_SYNC_BYTES) : nullptr;          // behind the split-K sync area (see conv wgrad)
-        if (part) {
-            const long long chunk = (M + split - 1) / split;
-            set_kernel_name("colsum_split_f32");
-            hipLaunchKernelGGL(colsum_part_kernel, dim3((unsigned)((C + 63) / 64), (unsigned)split), dim3(256), 0, (hipStream_t)stream, a, b,
-                               part, (long long)M, C, chunk);
-            hipLaunchKernelGGL(sum_parts_kernel, dim3(blocks_for(C, 256)), dim3(256), 0, (hipStream_t)stream, part, out, (long long)C,
-                               (int)split);
-            MV_LAUNCH_CHECK();
-            return MV_OK;
-        }
+    float* part = nullptr;
+    if (split > 1 && take_scratch_parts((hipStream_t)stream, split, split, C, &part)) {          // all the parts or none
+        const long long chunk = (M + split - 1) / split;
+        set_kernel_name("colsum_split_f32");
+        hipLaunchKernelGGL(colsum_part_kernel, dim3((unsigned)((C + 63) / 64), (unsigned)split), dim3(256), 0, (hipStream_t)stream, a, b,
+                           part, (long long)M, C, chunk);
+        sum_parts((hipStream_t)stream, part, out, C, (int)split);
+        MV_LAUNCH_CHECK();
+        return MV_OK;
     }
     set_kernel_name("colsum_f32");
     hipLaunchKernelGGL(colsum_kernel, dim3((unsigned)((C + 63) / 64)), dim3(256), 0, (hipStream_t)stream, a, b, out, (long long)M, C);

@@ -15,7 +15,7 @@ import functools
 import numpy as np
 
 from tests import _strict as S
-from tests._linear_mp_ref import _cover, _ties, rne_bf16
+from tests._linear_mp_ref import _cover, _ties, prove_round_core, rne_bf16, wgrad_split_rule
 
 F64 = np.float64
 ENTRIES = ("fwd", "dgrad", "wgrad")
@@ -198,41 +198,15 @@ def operands_of(entry, x, w, dy):
 
 
 def prove_round_case(entry, g, ref, mag, x, w, dy, bias):
-    """The preconditions of the rounding-visible case, on the values times 2^16: integers below 2^24 (S.prove_exact, frac_bits = 16), every
-    operand of magnitude in [0.5, 2), every tie class present in both operands, the bias not a bf16 value."""
+    """_linear_mp_ref.prove_round_core on this entry's operands, for a reduction of 16."""
     assert kred_of(entry, g) == 16
-    S.prove_exact(f"conv_mp/{entry}/round", ref, mag, weights_of(entry, g, x, w, dy), out="fp32", frac_bits=16)
-    for name, t in zip(("a", "b"), operands_of(entry, x, w, dy)):
-        k = np.rint(np.asarray(t, F64) * 1024).astype(np.int64)
-        assert np.array_equal(k.astype(F64) * 2.0 ** -10, np.asarray(t, F64)) and (np.abs(k) >= 512).all() and (np.abs(k) <= 2047).all(), name
-        tie = (np.abs(k) % 8 == 4) & (np.abs(k) >= 1024)
-        par = (np.abs(k) >> 3) & 1
-        for sign in (-1, 1):
-            for p_ in (0, 1):
-                assert (tie & (np.sign(k) == sign) & (par == p_)).any(), f"{entry}/{name}: no tie of sign {sign}, parity {p_}"
-        assert (np.abs(k) % 8 == 3).any() and (np.abs(k) % 8 == 5).any(), f"{entry}/{name}: no value beside a tie"
-        r = np.asarray(rne_bf16(t), F64) * 256
-        assert np.array_equal(np.rint(r), r) and (np.abs(r) <= 512).all(), f"{entry}/{name}: rounded operand not a multiple of 2^-8 below 2"
-    if entry == "fwd":
-        assert (np.abs(bias) <= 32).all() and (rne_bf16(bias) != bias).all(), "a bias element is a bf16 value"
-    assert float(np.abs(mag).max()) < 2.0 ** 7
+    prove_round_core("conv_mp", entry, ref, mag, weights_of(entry, g, x, w, dy), operands_of(entry, x, w, dy), bias)
 
 
-# ------------------------------------------------------------------------------------------------ wgrad's split (conv_mp.hip)
+# ------------------------------------------------------------------------------------------------ wgrad's split
 def wgrad_split(g, offer=None):
-    """(parts the entry wants, parts it runs with `offer` bytes of scratch, positions per part): mv_conv2d_mp_wgrad's rule -- one tile per
-    (128 filters, tap, 128 channels); about 1024 workgroups, at least 8 steps of 32 positions per part, at most 64 parts, as many as the
-    offer holds behind its first 4096 bytes, none below two."""
-    tiles = -(-g.K // TILE) * g.R * g.S * -(-g.C // TILE)
-    steps = -(-g.P // KSTEP)
-    want = 1 if tiles >= 1024 else -(-1024 // tiles)
-    want = max(1, min(want, steps // 8, 64))
-    split = want
-    if split > 1:
-        fit = 0 if offer is None else max(0, offer - 4096) // (g.out_elems * 4)
-        split = 1 if fit < 2 else min(split, fit)
-    chunk = -(-steps // split) * KSTEP
-    return want, -(-g.P // chunk), chunk
+    """mv_conv2d_mp_wgrad: one tile per (128 filters, tap, 128 channels) of dw [K, R, S, C], the reduction runs over the P positions."""
+    return wgrad_split_rule(-(-g.K // TILE) * g.R * g.S * -(-g.C // TILE), g.P, g.out_elems, offer)
 
 
 # ------------------------------------------------------------------------------------------------ the rule

@@ -172,12 +172,12 @@ def gauss_case(M, N, K, seed=13):
     return x, w, g, bias
 
 
-def prove_round_case(entry, ref, mag, x, w, g, bias):
-    """The preconditions of the rounding-visible case, on the values times 2^16: integers below 2^24 (S.prove_exact, frac_bits = 16), every
-    operand of magnitude in [0.5, 2), every tie class present, the bias not a bf16 value."""
-    a, b = _operands(entry, x, w, g)
-    S.prove_exact(f"linear_mp/{entry}/round", ref, mag, [a, b], out="fp32", frac_bits=16)
-    for name, t in (("a", a), ("b", b)):
+def prove_round_core(label, entry, ref, mag, weights, operands, bias):
+    """The preconditions of a rounding-visible case (this file's and tests/_conv_mp_ref.py's), on the values times 2^16: integers below 2^24
+    (S.prove_exact on `weights`, frac_bits = 16), both `operands` of magnitude in [0.5, 2) with every tie class present, the bias not a
+    bf16 value."""
+    S.prove_exact(f"{label}/{entry}/round", ref, mag, weights, out="fp32", frac_bits=16)
+    for name, t in zip(("a", "b"), operands):
         k = np.rint(np.asarray(t, F64) * 1024).astype(np.int64)
         assert np.array_equal(k.astype(F64) * 2.0 ** -10, np.asarray(t, F64)) and (np.abs(k) >= 512).all() and (np.abs(k) <= 2047).all(), name
         tie = (np.abs(k) % 8 == 4) & (np.abs(k) >= 1024)
@@ -194,20 +194,31 @@ def prove_round_case(entry, ref, mag, x, w, g, bias):
     assert float(np.abs(mag).max()) < 2.0 ** 7
 
 
-# ------------------------------------------------------------------------------------------------ wgrad's split (linear_mp.hip)
-def wgrad_split(M, N, K, offer=None):
-    """(parts the entry wants, parts it runs with `offer` bytes of scratch): mv_linear_mp_wgrad's rule -- about 1024 workgroups, at least
-    8 steps of 32 rows per part, at most 64 parts, as many as the offer holds behind its first 4096 bytes, none below two."""
-    tiles = -(-N // TILE) * -(-K // TILE)
-    steps = -(-M // KSTEP)
+def prove_round_case(entry, ref, mag, x, w, g, bias):
+    """prove_round_core on this entry's two operands (which are also the matrices S.prove_exact's coverage looks at)."""
+    a, b = _operands(entry, x, w, g)
+    prove_round_core("linear_mp", entry, ref, mag, [a, b], (a, b), bias)
+
+
+# ------------------------------------------------------------------------------------------------ wgrad's split (linear_mp_tile.h)
+def wgrad_split_rule(tiles, red, out_elems, offer=None):
+    """(parts wanted, parts run with `offer` bytes of scratch, reduction elements per part): lmp_wgrad_split's rule for a weight gradient
+    of `tiles` output tiles, reduction length `red` and `out_elems` outputs -- about 1024 workgroups, at least 8 steps of 32 per part, at
+    most 64 parts, as many as the offer holds behind its first 4096 bytes, none below two; then no empty part."""
+    steps = -(-red // KSTEP)
     want = 1 if tiles >= 1024 else -(-1024 // tiles)
     want = max(1, min(want, steps // 8, 64))
     split = want
     if split > 1:
-        fit = 0 if offer is None else max(0, offer - 4096) // (N * K * 4)
+        fit = 0 if offer is None else max(0, offer - 4096) // (out_elems * 4)
         split = 1 if fit < 2 else min(split, fit)
     chunk = -(-steps // split) * KSTEP
-    return want, -(-M // chunk), chunk
+    return want, -(-red // chunk), chunk
+
+
+def wgrad_split(M, N, K, offer=None):
+    """mv_linear_mp_wgrad: 128 x 128 tiles of dw [N, K], the reduction runs over the M rows."""
+    return wgrad_split_rule(-(-N // TILE) * -(-K // TILE), M, N * K, offer)
 
 
 # ------------------------------------------------------------------------------------------------ the model case (vit)

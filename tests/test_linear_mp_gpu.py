@@ -7,7 +7,7 @@ float64 on the bf16-rounded operands.
 
 1. exact, integers in [-2, 2], the seven shapes of R.SHAPES (odd K / N: the 4-byte load path; (1, 1, 1): a tile that is all edge).
 2. exact with the rounding visible: operands k 2^-10 with every tie, reduction 16, a bias that is no bf16 value.
-3. wgrad under every scratch regime: bit-equal, bytes [0, 4096) of the offer left zero.
+3. wgrad under every scratch regime: bit-equal, bytes [0, 4096) of the offer left zero; an offer it does not take stays on offer.
 4. Gaussian operands within S.elem_bound(ref, mag, kred, "fp32"), kred = the reduction length: holds for any summation order (a tree over
    n terms is at most n - 1 deep, so the split adds no term).
 5. the rule: g_linear under "bf16" (y, dx, dW, db; a frozen weight launches no wgrad; the head stays on the fp32 kernel).
@@ -103,6 +103,25 @@ def test_wgrad_scratch_regimes(M):
         results.append(got)
     for r in results[1:]:
         assert np.array_equal(r, results[0])
+
+
+def test_wgrad_leaves_an_offer_it_does_not_take():
+    """An offer with room for one part: mv_linear_mp_wgrad (1030 x 17 x 9 wants 4 parts) runs unsplit and only LOOKS at the offer, so the
+    next launch on the stream, with no new mv_set_scratch, still finds it: mv_colsum_f32 on 515 x 2 (3 parts, 4096 + 24 bytes) splits."""
+    M, N, K = 1030, 17, 9
+    offer = SYNC + int(1.5 * N * K * 4)
+    assert R.wgrad_split(M, N, K)[0] == 4 and R.wgrad_split(M, N, K, offer)[1] == 1
+    assert SYNC + 24 <= offer < SYNC + 2 * N * K * 4 and S.colsum_split(515) == (3, 172)
+    x, w, g, _ = R.int_case(M, N, K)
+    ref, mag = R.product_ref("wgrad", x, w, g)
+    S.prove_exact("linear_mp/wgrad/untaken", ref, mag, list(R._operands("wgrad", x, w, g)), out="fp32")
+    a = S.int_tensor(S.rng_of(71), (515, 2), 2)
+    xd, gd, ad = _f(x), _f(g), _f(a)
+    with _Scratch(offer):
+        got, kern = _run("mv_linear_mp_wgrad", lambda y: (_p(gd), _p(xd), y, M, N, K, _stream()), (N, K), "fp32")
+        col, ckern = _run("mv_colsum_f32", lambda y: (_p(ad), None, y, 515, 2, _stream()), (2,), "fp32")
+    _judge("linear_mp/wgrad/untaken_offer", kern, KERNEL["wgrad"], got, ref, "fp32")
+    _judge("linear_mp/wgrad/untaken_offer/colsum_after", ckern, "colsum_split_f32", col, S.colsum_ref(a, None)[0], "fp32")
 
 
 # ================================================================================================ 4. bounded, Gaussian

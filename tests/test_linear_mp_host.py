@@ -113,6 +113,57 @@ def test_wgrad_split_of_the_regime_cases():
     assert R.wgrad_split(788, 192, 768, 8 << 20)[1] > 1 and R.wgrad_split(257, 96, 40, 8 << 20)[1] == 1
 
 
+def _old_linear_split(M, N, K, offer=None):
+    """The formula _linear_mp_ref.wgrad_split had before it was shared with _conv_mp_ref, verbatim."""
+    TILE, KSTEP = 128, 32
+    tiles = -(-N // TILE) * -(-K // TILE)
+    steps = -(-M // KSTEP)
+    want = 1 if tiles >= 1024 else -(-1024 // tiles)
+    want = max(1, min(want, steps // 8, 64))
+    split = want
+    if split > 1:
+        fit = 0 if offer is None else max(0, offer - 4096) // (N * K * 4)
+        split = 1 if fit < 2 else min(split, fit)
+    chunk = -(-steps // split) * KSTEP
+    return want, -(-M // chunk), chunk
+
+
+def _old_conv_split(g, offer=None):
+    """The formula _conv_mp_ref.wgrad_split had, verbatim."""
+    TILE, KSTEP = 128, 32
+    tiles = -(-g.K // TILE) * g.R * g.S * -(-g.C // TILE)
+    steps = -(-g.P // KSTEP)
+    want = 1 if tiles >= 1024 else -(-1024 // tiles)
+    want = max(1, min(want, steps // 8, 64))
+    split = want
+    if split > 1:
+        fit = 0 if offer is None else max(0, offer - 4096) // (g.out_elems * 4)
+        split = 1 if fit < 2 else min(split, fit)
+    chunk = -(-steps // split) * KSTEP
+    return want, -(-g.P // chunk), chunk
+
+
+def test_shared_wgrad_split_is_both_old_formulas():
+    """The one rule (R.wgrad_split_rule, behind R.wgrad_split and _conv_mp_ref.wgrad_split) against the two formulas it replaced, exactly,
+    over 1 / 2 / 9 / 1023 / 1024 tiles, reductions around the 8-step and the part boundaries, and offers around one and two parts."""
+    import types
+
+    from tests import _conv_mp_ref as CR
+    T = 128
+    linear = {1: (1, 1), 2: (T + 1, 1), 9: (3 * T, 3 * T), 1023: (33 * T, 31 * T), 1024: (32 * T, 32 * T)}        # tiles: (N, K)
+    conv = {1: (1, 1, 1, 1), 2: (1, 2, 1, 1), 9: (1, 3, 3, 1), 1023: (31 * T, 3, 11, 1), 1024: (32 * T, 4, 8, 1)}  # tiles: (K, R, S, C)
+    for tiles in (1, 2, 9, 1023, 1024):
+        N, K = linear[tiles]
+        ck, cr, cs, cc = conv[tiles]
+        assert -(-N // T) * -(-K // T) == tiles and -(-ck // T) * cr * cs * -(-cc // T) == tiles
+        for red in (1, 255, 256, 257, 1030, 18145):
+            g = types.SimpleNamespace(K=ck, R=cr, S=cs, C=cc, P=red, out_elems=ck * cr * cs * cc)
+            for out, old, new in ((N * K, lambda o: _old_linear_split(red, N, K, o), lambda o: R.wgrad_split(red, N, K, o)),
+                                  (g.out_elems, lambda o: _old_conv_split(g, o), lambda o: CR.wgrad_split(g, o))):
+                for offer in (None, 4096, 4096 + out * 4, 4096 + 2 * out * 4, 4096 + 2 * out * 4 - 1, 4096 + 100 * out * 4):
+                    assert new(offer) == old(offer) == R.wgrad_split_rule(tiles, red, out, offer), (tiles, red, out, offer)
+
+
 # ================================================================================================ the model references
 def test_vit_emulation_is_above_fp32_noise():
     """(b) against (a): the effect of rounding every Linear's operands to bf16 on the gradient, relative L2 over all parameters.  It has

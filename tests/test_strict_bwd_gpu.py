@@ -9,7 +9,7 @@ worst |got - ref| / bound (`pytest -s`).
 Exact (np.array_equal with the float64 reference; `S.prove_exact(..., out="fp32")` asserted before each launch; operands are integers
 in [-2, 2], probabilities multiples of 1/8): mv_conv2d_dgrad_nhwc_f32 and mv_conv2d_wgrad_nhwc_f32 at the eleven shapes of
 S.CONV_BWD_SHAPES on the matrix-core and on the VALU path (the weight gradient without scratch, with 8 MiB, with room for two parts
-and with room for one; bytes [0, 4096) of the offer must stay zero), mv_colsum_f32 with and without scratch, mv_softmax_bwd_f32,
+and with room for one; bytes [0, 4096) of the offer must stay zero), mv_colsum_f32 with and without scratch and with an offer one part short, mv_softmax_bwd_f32,
 mv_mha_bwd_f32 (dqkv and ds_scratch), mv_maxpool2d_bwd_nhwc_f32 (distinct integers per channel, also all below -1),
 mv_patch_merge_gather_bwd_f32 at odd sizes, mv_transpose2d_f32 with a row stride, mv_scatter_rows_sum_f32.
 Bounded on Gaussian operands:
@@ -211,6 +211,26 @@ def test_colsum(M, C, product, kind):
             got, kern = _run("mv_colsum_f32", lambda y: (_p(ad), _p(bd), y, M, C, _stream()), (C,), "fp32")
         _judge(f"colsum/{M}x{C}/{'product' if product else 'sum'}/{kind}/split{split}", kern, "colsum_split_f32" if split > 1 else "colsum_f32",
                got, ref, "fp32", **({} if kind == "int" else {"mag": mag, "n_ops": S.colsum_n_ops(M, split)}))
+
+
+def test_colsum_takes_all_its_parts_or_none():
+    """1030 x 70 wants 5 parts, i.e. 4096 + 5 * 70 * 4 bytes.  An offer with room for 4 is left alone: colsum_f32, bit-equal to the run
+    without an offer (and to S.emu_colsum's single part), and not one byte of the offer written."""
+    M, C = 1030, 70
+    assert S.colsum_split(M)[0] == 5
+    a = S.rng_of(67).standard_normal((M, C)).astype(np.float32)
+    ad = _f(a)
+    runs = []
+    for offer in (None, SYNC + 4 * C * 4):
+        with _Scratch(offer) as sc:
+            got, kern = _run("mv_colsum_f32", lambda y: (_p(ad), None, y, M, C, _stream()), (C,), "fp32")
+        print(f"colsum/all_or_nothing/offer {offer}: served by {kern}")
+        assert kern == "colsum_f32"
+        if offer is not None:
+            assert not bool(sc.ws.any()), "an offer that is too small for every part was written"
+        runs.append(np.asarray(got, np.float32))
+    assert np.array_equal(runs[0].view(np.uint32), runs[1].view(np.uint32))
+    assert np.array_equal(runs[0].view(np.uint32), S.emu_colsum(a, None, 1).view(np.uint32))
 
 
 # ================================================================================================ softmax_bwd / mha_bwd
