@@ -14,13 +14,10 @@
 //                      and V^T fragments are two 8-byte LDS reads per lane.
 // Whole-row softmax (N <= 256 keys held in accumulators): no online rescaling needed for ViT's
 // N = 197.  Longer sequences / odd head sizes use the generic kernel.
-#include "common.h"
 #include "rng_common.h"
+#include "swin_attn_core.h"      // p_frag: the accumulator -> P operand pack (and the register / key order, written there)
 
 namespace mv {
-
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 template <int DH, int NT, bool HM, bool PR>
 __global__ __launch_bounds__(512) void mha_mfma_kernel(const bf16_t* __restrict__ qkv, bf16_t* __restrict__ out,
@@ -267,16 +264,10 @@ __global__ __launch_bounds__(512) void mha_mfma_kernel(const bf16_t* __restrict_
                 for (int st = 0; st < PS; ++st) {
                     const int kt = st >> 1, t2 = st & 1;
                     if (st + PD < PS) rdv(st + PD);
-                    uint4 pf;
-                    pf.x = pack_bf2(sacc[kt][8 * t2 + 0], sacc[kt][8 * t2 + 1]);
-                    pf.y = pack_bf2(sacc[kt][8 * t2 + 2], sacc[kt][8 * t2 + 3]);
-                    pf.z = pack_bf2(sacc[kt][8 * t2 + 4], sacc[kt][8 * t2 + 5]);
-                    pf.w = pack_bf2(sacc[kt][8 * t2 + 6], sacc[kt][8 * t2 + 7]);
+                    const bf16x8 pf = p_frag(sacc[kt], t2);
 #pragma unroll
                     for (int dt = 0; dt < DT; ++dt)
-                        oacc[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, vf[st][dt]),
-                                                                           __builtin_bit_cast(bf16x8, pf), oacc[dt], 0,
-                                                                           0, 0);
+                        oacc[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, vf[st][dt]), pf, oacc[dt], 0, 0, 0);
                     __builtin_amdgcn_sched_barrier(0);
                     if (st == PS / 2) {
                         // half of the score registers are dead by now: fetch the Q fragments of the wave's tile of

@@ -7,13 +7,14 @@
 //   * one wave per (window, head): K and Q fragments (16 bytes = 8 channels of one token) come straight
 //     from global memory -- nothing is shared between waves except the head's bias table;
 //   * S^T = K.Q^T puts one query per lane: bias (+ shift mask, -100 like the reference) is added and the
-//     softmax is done on accumulator registers + one lane^32 exchange;
+//     softmax is done on accumulator registers + one lane^32 exchange (win_softmax, swin_attn_core.h: the
+//     fragment, register and key-order conventions are written there);
 //   * V is transposed through a wave-private LDS patch (key-contiguous) so the PV MFMA reads 8-byte fragments;
 //     the PV reduction index uses the accumulator's own register order (no cross-lane movement of P);
 //   * block = 4 waves sharing one head: the head's relative-position bias, padded to 64x64 fp32, is staged in
 //     LDS once per block and re-used for all the windows the block walks.
-#include "mfma_common.h"
 #include "rng_common.h"
+#include "swin_attn_core.h"
 #include "swin_geom.h"
 
 namespace mv {
@@ -22,7 +23,8 @@ struct SwinP {
     const bf16_t* qkv;
     const float* bias;     // [heads][n][n]
     bf16_t* out;
-    int B, Hf, Wf, C, heads, wsh, wsw, shh, shw;
+    int B, C, heads;
+    WindowGeom g;          // shift already dropped where the window covers the map (swin_check_geom)
     int n, nWw, nW, total_windows;
     const uint32_t* drop_keys;   // DROP: one Threefry key per sample, [B][2]
     float keep;
@@ -76,7 +78,7 @@ __global__ __launch_bounds__(256) void swin_attn_mfma_kernel(const SwinP p) {
 
     const int fr = lane & 31, fh = lane >> 5;
     const long long rs = 3LL * p.C;
-    const bool shifted = (p.shh + p.shw) > 0;
+    const bool shifted = (p.g.shh + p.g.shw) > 0;
     float scale = rsqrtf((float)DH);
     if constexpr (COS) scale = p.logit_mul[h];
     char* vt = vt_l[wave];
@@ -85,21 +87,9 @@ __global__ __launch_bounds__(256) void swin_attn_mfma_kernel(const SwinP p) {
     for (int win = blockIdx.x * 4 + wave; win < p.total_windows; win += gridDim.x * 4) {
         const int b = win / p.nW, wloc = win - b * p.nW;
         const int wy = wloc / p.nWw, wx = wloc - wy * p.nWw;
-        // token t of this window -> element offset of its qkv row (original, un-rolled position)
-        auto tok_row = [&](int t) -> long long {
-            const int ty = t / p.wsw, tx = t - ty * p.wsw;
-            int oy = wy * p.wsh + ty + p.shh, ox = wx * p.wsw + tx + p.shw;
-            if (oy >= p.Hf) oy -= p.Hf;
-            if (ox >= p.Wf) ox -= p.Wf;
-            return ((long long)b * p.Hf + oy) * p.Wf + ox;
-        };
-        auto region = [&](int t) {
-            const int ty = t / p.wsw, tx = t - ty * p.wsw;
-            const int y = wy * p.wsh + ty, x = wx * p.wsw + tx;          // rolled coordinates
-            const int rh = (y < p.Hf - p.wsh) ? 0 : (y < p.Hf - p.shh ? 1 : 2);
-            const int rw = (x < p.Wf - p.wsw) ? 0 : (x < p.Wf - p.shw ? 1 : 2);
-            return rh * 3 + rw;
-        };
+        // token t of this window -> its qkv / out row (original, un-rolled position) and its shift-mask region (swin_geom.h)
+        auto tok_row = [&](int t) { return swin_tok_row(p.g, b, wy, wx, t); };
+        auto region = [&](int t) { return swin_tok_region(p.g, wy, wx, t); };
         if (shifted) kreg[lane] = lane < n ? region(lane) : -1;
 
         // ---- V^T into LDS: each lane transposes 2 keys x 8 d (two items per lane cover 64 keys x 32 d)
@@ -170,39 +160,8 @@ __global__ __launch_bounds__(256) void swin_attn_mfma_kernel(const SwinP p) {
                     s[tk] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, kf[tk][kk]),
                                                                     __builtin_bit_cast(bf16x8, qf[tq][kk]), s[tk], 0, 0, 0);
             }
-            // scale, bias, mask; accumulator register e of key tile tk = key 32*tk + (e&3) + 8*(e>>2) + 4*fh
-            float mx = -INFINITY;
-#pragma unroll
-            for (int tk = 0; tk < 2; ++tk)
-#pragma unroll
-                for (int g = 0; g < 4; ++g) {
-                    const int key0 = tk * 32 + 8 * g + 4 * fh;
-                    const float4 bv = *(const float4*)(bias_l + (q & 63) * 64 + key0);
-                    int4 kr = make_int4(0, 0, 0, 0);
-                    if (shifted) kr = *(const int4*)(kreg + key0);
-                    const float bb[4] = {bv.x, bv.y, bv.z, bv.w};
-                    const int rr[4] = {kr.x, kr.y, kr.z, kr.w};
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) {
-                        float v = s[tk][4 * g + e] * scale + bb[e];
-                        if (shifted && rr[e] != qreg[tq]) v += -100.0f;
-                        if (key0 + e >= n) v = -INFINITY;
-                        s[tk][4 * g + e] = v;
-                        mx = fmaxf(mx, v);
-                    }
-                }
-            mx = fmaxf(mx, __shfl_xor(mx, 32));
-            float sum = 0.f;
-#pragma unroll
-            for (int tk = 0; tk < 2; ++tk)
-#pragma unroll
-                for (int e = 0; e < 16; ++e) {
-                    const float pe = __expf(s[tk][e] - mx);
-                    s[tk][e] = pe;
-                    sum += pe;
-                }
-            sum += __shfl_xor(sum, 32);
-            const float inv = 1.f / sum;
+            // scale, bias, mask, softmax on the accumulators (register -> key order: swin_attn_core.h)
+            const float inv = win_softmax<true>(s, scale, bias_l + (q & 63) * 64, kreg, qreg[tq], fh, shifted, n);
             if constexpr (DROP) {
                 const uint32_t k0 = p.drop_keys[2 * b], k1 = p.drop_keys[2 * b + 1];
                 const uint32_t nel = (uint32_t)p.nW * p.heads * n * n;
@@ -217,38 +176,21 @@ __global__ __launch_bounds__(256) void swin_attn_mfma_kernel(const SwinP p) {
                         s[tk][e] = on ? s[tk][e] * rk : 0.f;
                     }
             }
-            // O^T[d][q] = sum_key V^T[d][key] P[key][q]
+            // O^T[d][q] = sum_key V^T[d][key] P[key][q]; V^T rows are in key order: a step's fragment is two 8-byte pieces.
+            // (Own loop, not win_pv: through it hipcc keeps the V^T fragments of query tile 0 for tile 1, +16 VGPRs, 167 -> 183.)
             f32x16 o;
 #pragma unroll
             for (int e = 0; e < 16; ++e) o[e] = 0.f;
 #pragma unroll
-            for (int tk = 0; tk < 2; ++tk)
-#pragma unroll
-                for (int t2 = 0; t2 < 2; ++t2) {
-                    uint4 pf;
-                    pf.x = pack_bf2(s[tk][8 * t2 + 0], s[tk][8 * t2 + 1]);
-                    pf.y = pack_bf2(s[tk][8 * t2 + 2], s[tk][8 * t2 + 3]);
-                    pf.z = pack_bf2(s[tk][8 * t2 + 4], s[tk][8 * t2 + 5]);
-                    pf.w = pack_bf2(s[tk][8 * t2 + 6], s[tk][8 * t2 + 7]);
-                    const int key0 = tk * 32 + 16 * t2 + 4 * fh;
-                    const char* vrow = vt + fr * VPITCH + key0 * 2;
-                    const uint2 lo = *(const uint2*)(vrow);
-                    const uint2 hi = *(const uint2*)(vrow + 16);
-                    const uint4 vf = make_uint4(lo.x, lo.y, hi.x, hi.y);
-                    o = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, vf), __builtin_bit_cast(bf16x8, pf),
-                                                                o, 0, 0, 0);
-                }
-            if (q < n) {
-                bf16_t* dst = p.out + orow[tq] * p.C + h * DH;
-#pragma unroll
-                for (int g = 0; g < 4; ++g) {
-                    const int d = 8 * g + 4 * fh;
-                    uint2 u;
-                    u.x = pack_bf2(o[4 * g] * inv, o[4 * g + 1] * inv);
-                    u.y = pack_bf2(o[4 * g + 2] * inv, o[4 * g + 3] * inv);
-                    *(uint2*)(dst + d) = u;
-                }
+            for (int st = 0; st < 4; ++st) {
+                const bf16x8 pf = p_frag(s[st >> 1], st & 1);
+                const char* vrow = vt + fr * VPITCH + (16 * st + 4 * fh) * 2;
+                const uint2 lo = *(const uint2*)(vrow);
+                const uint2 hi = *(const uint2*)(vrow + 16);
+                const uint4 vf = make_uint4(lo.x, lo.y, hi.x, hi.y);
+                o = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, vf), pf, o, 0, 0, 0);
             }
+            if (q < n) store_quads_bf16((char*)(p.out + orow[tq] * p.C + h * DH + 4 * fh), o * inv);
         }
         wave_lds_fence();      // the next window's kreg / V^T overwrite what other lanes may still be reading
     }
@@ -265,7 +207,7 @@ int swin_mfma_launch(const void* qkv, const float* bias, void* out, int B, int H
     p.drop_keys = drop_keys; p.keep = keep;
     p.rnorm = rnorm; p.logit_mul = logit_mul;
     p.qkv = (const bf16_t*)qkv; p.bias = bias; p.out = (bf16_t*)out;
-    p.B = B; p.Hf = Hf; p.Wf = Wf; p.C = C; p.heads = heads; p.wsh = ws_h; p.wsw = ws_w; p.shh = shift_h; p.shw = shift_w;
+    p.B = B; p.C = C; p.heads = heads; p.g = {Hf, Wf, ws_h, ws_w, shift_h, shift_w};
     p.n = ws_h * ws_w;
     p.nWw = Wf / ws_w;
     p.nW = (Hf / ws_h) * p.nWw;

@@ -17,9 +17,11 @@
 //   proj      the same three-tiles-per-wave GEMM over the attention output; + bias -> fp32 tile in LDS
 //   epilogue  whole rows: + residual row (coalesced fp32 re-read), stored back to the token's own position (window reverse +
 //             roll back = the position it was gathered from)
+// Window geometry: swin_geom.h.  Softmax / P.V core and the fragment, register and key-order conventions: swin_attn_core.h.
 #include <type_traits>
 
-#include "mfma_common.h"
+#include "swin_attn_core.h"
+#include "swin_geom.h"
 
 namespace mv {
 
@@ -36,8 +38,61 @@ struct SwinBAP {
     int Hf, Wf, shh, shw, nWw, nW;
     float eps;
     int ablate;            // debug build only (w96_ablate): 1 no weight streaming, 2 no bias rows, 4 no stores, 8 no gather
-    long long* prof;       // experiments only (tools/time_swin_block_attn.py): per-wave wall-clock stamps at the phase boundaries
+    long long* prof;       // debug build only (tools/time_swin_block_attn.py): per-wave wall-clock stamps at the phase boundaries
 };
+
+// debug build only: bit of w96_ablate set -- a constant false in the product
+__device__ __forceinline__ bool ablated(const SwinBAP& p, int bit) {
+#ifdef MV_I8_PROF
+    return (p.ablate & bit) != 0;
+#else
+    return false;
+#endif
+}
+
+// LDS layouts, read by the kernels (offsets) and by the entry (dynamic-LDS bytes).  q, k rows: 32 dh (+ pad); v^T rows: 64 keys (+ pad)
+constexpr int QROW = 80, VROW = 144;
+template <int C, int NWIN, int NWV>
+struct SbaLayout {
+    static constexpr int NSLOT = NWV / 2, TR = 64 * NWIN;            // (head of group, window) slots; token rows per workgroup
+    // token rows of the normalised input / the attention output: 2 C bytes + 16 of padding (conflict-free 16-byte fragment reads);
+    // C = 96: the padding would not fit -- 16 bytes after every FOURTH row do the same job (192-byte rows start 48 dwords apart)
+    static constexpr int XBYTES = C == 96 ? TR * 192 + (TR / 4) * 16 : TR * (C * 2 + 16);
+    static __device__ constexpr int xoff(int r) { return C == 96 ? r * 192 + (r >> 2) * 16 : r * (C * 2 + 16); }
+    static constexpr int NX = 0;
+    static constexpr int Q = XBYTES;                                 // [NSLOT (head of group, window)][64 tokens][QROW]
+    static constexpr int K = Q + NSLOT * 64 * QROW;
+    static constexpr int V = K + NSLOT * 64 * QROW;                  // [NSLOT][32 dh][VROW]
+    static constexpr int O = V + NSLOT * 32 * VROW;
+    static constexpr int REG = O + XBYTES;                           // int[NWIN][64]: shift-mask region per token
+    static constexpr int BYTES = REG + NWIN * 256;
+    static constexpr int YROW = C * 4 + 16;                          // the fp32 result tile re-uses the space from 0
+    static_assert(TR * YROW <= O && BYTES <= 160 * 1024, "result tile must fit below the attention output");
+};
+struct Win96Layout {                                                 // k [3 heads][64 tokens][QROW], v^T [3][32 dh][VROW], regions int[64]
+    static constexpr int K = 0, V = 3 * 64 * QROW, REG = V + 3 * 32 * VROW, BYTES = REG + 256;
+    static constexpr int YP = 100;                                   // floats per staged result row (96 + 4: conflict-free 16-byte pieces)
+    static_assert(2 * (32 * YP + 64) * 4 <= BYTES, "the result tiles re-use the k / v space");
+};
+
+// GEMM accumulator + bias: register 4 gq + i = channel 8 gq + 4 fh + i of the 32-channel tile; bb = the tile's bias + 4 fh
+__device__ __forceinline__ f32x16 add_bias(const f32x16& acc, const float* bb) {
+    f32x16 v;
+#pragma unroll
+    for (int gq = 0; gq < 4; ++gq) {
+        const float4 bv = *(const float4*)(bb + 8 * gq);
+        v[4 * gq + 0] = acc[4 * gq + 0] + bv.x; v[4 * gq + 1] = acc[4 * gq + 1] + bv.y;
+        v[4 * gq + 2] = acc[4 * gq + 2] + bv.z; v[4 * gq + 3] = acc[4 * gq + 3] + bv.w;
+    }
+    return v;
+}
+// the lane's token as one column of v^T[dh][slot]: dst = the head's v^T + 2 vt_slot(token block, fr)
+__device__ __forceinline__ void store_vt(char* dst, const f32x16& v, int fh) {
+#pragma unroll
+    for (int gq = 0; gq < 4; ++gq)
+#pragma unroll
+        for (int e = 0; e < 4; ++e) *(bf16_t*)(dst + (8 * gq + 4 * fh + e) * VROW) = f2bf(v[4 * gq + e]);
+}
 
 // NWV = waves per workgroup: 8, or 4 for C = 96 (two windows, one head at a time: half the LDS, so that TWO workgroups share a CU --
 // a stage-0 workgroup has 1.5 us of matrix work and ~22 us of dependent latencies: gather, 7 barriers, bias loads, epilogue)
@@ -51,19 +106,9 @@ __global__ __launch_bounds__(NWV * 64) void swin_block_attn_kernel(const SwinBAP
     constexpr int NTB = 2 * NWIN, TR = 64 * NWIN, GT = 3 * HG, NCT = C / 32;      // token blocks / rows per workgroup; tiles per group
     static_assert(NWIN * HG == NSLOT && NH % HG == 0 && C % 48 == 0 && KS % U == 0 && U % D == 0 && U % PB == 0 && GT * NTB == 3 * NWV &&
                   NCT * NTB == 3 * NWV, "layout");
-    // token rows of the normalised input / the attention output: 2 C bytes + 16 of padding (conflict-free 16-byte fragment reads);
-    // C = 96: the padding would not fit -- 16 bytes after every FOURTH row do the same job (192-byte rows start 48 dwords apart)
-    constexpr int XBYTES = C == 96 ? TR * 192 + (TR / 4) * 16 : TR * (C * 2 + 16);
-    auto xoff = [](int r) -> int { return C == 96 ? r * 192 + (r >> 2) * 16 : r * (C * 2 + 16); };
-    constexpr int QROW = 80, VROW = 144;                 // q, k rows: 32 dh (+ pad); v^T rows: 64 keys (+ pad)
-    constexpr int LDS_NX = 0;
-    constexpr int LDS_Q = XBYTES;                        // [NSLOT (head of group, window)][64 tokens][QROW]
-    constexpr int LDS_K = LDS_Q + NSLOT * 64 * QROW;
-    constexpr int LDS_V = LDS_K + NSLOT * 64 * QROW;     // [NSLOT][32 dh][VROW]
-    constexpr int LDS_O = LDS_V + NSLOT * 32 * VROW;
-    constexpr int LDS_REG = LDS_O + XBYTES;              // int[NWIN][64]: shift-mask region per token
-    constexpr int YROW = C * 4 + 16;
-    static_assert(TR * YROW <= LDS_O && LDS_REG + NWIN * 256 <= 160 * 1024, "result tile must fit below the attention output");
+    using L = SbaLayout<C, NWIN, NWV>;
+    constexpr int LDS_NX = L::NX, LDS_Q = L::Q, LDS_K = L::K, LDS_V = L::V, LDS_O = L::O, LDS_REG = L::REG, YROW = L::YROW;
+    auto xoff = [](int r) -> int { return L::xoff(r); };
     extern __shared__ __attribute__((aligned(16))) char smem[];
 
     const int tid = threadIdx.x, lane = tid & 63;
@@ -71,19 +116,19 @@ __global__ __launch_bounds__(NWV * 64) void swin_block_attn_kernel(const SwinBAP
     const int fr = lane & 31, fh = lane >> 5;
     const int wgs = p.nW / NWIN;                          // workgroups per image
     const int b = blockIdx.x / wgs, wloc0 = (blockIdx.x - b * wgs) * NWIN;
+#ifdef MV_I8_PROF              // per-wave phase stamps (tools/time_swin_block_attn.py, SBA_PROF): st_w is indexed dynamically = 80 bytes of scratch
     long long st_w[8];
     int nst = 0;
 #define MV_SBA_STAMP() do { if (p.prof && nst < 8) st_w[nst++] = wall_clock64(); } while (0)
+#else
+#define MV_SBA_STAMP() do { } while (0)
+#endif
     MV_SBA_STAMP();                                       // 0: start
+    const WindowGeom geo = {p.Hf, p.Wf, WS, WS, p.shh, p.shw};
     const bool shifted = (p.shh + p.shw) > 0;
     auto tok_row = [&](int r) -> long long {            // row r = 64 * window + token -> its row in x / y (un-rolled position)
-        const int wloc = wloc0 + (r >> 6), t = r & 63;
-        const int wy = wloc / p.nWw, wx = wloc - wy * p.nWw;
-        const int ty = t / WS, tx = t - ty * WS;
-        int oy = wy * WS + ty + p.shh, ox = wx * WS + tx + p.shw;
-        if (oy >= p.Hf) oy -= p.Hf;
-        if (ox >= p.Wf) ox -= p.Wf;
-        return ((long long)b * p.Hf + oy) * p.Wf + ox;
+        const int wloc = wloc0 + (r >> 6), wy = wloc / p.nWw;
+        return swin_tok_row(geo, b, wy, wloc - wy * p.nWw, r & 63);
     };
 
     // ---------------- weight-fragment streams: units 3w .. 3w+2 of (tiles x NTB token blocks) touch at most two channel tiles ------
@@ -139,15 +184,9 @@ __global__ __launch_bounds__(NWV * 64) void swin_block_attn_kernel(const SwinBAP
                 *(uint2*)(smem + LDS_NX + xoff(r) + (lq + LPR * i) * 8) = u;
             }
         }
-        if (tid < TR) {                                  // shift-mask region of every token (rolled coordinates, swin.py:190-209)
-            const int wloc = wloc0 + (tid >> 6);
-            const int wy = wloc / p.nWw, wx = wloc - wy * p.nWw;
-            const int t = (tid & 63) < NTOK ? (tid & 63) : NTOK - 1;
-            const int ty = t / WS, tx = t - ty * WS;
-            const int yy = wy * WS + ty, xx = wx * WS + tx;
-            const int rh = (yy < p.Hf - WS) ? 0 : (yy < p.Hf - p.shh ? 1 : 2);
-            const int rw = (xx < p.Wf - WS) ? 0 : (xx < p.Wf - p.shw ? 1 : 2);
-            ((int*)(smem + LDS_REG))[tid] = shifted ? rh * 3 + rw : 0;
+        if (tid < TR) {                                  // shift-mask region of every token (padded ones: the last real token's)
+            const int wloc = wloc0 + (tid >> 6), wy = wloc / p.nWw, t = (tid & 63) < NTOK ? (tid & 63) : NTOK - 1;
+            ((int*)(smem + LDS_REG))[tid] = shifted ? swin_tok_region(geo, wy, wloc - wy * p.nWw, t) : 0;
         }
     }
     __syncthreads();
@@ -217,33 +256,9 @@ __global__ __launch_bounds__(NWV * 64) void swin_block_attn_kernel(const SwinBAP
             const int tile = u_tile[i], tb = u_tb[i];
             const int kind = tile / HG, hl = tile - kind * HG;          // 0 q, 1 k, 2 v; head of the group
             const int win = tb >> 1, slotq = hl * NWIN + win;           // (head of group, window) slot of the q / k / v buffers
-            const float* bb = p.bqkv + ((size_t)g * GT + tile) * 32 + 4 * fh;
-            const int tok = 32 * (tb & 1) + fr;
-            if (kind < 2) {
-                char* dst = smem + (kind == 0 ? LDS_Q : LDS_K) + (slotq * 64 + tok) * QROW + 8 * fh;
-#pragma unroll
-                for (int gq = 0; gq < 4; ++gq) {
-                    const float4 bv = *(const float4*)(bb + 8 * gq);
-                    uint2 u;
-                    u.x = pack_bf2(acc[i][4 * gq + 0] + bv.x, acc[i][4 * gq + 1] + bv.y);
-                    u.y = pack_bf2(acc[i][4 * gq + 2] + bv.z, acc[i][4 * gq + 3] + bv.w);
-                    *(uint2*)(dst + 16 * gq) = u;
-                }
-            } else {
-                // v^T[dh][slot(key)]: the 8 keys a lane feeds to one P.V step sit next to each other (slot order (token block, pair
-                // of groups, lane half, group parity, r)) -- the lane's own position decides the slot of its token
-                const int kg = fr >> 3, khh = (fr >> 2) & 1, kr = fr & 3;
-                const int slot = (((tb & 1) * 2 + (kg >> 1)) * 2 + khh) * 8 + (kg & 1) * 4 + kr;
-                char* dst = smem + LDS_V + slotq * 32 * VROW + slot * 2;
-#pragma unroll
-                for (int gq = 0; gq < 4; ++gq) {
-                    const float4 bv = *(const float4*)(bb + 8 * gq);
-                    const float vv[4] = {acc[i][4 * gq + 0] + bv.x, acc[i][4 * gq + 1] + bv.y, acc[i][4 * gq + 2] + bv.z,
-                                         acc[i][4 * gq + 3] + bv.w};
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) *(bf16_t*)(dst + (8 * gq + 4 * fh + e) * VROW) = f2bf(vv[e]);
-                }
-            }
+            const f32x16 v = add_bias(acc[i], p.bqkv + ((size_t)g * GT + tile) * 32 + 4 * fh);
+            if (kind < 2) store_quads_bf16(smem + (kind == 0 ? LDS_Q : LDS_K) + (slotq * 64 + 32 * (tb & 1) + fr) * QROW + 8 * fh, v);
+            else store_vt(smem + LDS_V + slotq * 32 * VROW + vt_slot(tb & 1, fr) * 2, v, fh);
         }
         __syncthreads();
         if (g == 0) MV_SBA_STAMP();                       // 3: q / k / v stores + barrier
@@ -269,63 +284,11 @@ __global__ __launch_bounds__(NWV * 64) void swin_block_attn_kernel(const SwinBAP
 #pragma unroll
                 for (int j = 0; j < 2; ++j) s[kt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kf[kt][j], qf[j], s[kt], 0, 0, 0);
             }
-            const float* brow = p.bias + ((size_t)h * 64 + qtok) * 64;
             const int* rl = regl + 64 * win;
-            const int qreg = rl[qtok];
-            float mx = -INFINITY;
-#pragma unroll
-            for (int kt = 0; kt < 2; ++kt)
-#pragma unroll
-                for (int gq = 0; gq < 4; ++gq) {
-                    const int key0 = 32 * kt + 8 * gq + 4 * fh;
-                    const float4 bv = *(const float4*)(brow + key0);
-                    const int4 kr = *(const int4*)(rl + key0);
-                    const float bb[4] = {bv.x, bv.y, bv.z, bv.w};
-                    const int rr[4] = {kr.x, kr.y, kr.z, kr.w};
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) {
-                        float v = fmaf(s[kt][4 * gq + e], scale, bb[e]);
-                        if (rr[e] != qreg) v += -100.0f;
-                        s[kt][4 * gq + e] = v;
-                        mx = fmaxf(mx, v);
-                    }
-                }
-            mx = fmaxf(mx, __shfl_xor(mx, 32));
-            float sum = 0.f;
-#pragma unroll
-            for (int kt = 0; kt < 2; ++kt)
-#pragma unroll
-                for (int e = 0; e < 16; ++e) {
-                    const float pe = __expf(s[kt][e] - mx);
-                    s[kt][e] = pe;
-                    sum += pe;
-                }
-            sum += __shfl_xor(sum, 32);
-            const float inv = 1.f / sum;
-            f32x16 o;
-#pragma unroll
-            for (int e = 0; e < 16; ++e) o[e] = 0.f;
+            const float inv = win_softmax<false>(s, scale, p.bias + ((size_t)h * 64 + qtok) * 64, rl, rl[qtok], fh);
             const char* vp = smem + LDS_V + (slotq * 32 + fr) * VROW + fh * 16;
-#pragma unroll
-            for (int kt = 0; kt < 2; ++kt)
-#pragma unroll
-                for (int gp = 0; gp < 2; ++gp) {
-                    uint4 pf;
-                    pf.x = pack_bf2(s[kt][8 * gp + 0], s[kt][8 * gp + 1]);
-                    pf.y = pack_bf2(s[kt][8 * gp + 2], s[kt][8 * gp + 3]);
-                    pf.z = pack_bf2(s[kt][8 * gp + 4], s[kt][8 * gp + 5]);
-                    pf.w = pack_bf2(s[kt][8 * gp + 6], s[kt][8 * gp + 7]);
-                    const bf16x8 vf = *(const bf16x8*)(vp + (kt * 2 + gp) * 32);
-                    o = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vf, __builtin_bit_cast(bf16x8, pf), o, 0, 0, 0);
-                }
-            char* od = smem + LDS_O + xoff(64 * win + qtok) + (32 * h + 4 * fh) * 2;
-#pragma unroll
-            for (int gq = 0; gq < 4; ++gq) {
-                uint2 u;
-                u.x = pack_bf2(o[4 * gq + 0] * inv, o[4 * gq + 1] * inv);
-                u.y = pack_bf2(o[4 * gq + 2] * inv, o[4 * gq + 3] * inv);
-                *(uint2*)(od + 16 * gq) = u;
-            }
+            const f32x16 o = win_pv(s, [&](int st) { return *(const bf16x8*)(vp + st * 32); });
+            store_quads_bf16(smem + LDS_O + xoff(64 * win + qtok) + (32 * h + 4 * fh) * 2, o * inv);
         }
         if (g == 0) MV_SBA_STAMP();                       // 4: attention of group 0
         __syncthreads();
@@ -375,6 +338,7 @@ __global__ __launch_bounds__(NWV * 64) void swin_block_attn_kernel(const SwinBAP
             }
         }
     }
+#ifdef MV_I8_PROF
     if (p.prof) {
         const long long tend = wall_clock64();
         if (lane == 0) {
@@ -383,6 +347,7 @@ __global__ __launch_bounds__(NWV * 64) void swin_block_attn_kernel(const SwinBAP
             o[8] = tend;
         }
     }
+#endif
 #undef MV_SBA_STAMP
 }
 
@@ -402,10 +367,9 @@ __global__ __launch_bounds__(NWV * 64) void swin_block_attn_kernel(const SwinBAP
 //     (y^T += Wp[:, head] . o^T; the proj fragments arrive in the standard order and are re-ordered to the accumulator's channel
 //     order by two half-wave swaps each) -- the attention output never exists in memory;
 //   * the wave's 32 x 96 result leaves through LDS (K / V are dead by then) as whole 384-byte rows.
-template <int UNUSED>
 __global__ __launch_bounds__(128, 3) void swin_win96_kernel(const SwinBAP p) {
-    constexpr int C = 96, KS = 6, NH = 3, NTOK = 49, WS = 7, QROW = 80, VROW = 144;
-    constexpr int LDS_K = 0, LDS_V = NH * 64 * QROW, LDS_REG = LDS_V + NH * 32 * VROW;
+    constexpr int C = 96, KS = 6, NH = 3, NTOK = 49, WS = 7;
+    constexpr int LDS_K = Win96Layout::K, LDS_V = Win96Layout::V, LDS_REG = Win96Layout::REG;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);              // = token block of the window
@@ -423,15 +387,8 @@ __global__ __launch_bounds__(128, 3) void swin_win96_kernel(const SwinBAP p) {
     const bool shifted = (p.shh + p.shw) > 0;
     const int tok = 32 * wave + fr;
     const bool real = tok < NTOK;
-    long long row;
-    {
-        const int t = real ? tok : 0;
-        const int ty = t / WS, tx = t - ty * WS;
-        int oy = wy * WS + ty + p.shh, ox = wx * WS + tx + p.shw;
-        if (oy >= p.Hf) oy -= p.Hf;
-        if (ox >= p.Wf) ox -= p.Wf;
-        row = (((long long)b * p.Hf + oy) * p.Wf + ox) * C;
-    }
+    const WindowGeom geo = {p.Hf, p.Wf, WS, WS, p.shh, p.shw};
+    const long long row = swin_tok_row(geo, b, wy, wx, real ? tok : 0) * C;       // padded tokens read token 0, and store nothing
     // ---- the first weight tile is on its way before anything else
     const uint4* wq = (const uint4*)p.wqkv + lane;                       // [head][q | k | v][k-step][lane]
     constexpr int NF = 3 * NH * KS, RING = 8, LOOK = 7;                 // 54 fragments of 1 KB, 7 in flight
@@ -442,11 +399,7 @@ __global__ __launch_bounds__(128, 3) void swin_win96_kernel(const SwinBAP p) {
     // ---- gather + LayerNorm: B fragments of the qkv GEMM, and the residual in accumulator layout
     float raw[KS][8];
     {
-#ifdef MV_I8_PROF
-        const float* src = p.x + ((p.ablate & 8) ? (long long)(lane * 96) : row) + 8 * fh;
-#else
-        const float* src = p.x + row + 8 * fh;
-#endif
+        const float* src = p.x + (ablated(p, 8) ? (long long)(lane * 96) : row) + 8 * fh;
 #pragma unroll
         for (int j = 0; j < KS; ++j) {
             const float4 a = *(const float4*)(src + 16 * j), c = *(const float4*)(src + 16 * j + 4);
@@ -454,14 +407,8 @@ __global__ __launch_bounds__(128, 3) void swin_win96_kernel(const SwinBAP p) {
             raw[j][4] = c.x; raw[j][5] = c.y; raw[j][6] = c.z; raw[j][7] = c.w;
         }
     }
-    if (tid < 64) {                                      // shift-mask region of every token (rolled coordinates, swin.py:190-209)
-        const int t = tid < NTOK ? tid : NTOK - 1;
-        const int ty = t / WS, tx = t - ty * WS;
-        const int yy = wy * WS + ty, xx = wx * WS + tx;
-        const int rh = (yy < p.Hf - WS) ? 0 : (yy < p.Hf - p.shh ? 1 : 2);
-        const int rw = (xx < p.Wf - WS) ? 0 : (xx < p.Wf - p.shw ? 1 : 2);
-        ((int*)(smem + LDS_REG))[tid] = shifted ? rh * 3 + rw : 0;
-    }
+    if (tid < 64)                                        // shift-mask region of every token (padded ones: the last real token's)
+        ((int*)(smem + LDS_REG))[tid] = shifted ? swin_tok_region(geo, wy, wx, tid < NTOK ? tid : NTOK - 1) : 0;
     uint4 xf[KS];
     {
         float s = 0.f;
@@ -504,7 +451,7 @@ __global__ __launch_bounds__(128, 3) void swin_win96_kernel(const SwinBAP p) {
 
     MV_W96_STAMP();                                       // 1: gather + LayerNorm + residual seed
     // ---- q | k | v of the three heads: tile u = 3 head + kind; a ring of 8 weight fragments, 7 loads in flight
-    uint4 qf[NH][2];
+    bf16x8 qf[NH][2];
 #pragma unroll
     for (int u = 0; u < 3 * NH; ++u) {
         const int h = u / 3, kind = u - 3 * h;
@@ -515,46 +462,20 @@ __global__ __launch_bounds__(128, 3) void swin_win96_kernel(const SwinBAP p) {
         for (int j = 0; j < KS; ++j) {
             const int i = u * KS + j;
             const uint4 a = wb[i % RING];
-#ifdef MV_I8_PROF
-            if (i + LOOK < NF) wb[(i + LOOK) % RING] = wq[((p.ablate & 1) ? 0 : (i + LOOK)) * 64];
-#else
-            if (i + LOOK < NF) wb[(i + LOOK) % RING] = wq[(i + LOOK) * 64];
-#endif
+            if (i + LOOK < NF) wb[(i + LOOK) % RING] = wq[(ablated(p, 1) ? 0 : (i + LOOK)) * 64];
             acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, xf[j]), acc, 0, 0, 0);
         }
-        const float* bb = p.bqkv + u * 32 + 4 * fh;
-        float v[16];
-#pragma unroll
-        for (int gq = 0; gq < 4; ++gq) {
-            const float4 bv = *(const float4*)(bb + 8 * gq);
-            v[4 * gq + 0] = acc[4 * gq + 0] + bv.x; v[4 * gq + 1] = acc[4 * gq + 1] + bv.y;
-            v[4 * gq + 2] = acc[4 * gq + 2] + bv.z; v[4 * gq + 3] = acc[4 * gq + 3] + bv.w;
-        }
-        if (kind < 2) {
+        const f32x16 v = add_bias(acc, p.bqkv + u * 32 + 4 * fh);
+        if (kind == 0) {
             // head channels in accumulator order: k-step j of a lane = channels 8 (2 j + (e >> 2)) + 4 fh + (e & 3) -- the same on the
             // q side (registers) and the k side (LDS row of the token, 16 bytes at (2 fh + j) * 16), so S^T = K . Q^T is exact
-            uint4 pk[2];
-#pragma unroll
-            for (int j = 0; j < 2; ++j) {
-                pk[j].x = pack_bf2(v[8 * j + 0], v[8 * j + 1]); pk[j].y = pack_bf2(v[8 * j + 2], v[8 * j + 3]);
-                pk[j].z = pack_bf2(v[8 * j + 4], v[8 * j + 5]); pk[j].w = pack_bf2(v[8 * j + 6], v[8 * j + 7]);
-            }
-            if (kind == 0) { qf[h][0] = pk[0]; qf[h][1] = pk[1]; }
-            else {
-                char* dst = smem + LDS_K + (h * 64 + tok) * QROW + fh * 32;
-                *(uint4*)dst = pk[0];
-                *(uint4*)(dst + 16) = pk[1];
-            }
-        } else {
-            // v^T[dh][slot(key)]: the 8 keys a lane feeds to one P.V step sit next to each other (same order as the 8-wave kernel)
-            const int kg = fr >> 3, khh = (fr >> 2) & 1, kr = fr & 3;
-            const int slot = ((wave * 2 + (kg >> 1)) * 2 + khh) * 8 + (kg & 1) * 4 + kr;
-            char* dst = smem + LDS_V + h * 32 * VROW + slot * 2;
-#pragma unroll
-            for (int gq = 0; gq < 4; ++gq)
-#pragma unroll
-                for (int e = 0; e < 4; ++e) *(bf16_t*)(dst + (8 * gq + 4 * fh + e) * VROW) = f2bf(v[4 * gq + e]);
-        }
+            qf[h][0] = p_frag(v, 0);
+            qf[h][1] = p_frag(v, 1);
+        } else if (kind == 1) {
+            char* dst = smem + LDS_K + (h * 64 + tok) * QROW + fh * 32;
+            *(bf16x8*)dst = p_frag(v, 0);
+            *(bf16x8*)(dst + 16) = p_frag(v, 1);
+        } else store_vt(smem + LDS_V + h * 32 * VROW + vt_slot(wave, fr) * 2, v, fh);       // same slot order as the 8-wave kernel
     }
     MV_W96_STAMP();                                       // 2: qkv of three heads + k / v stores
     __syncthreads();
@@ -571,11 +492,7 @@ __global__ __launch_bounds__(128, 3) void swin_win96_kernel(const SwinBAP p) {
 #pragma unroll
         for (int ct = 0; ct < 3; ++ct)
 #pragma unroll
-#ifdef MV_I8_PROF
-            for (int j = 0; j < 2; ++j) wpf[ct][j] = wpq[((p.ablate & 1) ? 0 : (ct * KS + 2 * h + j)) * 64];
-#else
-            for (int j = 0; j < 2; ++j) wpf[ct][j] = wpq[(ct * KS + 2 * h + j) * 64];
-#endif
+            for (int j = 0; j < 2; ++j) wpf[ct][j] = wpq[(ablated(p, 1) ? 0 : (ct * KS + 2 * h + j)) * 64];
         const char* kp = smem + LDS_K + (h * 64 + fr) * QROW + fh * 32;
         f32x16 s[2];
 #pragma unroll
@@ -585,68 +502,15 @@ __global__ __launch_bounds__(128, 3) void swin_win96_kernel(const SwinBAP p) {
 #pragma unroll
             for (int j = 0; j < 2; ++j) {
                 const bf16x8 kf = *(const bf16x8*)(kp + kt * 32 * QROW + j * 16);
-                s[kt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kf, __builtin_bit_cast(bf16x8, qf[h][j]), s[kt], 0, 0, 0);
+                s[kt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kf, qf[h][j], s[kt], 0, 0, 0);
             }
         }
-        const float* brow = p.bias + ((size_t)h * 64 + tok) * 64;
-        float mx = -INFINITY;
-#pragma unroll
-        for (int kt = 0; kt < 2; ++kt)
-#pragma unroll
-            for (int gq = 0; gq < 4; ++gq) {
-                const int key0 = 32 * kt + 8 * gq + 4 * fh;
-#ifdef MV_I8_PROF
-                const float4 bv = *(const float4*)(brow + ((p.ablate & 2) ? 4 * fh : key0));
-#else
-                const float4 bv = *(const float4*)(brow + key0);
-#endif
-                const int4 kr = *(const int4*)(rl + key0);
-                const float bb[4] = {bv.x, bv.y, bv.z, bv.w};
-                const int rr[4] = {kr.x, kr.y, kr.z, kr.w};
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    float v = fmaf(s[kt][4 * gq + e], scale, bb[e]);
-                    if (rr[e] != qreg) v += -100.0f;
-                    s[kt][4 * gq + e] = v;
-                    mx = fmaxf(mx, v);
-                }
-            }
-        mx = fmaxf(mx, __shfl_xor(mx, 32));
-        float sum = 0.f;
-#pragma unroll
-        for (int kt = 0; kt < 2; ++kt)
-#pragma unroll
-            for (int e = 0; e < 16; ++e) {
-                const float pe = __expf(s[kt][e] - mx);
-                s[kt][e] = pe;
-                sum += pe;
-            }
-        sum += __shfl_xor(sum, 32);
-        const float inv = 1.f / sum;
-        f32x16 o;
-#pragma unroll
-        for (int e = 0; e < 16; ++e) o[e] = 0.f;
+        const float inv = win_softmax<false>(s, scale, p.bias + ((size_t)h * 64 + tok) * 64, rl, qreg, fh, true, 64, ablated(p, 2));
         const char* vp = smem + LDS_V + (h * 32 + fr) * VROW + fh * 16;
-#pragma unroll
-        for (int kt = 0; kt < 2; ++kt)
-#pragma unroll
-            for (int gp = 0; gp < 2; ++gp) {
-                uint4 pf;
-                pf.x = pack_bf2(s[kt][8 * gp + 0], s[kt][8 * gp + 1]);
-                pf.y = pack_bf2(s[kt][8 * gp + 2], s[kt][8 * gp + 3]);
-                pf.z = pack_bf2(s[kt][8 * gp + 4], s[kt][8 * gp + 5]);
-                pf.w = pack_bf2(s[kt][8 * gp + 6], s[kt][8 * gp + 7]);
-                const bf16x8 vf = *(const bf16x8*)(vp + (kt * 2 + gp) * 32);
-                o = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vf, __builtin_bit_cast(bf16x8, pf), o, 0, 0, 0);
-            }
+        const f32x16 o = win_pv(s, [&](int st) { return *(const bf16x8*)(vp + st * 32); }) * inv;
         // o[4 gq + i] = out[my token][32 h + 8 gq + 4 fh + i]: k-step j of proj = registers 8 j .. 8 j + 7.  The standard proj fragment
         // of a lane holds input channels 16 jj + 8 fh + 0..7; the accumulator order wants {0..3, 8..11} below and {4..7, 12..15} above
-        uint4 of[2];
-#pragma unroll
-        for (int j = 0; j < 2; ++j) {
-            of[j].x = pack_bf2(o[8 * j + 0] * inv, o[8 * j + 1] * inv); of[j].y = pack_bf2(o[8 * j + 2] * inv, o[8 * j + 3] * inv);
-            of[j].z = pack_bf2(o[8 * j + 4] * inv, o[8 * j + 5] * inv); of[j].w = pack_bf2(o[8 * j + 6] * inv, o[8 * j + 7] * inv);
-        }
+        const bf16x8 of[2] = {p_frag(o, 0), p_frag(o, 1)};
 #pragma unroll
         for (int ct = 0; ct < 3; ++ct)
 #pragma unroll
@@ -655,7 +519,7 @@ __global__ __launch_bounds__(128, 3) void swin_win96_kernel(const SwinBAP p) {
                 const auto s0 = __builtin_amdgcn_permlane32_swap(a.x, a.z, false, false);
                 const auto s1 = __builtin_amdgcn_permlane32_swap(a.y, a.w, false, false);
                 a.x = s0[0]; a.z = s0[1]; a.y = s1[0]; a.w = s1[1];
-                yacc[ct] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, of[j]), yacc[ct], 0, 0, 0);
+                yacc[ct] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a), of[j], yacc[ct], 0, 0, 0);
             }
         MV_W96_STAMP();                                   // 4, 5, 6: head h (attention + proj slice)
     }
@@ -665,7 +529,7 @@ __global__ __launch_bounds__(128, 3) void swin_win96_kernel(const SwinBAP p) {
     // now -- and leaves as whole 384-byte rows, 16 bytes per lane.
     __syncthreads();                                     // both waves are done with K / V
     {
-        constexpr int YP = 100;                          // floats per staged row (96 + 4: conflict-free 16-byte pieces)
+        constexpr int YP = Win96Layout::YP;
         float* yt = (float*)smem + wave * (32 * YP + 64);
         long long* ro = (long long*)(yt + 32 * YP);      // row offset of each of the wave's 32 tokens, -1 = padding token
         const float* bp = p.bp + 4 * fh;
@@ -679,9 +543,7 @@ __global__ __launch_bounds__(128, 3) void swin_win96_kernel(const SwinBAP p) {
             }
         if (fh == 0) ro[fr] = real ? row : -1;
         wave_lds_fence();
-#ifdef MV_I8_PROF
-        if ((p.ablate & 4) && yacc[0][0] != 12345.678f) return;
-#endif
+        if (ablated(p, 4) && yacc[0][0] != 12345.678f) return;
 #pragma unroll
         for (int i = 0; i < 12; ++i) {
             const int idx = lane + 64 * i, r = idx / 24, q = idx - r * 24;
@@ -744,15 +606,12 @@ int mv_swin_block_attn_fwd(const void* x, const void* wqkv_f, const float* bqkv,
         p.prof = (long long*)(((unsigned long long)(unsigned)get_flag("prof_hi") << 32) | (unsigned)get_flag("prof_lo"));
 #endif
     const int nwin = swin_block_attn_nwin(C);
-    const int nwv = C == 96 ? 4 : 8;
-    const int tr = 64 * nwin, nslot = nwv / 2;
-    const int xbytes = C == 96 ? tr * 192 + (tr / 4) * 16 : tr * (C * 2 + 16);
-    const int smem = 2 * xbytes + 2 * nslot * 64 * 80 + nslot * 32 * 144 + nwin * 256;
     const dim3 grid((unsigned)(B * (p.nW / nwin)));
 #define MV_SBA_GO(CC, NW, WV)                                                                                        \
     do {                                                                                                             \
         auto kern = swin_block_attn_kernel<CC, NW, WV>;                                                              \
         static LdsAttrSite attr;                                                                                     \
+        constexpr int smem = SbaLayout<CC, NW, WV>::BYTES;                                                           \
         MV_HIP(attr.ensure((const void*)kern, smem));                                                                \
         hipLaunchKernelGGL(kern, grid, dim3(WV * 64), smem, stream, p);                                              \
     } while (0)
@@ -761,8 +620,7 @@ int mv_swin_block_attn_fwd(const void* x, const void* wqkv_f, const float* bqkv,
     else if (get_flag("swin_c96_shared")) { set_kernel_name("swin_block_attn_c96"); MV_SBA_GO(96, 2, 4); }
     else {
         set_kernel_name("swin_win96");
-        constexpr int LDS96 = 3 * 64 * 80 + 3 * 32 * 144 + 256;
-        hipLaunchKernelGGL(swin_win96_kernel<0>, dim3((unsigned)(B * p.nW)), dim3(128), LDS96, stream, p);
+        hipLaunchKernelGGL(swin_win96_kernel, dim3((unsigned)(B * p.nW)), dim3(128), Win96Layout::BYTES, stream, p);
     }
 #undef MV_SBA_GO
     MV_LAUNCH_CHECK();

@@ -17,8 +17,12 @@ __device__ __forceinline__ void swin_rolled(const WindowGeom& g, int wy, int wx,
     x = wx * g.wsw + t % g.wsw;
 }
 // rolled (y, x) of image b -> the row of the [B, Hf, Wf] map it was rolled from: np.roll(x, -s)[i] = x[(i + s) % n]
+// One conditional subtract IS the modulo: y < Hf, and a checked geometry (swin_check_geom) has shh < wsh <= Hf, so y + shh < 2 Hf.
 __device__ __forceinline__ long long swin_src_row(const WindowGeom& g, int b, int y, int x) {
-    return ((long long)b * g.Hf + (y + g.shh) % g.Hf) * g.Wf + (x + g.shw) % g.Wf;
+    int oy = y + g.shh, ox = x + g.shw;
+    if (oy >= g.Hf) oy -= g.Hf;
+    if (ox >= g.Wf) ox -= g.Wf;
+    return ((long long)b * g.Hf + oy) * g.Wf + ox;
 }
 // shift-mask region id of rolled (y, x): 3 x 3 bands (swin.py:190-209); tokens of different regions do not attend to each other
 __device__ __forceinline__ int swin_region(const WindowGeom& g, int y, int x) {

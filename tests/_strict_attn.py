@@ -190,28 +190,38 @@ def eff_shift(Hf, ws, shift):
     return 0 if ws >= Hf else shift
 
 
+def hw(Hf):
+    """A shape's map entry: Hf (square map) or (Hf, Wf)."""
+    return (Hf, Hf) if np.isscalar(Hf) else tuple(Hf)
+
+
 def region_map(Hf, ws, shift, off_by_one=False):
     """(nW, n) region ids of the rolled map: the mask construction of tests/_cases.py::_swin_core_ref.  off_by_one: the defect."""
-    nW, n = (Hf // ws) ** 2, ws * ws
-    s = eff_shift(Hf, ws, shift)
-    if s == 0:
+    H, W = hw(Hf)
+    nW, n = (H // ws) * (W // ws), ws * ws
+    sh, sw = eff_shift(H, ws, shift), eff_shift(W, ws, shift)
+    if sh == 0 and sw == 0:
         return np.zeros((nW, n), np.int64)
-    m = np.zeros((Hf, Hf), np.int64)
-    e = Hf - s + (1 if off_by_one else 0)
-    sl = ((0, Hf - ws), (Hf - ws, e), (e, Hf))
+    m = np.zeros((H, W), np.int64)
+
+    def bands(L, s):
+        e = L - s + (1 if off_by_one else 0)
+        return (0, L - ws), (L - ws, e), (e, L)
+
     c = 0
-    for a in sl:
-        for b in sl:
+    for a in bands(H, sh):
+        for b in bands(W, sw):
             m[a[0]:a[1], b[0]:b[1]] = c
             c += 1
-    return m.reshape(Hf // ws, ws, Hf // ws, ws).transpose(0, 2, 1, 3).reshape(nW, n)
+    return m.reshape(H // ws, ws, W // ws, ws).transpose(0, 2, 1, 3).reshape(nW, n)
 
 
 def mask_classes(Hf, ws, shift):
     """(n,) class of a window token: which side of the shift boundary in each axis (tokens of one class share a region in every window)."""
-    s = eff_shift(Hf, ws, shift)
+    H, W = hw(Hf)
+    sh, sw = eff_shift(H, ws, shift), eff_shift(W, ws, shift)
     t = np.arange(ws * ws)
-    return ((t // ws) >= ws - s) * 2 + ((t % ws) >= ws - s) if s else np.zeros(ws * ws, np.int64)
+    return ((t // ws) >= ws - sh) * 2 + ((t % ws) >= ws - sw) if sh or sw else np.zeros(ws * ws, np.int64)
 
 
 def swin_extra(bias, regions, heads, B):
@@ -225,20 +235,18 @@ def swin_extra(bias, regions, heads, B):
 def swin_pack(q, k, v, B, Hf, heads, ws, shift):
     """Groups (B nW heads, n, dh) -> qkv NHWC (B, Hf, Hf, 3 C), channel order [q | k | v][head][dh], the cyclic shift undone."""
     n, dh = q.shape[1:]
-    nw = Hf // ws
-    t = np.stack([q, k, v]).reshape(3, B, nw, nw, heads, ws, ws, dh)
-    x = t.transpose(1, 2, 5, 3, 6, 0, 4, 7).reshape(B, Hf, Hf, 3 * heads * dh)
-    s = eff_shift(Hf, ws, shift)
-    return np.ascontiguousarray(np.roll(x, (s, s), axis=(1, 2)))
+    H, W = hw(Hf)
+    t = np.stack([q, k, v]).reshape(3, B, H // ws, W // ws, heads, ws, ws, dh)
+    x = t.transpose(1, 2, 5, 3, 6, 0, 4, 7).reshape(B, H, W, 3 * heads * dh)
+    return np.ascontiguousarray(np.roll(x, (eff_shift(H, ws, shift), eff_shift(W, ws, shift)), axis=(1, 2)))
 
 
 def swin_groups(y, heads, ws, shift):
     """out NHWC (B, Hf, Hf, C) -> (B nW heads, n, dh)."""
-    B, Hf, _, C = y.shape
-    s = eff_shift(Hf, ws, shift)
-    nw, dh = Hf // ws, C // heads
-    x = np.roll(y, (-s, -s), axis=(1, 2)).reshape(B, nw, ws, nw, ws, heads, dh)
-    return x.transpose(0, 1, 3, 5, 2, 4, 6).reshape(B * nw * nw * heads, ws * ws, dh)
+    B, H, W, C = y.shape
+    nh, nw, dh = H // ws, W // ws, C // heads
+    x = np.roll(y, (-eff_shift(H, ws, shift), -eff_shift(W, ws, shift)), axis=(1, 2)).reshape(B, nh, ws, nw, ws, heads, dh)
+    return x.transpose(0, 1, 3, 5, 2, 4, 6).reshape(B * nh * nw * heads, ws * ws, dh)
 
 
 def mha_pack(q, k, v, B, H, head_major=False):
@@ -427,13 +435,15 @@ MHA_OTHER = ((1, 197, 2, 64, "bf16", True, "mha_generic"), (1, 8, 4, 8, "bf16", 
 SWIN_SHAPES = ((2, 14, 96, 3, 7, 3), (2, 14, 96, 3, 7, 0), (1, 7, 192, 6, 7, 3), (2, 16, 64, 2, 8, 4), (2, 12, 64, 2, 4, 2))   # (B, Hf, C, heads, ws, shift)
 SWIN_OTHER = ((2, 14, 96, 3, 7, 3, "bf16", True, "swin_attn_generic"), (1, 14, 32, 2, 7, 3, "fp32", False, "swin_attn_f32_lds"))
 COS_SHAPES = ((1, 14, 64, 2, 7, 3), (1, 16, 64, 2, 8, 4))
+# Hf = (Hf, Wf): the window covers the map in one axis (its shift is dropped), the other wraps at the largest legal shift, ws - 1
+SWIN_WRAP_SHAPES = ((1, (8, 4), 32, 1, 4, 3), (1, (4, 8), 32, 1, 4, 3))
 
 
 def swin_problem(kind, shape, seed, by_bias=True, off_by_one=False, dtype="bf16"):
     """(problem, extra, regions) of a Swin shape; `extra` = bias + mask from region_map (off_by_one: the defective mask)."""
     B, Hf, C, heads, ws, shift = shape
     n, dh = ws * ws, C // heads
-    nW = (Hf // ws) ** 2
+    nW = (hw(Hf)[0] // ws) * (hw(Hf)[1] // ws)
     reg = region_map(Hf, ws, shift)
     G = B * nW * heads
     greg = np.broadcast_to(reg[None, :, None], (B, nW, heads, n)).reshape(G, n)

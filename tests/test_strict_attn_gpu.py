@@ -92,26 +92,27 @@ def _run_swin(p, shape, dtype="bf16", generic=False, keys=None, keep=1.0, cos=Fa
     from eqxvision_amd import _lib
     B, Hf, C, heads, ws, shift = shape
     qd = _dev(A.swin_pack(p["q"], p["k"], p["v"], B, Hf, heads, ws, shift), dtype)
+    Hf, Wf = A.hw(Hf)
     bd = torch.from_numpy(p["bias"]).cuda()
-    y = _dest(B * Hf * Hf, C, TD[dtype])
+    y = _dest(B * Hf * Wf, C, TD[dtype])
     dt = _lib.BF16 if dtype == "bf16" else _lib.F32
     _lib.set_flag("force_generic", 1 if generic else 0)
     try:
         if cos:
             rn = torch.ones(B, 2, ws * ws, C, dtype=torch.float32, device="cuda")
             mul = torch.tensor([20.0, 100.0][:heads], dtype=torch.float32, device="cuda")
-            _lib.call("mv_swin_window_attn_cos_fwd", _p(qd), _p(rn), _p(mul), _p(bd), _p(y), None, 1.0, B, Hf, Hf, C, heads, ws, ws,
+            _lib.call("mv_swin_window_attn_cos_fwd", _p(qd), _p(rn), _p(mul), _p(bd), _p(y), None, 1.0, B, Hf, Wf, C, heads, ws, ws,
                       shift, shift, dt, _stream())
         elif keys is not None:
-            _lib.call("mv_swin_window_attn_dropout_fwd", _p(qd), _p(bd), _p(y), _p(keys), float(keep), B, Hf, Hf, C, heads, ws, ws,
+            _lib.call("mv_swin_window_attn_dropout_fwd", _p(qd), _p(bd), _p(y), _p(keys), float(keep), B, Hf, Wf, C, heads, ws, ws,
                       shift, shift, dt, _stream())
         else:
-            _lib.call("mv_swin_window_attn_fwd", _p(qd), _p(bd), _p(y), B, Hf, Hf, C, heads, ws, ws, shift, shift, dt, _stream())
+            _lib.call("mv_swin_window_attn_fwd", _p(qd), _p(bd), _p(y), B, Hf, Wf, C, heads, ws, ws, shift, shift, dt, _stream())
         kern = _lib.last_kernel()
     finally:
         _lib.set_flag("force_generic", 0)
     torch.cuda.synchronize()
-    return A.swin_groups(_back(y, (B, Hf, Hf, C)), heads, ws, shift), kern
+    return A.swin_groups(_back(y, (B, Hf, Wf, C)), heads, ws, shift), kern
 
 
 def _say(tag, *infos):
@@ -181,7 +182,8 @@ def test_mha_generic_paths(case):
 
 
 # ------------------------------------------------------------------------------------------------ Swin
-def _swin_suite(shape, kern, dtype="bf16", generic=False, cos=False, tie_codes=True, gauss=True, mfma=True):
+def _swin_suite(shape, kern, dtype="bf16", generic=False, cos=False, tie_codes=True, gauss=True, mfma=True, gauss_B=None):
+    """gauss_B: the batch of the Gaussian case where the shape's own gives the rounding-bias rule too few elements (as A.gauss_shape)."""
     B, Hf, C, heads, ws, shift = shape
     cases = [("select", True), ("tie", True), ("flat", True)]
     cases.append(("select", False))
@@ -189,11 +191,13 @@ def _swin_suite(shape, kern, dtype="bf16", generic=False, cos=False, tie_codes=T
         cases.append(("tie", False))
     if cos:
         cases = [("select", True), ("flat", True)]
-    if A.eff_shift(Hf, ws, shift):
+    if any(A.eff_shift(L, ws, shift) for L in A.hw(Hf)):
         cases.append(("mask", True))
     if gauss:
         cases.append(("gauss", True))
     for kind, by_bias in cases:
+        if kind == "gauss" and gauss_B:
+            shape = (gauss_B,) + tuple(shape[1:])
         p, extra = A.swin_problem(kind, shape, 5 if kind != "gauss" else 6, by_bias, dtype=dtype)
         if kind != "gauss":
             A.prove(p, extra)
@@ -218,6 +222,17 @@ def test_swin_generic_paths(case):
     dh = 32 two equal integer dot products need not round alike; there the tie comes from the bias (form (a)) only."""
     shape, dtype, generic, kern = case[:6], case[6], case[7], case[8]
     _swin_suite(shape, kern, dtype=dtype, generic=generic, tie_codes=(shape[2] // shape[3] == 16), mfma=False)
+
+
+@pytest.mark.parametrize("shape", A.SWIN_WRAP_SHAPES, ids=_ids(A.SWIN_WRAP_SHAPES))
+def test_swin_one_axis_wrap(shape):
+    """One window along the axis it covers (that shift is dropped), wrap at shift = ws - 1 along the other: the un-rolled row of
+    swin_geom.h is one conditional subtract, exact because y + shift < 2 Hf.  The matrix-core kernel and both fallback kernels.
+    B = 1 gives 1024 outputs; the Gaussian case of the matrix-core kernel runs the same map at B = 8 (8192 outputs), because the
+    rounding-bias rule needs 4096 eligible elements."""
+    _swin_suite(shape, "swin_attn_mfma", gauss_B=8)
+    _swin_suite(shape, "swin_attn_generic", generic=True, tie_codes=False, mfma=False)
+    _swin_suite(shape, "swin_attn_f32_lds", dtype="fp32", tie_codes=False, mfma=False)
 
 
 def test_swin_dropout():

@@ -1,5 +1,8 @@
 """Time mv_swin_block_attn_fwd (a Swin block's attention half in one launch, one workgroup per window) against the four launches it
-replaces (LayerNorm, qkv Linear, window attention, proj Linear + residual).  usage: time_swin_block_attn.py [B ...]  (stage 2)"""
+replaces (LayerNorm, qkv Linear, window attention, proj Linear + residual).  usage: time_swin_block_attn.py [B ...]  (stage 2)
+SBA_C = 384 | 192 | 96 picks the stage, FLAGS=swin_c96_shared the shared C = 96 kernel.  SBA_PROF=1 prints the per-wave phase stamps;
+the stamps are compiled only into the debug build (EQV_PROF=1 python -m eqxvision_amd.build, loaded with EQV_LIB=<that library>) --
+with the product library every stamp reads 0."""
 import sys, os
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np, torch
