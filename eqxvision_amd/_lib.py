@@ -185,6 +185,9 @@ PROTOTYPES = {
     "mv_conv2d_mp_fwd": [_vp, _vp, _vp, _vp] + [_i] * 13 + [_vp],
     "mv_conv2d_mp_dgrad": [_vp, _vp, _vp] + [_i] * 13 + [_vp],
     "mv_conv2d_mp_wgrad": [_vp, _vp, _vp] + [_i] * 13 + [_vp],
+    "mv_mha_mp_supported": [_i, _i],
+    "mv_mha_mp_fwd": [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _vp],
+    "mv_mha_mp_bwd": [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _vp],
     "mv_swin_window_attn_bwd_f32": [_vp] * 5 + [_i] * 9 + [_vp],
     "mv_scatter_rows_sum_f32": [_vp, _vp, _vp, _i, _i, _i, _vp],
     "mv_patch_merge_gather_bwd_f32": [_vp, _vp, _i, _i, _i, _i, _vp],

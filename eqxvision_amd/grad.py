@@ -61,6 +61,7 @@ class Tape:
         self.inside = 0         # > 0 while a g_* function runs (its own C-ABI calls are allowed)
         self.matmul_dtype = "fp32"   # filter_value_and_grad's `matmul_dtype`: "bf16" = g_linear's three products on the bf16 matrix cores
         self.conv_dtype = "fp32"     # filter_value_and_grad's `conv_dtype`: "bf16" = g_conv2d's three products (groups == 1) likewise
+        self.attn_dtype = "fp32"     # filter_value_and_grad's `attn_dtype`: "bf16" = g_qkv_attention's core, forward and backward, likewise
 
 
 class Node:
@@ -765,16 +766,32 @@ def g_patch_embed_tokens(x: Act, conv, cls, pos, n_extra: int, out_fp32: bool = 
 @_op
 def g_qkv_attention(x: Act, lin, heads: int, scale: float, need_probs: bool, drop=None):
     """qkv Linear + softmax(q k^T scale) v (vit.py:64-73) with the probabilities kept for the backward pass: dP = dO V^T, the softmax
-    gradient, dQ = dS K, dK = dS^T Q, dV = P^T dO in two launches (mv_mha_bwd_f32)."""
+    gradient, dQ = dS K, dK = dS^T Q, dV = P^T dO in two launches (mv_mha_bwd_f32).
+
+    Under filter_value_and_grad(..., attn_dtype="bf16"), for dh 32 / 64 and N <= 256 (mv_mha_mp_supported), the core runs on the bf16
+    matrix cores in both directions (mv_mha_mp_fwd / mv_mha_mp_bwd: operands rounded to bf16 on their way into LDS, fp32 accumulation,
+    fp32 results).  What is kept is qkv, out and one log-sum-exp per query row; the backward recomputes the probabilities, and a
+    [B, heads, N, N] tensor exists only when `need_probs` asks for the returned attention.  Any other shape takes the fp32 path.  The
+    qkv projection is a g_linear: `matmul_dtype` alone governs it."""
     if drop is not None:
         raise NotImplementedError("attention dropout has no backward yet")
     B, N, D = x.t.shape
     dh = D // heads
     qkv = g_linear.__wrapped__(x, lin)                                   # [B, N, 3 D], columns [q | k | v][head][dh]
     out = _new((B, N, D))
-    probs = _new((B, heads, N, N))
-    _call("mv_mha_fwd", _p(qkv.t), _p(out), _p(probs), B, N, heads, dh, float(scale), F32, _S())
     qt = qkv.t
+    if tape().attn_dtype == "bf16" and _lib.load().mv_mha_mp_supported(N, dh):
+        lse = _new((B, heads, N))
+        probs = _new((B, heads, N, N)) if need_probs else None
+        _call("mv_mha_mp_fwd", _p(qt), _p(out), _p(lse), _p(probs), B, N, heads, dh, float(scale), _S())
+
+        def backward(g):                                                  # g [B, N, D]
+            dqkv = _new((B, N, 3 * D))
+            _call("mv_mha_mp_bwd", _p(qt), _p(out), _p(g.contiguous()), _p(lse), _p(dqkv), B, N, heads, dh, float(scale), _S())
+            return (dqkv,)
+        return _mk(out, "seq", x.batched, [_node(qkv)], backward), probs
+    probs = _new((B, heads, N, N))
+    _call("mv_mha_fwd", _p(qt), _p(out), _p(probs), B, N, heads, dh, float(scale), F32, _S())
 
     def backward(g):                                                      # g [B, N, D]
         dqkv = _new((B, N, 3 * D))
@@ -1187,9 +1204,11 @@ def _frozen_ids(model, spec) -> set:
 
 MATMUL_DTYPES = ("fp32", "bf16")
 CONV_DTYPES = ("fp32", "bf16")
+ATTN_DTYPES = ("fp32", "bf16")
 
 
-def filter_value_and_grad(fn: Optional[Callable] = None, *, arg=None, matmul_dtype: str = "fp32", conv_dtype: str = "fp32") -> Callable:
+def filter_value_and_grad(fn: Optional[Callable] = None, *, arg=None, matmul_dtype: str = "fp32", conv_dtype: str = "fp32",
+                          attn_dtype: str = "fp32") -> Callable:
     """`eqx.filter_value_and_grad`: fn(model, *args) -> scalar loss; returns (loss, grads) with `grads` = the model tree with
     every array leaf replaced by its gradient (zeros where the loss does not depend on it) and every other leaf kept.
 
@@ -1208,13 +1227,25 @@ def filter_value_and_grad(fn: Optional[Callable] = None, *, arg=None, matmul_dty
     always did.  "bf16" is the same mixed precision for every Conv2d with groups == 1 (`g_conv2d`: forward, input gradient and weight
     gradient round their operands to bf16 and accumulate in fp32; a pointwise stride-1 convolution runs as a Linear on its rows).
     Grouped and depthwise convolutions, the bias and its gradient, BatchNorm, residual adds, activations, the patch embedding and
-    everything in memory stay fp32.  Any other value raises ValueError here, when the decorator is applied."""
+    everything in memory stay fp32.  Any other value raises ValueError here, when the decorator is applied.
+
+    `attn_dtype` (a keyword, independent of the other two): "fp32" (the default) launches what it always did.  "bf16" runs ViT's
+    attention core (`g_qkv_attention`: q k^T, P v and the four products of its backward) on the bf16 matrix cores for head widths 32
+    and 64 and at most 256 tokens: q, k, v, the gradient of the output and the probabilities are rounded to bf16 on their way into
+    the products, sums and the softmax are fp32, and the backward keeps a log-sum-exp per query row and recomputes the
+    probabilities, so no [B, heads, N, N] tensor is saved (one is written only for a caller that asked for the attention).  Other
+    shapes take the fp32 path silently.  Swin's window attention (49 tokens, relative-position bias, shift mask, a table gradient)
+    stays fp32 under either value, and so does the qkv projection unless `matmul_dtype` says otherwise.  Any other value raises
+    ValueError here, when the decorator is applied."""
     if matmul_dtype not in MATMUL_DTYPES:
         raise ValueError(f"filter_value_and_grad: matmul_dtype must be one of {MATMUL_DTYPES}, got {matmul_dtype!r}")
     if conv_dtype not in CONV_DTYPES:
         raise ValueError(f"filter_value_and_grad: conv_dtype must be one of {CONV_DTYPES}, got {conv_dtype!r}")
+    if attn_dtype not in ATTN_DTYPES:
+        raise ValueError(f"filter_value_and_grad: attn_dtype must be one of {ATTN_DTYPES}, got {attn_dtype!r}")
     if fn is None:
-        return functools.partial(filter_value_and_grad, arg=arg, matmul_dtype=matmul_dtype, conv_dtype=conv_dtype)
+        kw = {} if attn_dtype == "fp32" else {"attn_dtype": attn_dtype}      # the default carries itself: callers that do not name the
+        return functools.partial(filter_value_and_grad, arg=arg, matmul_dtype=matmul_dtype, conv_dtype=conv_dtype, **kw)   # keyword see the partial they always saw
 
     @functools.wraps(fn)
     def wrapped(model, *args, **kwargs):
@@ -1231,6 +1262,7 @@ def filter_value_and_grad(fn: Optional[Callable] = None, *, arg=None, matmul_dty
         t.frozen = frozen
         t.matmul_dtype = matmul_dtype
         t.conv_dtype = conv_dtype
+        t.attn_dtype = attn_dtype
         try:
             with precision("fp32"):
                 loss = fn(model, *args, **kwargs)

@@ -1018,6 +1018,23 @@ int mv_conv2d_mp_dgrad(const float* dy, const float* w_krsc, float* dx, int N, i
 int mv_conv2d_mp_wgrad(const float* x, const float* dy, float* dw_krsc, int N, int H, int W, int C, int K, int R, int S, int sh, int sw,
                        int ph, int pw, int dh, int dw, mv_stream_t stream);
 
+/* ---- mixed-precision attention core for the training step (filter_value_and_grad(..., attn_dtype="bf16"); vit.py:65-73, the op of
+ * mv_mha_fwd / mv_mha_bwd_f32).  qkv and dqkv are fp32 token-major [B, N, 3, H, dh]; out and dout fp32 [B, N, H*dh]; lse fp32
+ * [B, H, N]; probs fp32 [B, H, N, N] or NULL.  r(.) rounds an element to bf16, round-to-nearest-even, on its way into LDS or
+ * registers; products accumulate in fp32 on v_mfma_f32_32x32x16_bf16; nothing in memory changes type.
+ *   fwd:  s_ij = sum_d r(q_id) r(k_jd);  pe_ij = exp(scale s_ij - max_j scale s_ij);  Z_i = sum_j pe_ij (pe un-rounded)
+ *         out_i = (sum_j r(pe_ij) r(v_j)) / Z_i;  lse_i = max_j scale s_ij + log Z_i;  probs_ij = pe_ij / Z_i, written only when
+ *         probs != NULL (out and lse do not depend on it)
+ *   bwd:  from qkv, out, dout and lse, the probabilities recomputed: p_ij = exp(scale s_ij - lse_i);  delta_i = sum_d dout_id out_id
+ *         (fp32, un-rounded);  dp_ij = sum_d r(dout_id) r(v_jd);  ds_ij = scale p_ij (dp_ij - delta_i);  dV_j = sum_i r(p_ij) r(dout_i);
+ *         dQ_i = sum_j r(ds_ij) r(k_j);  dK_j = sum_i r(ds_ij) r(q_i).  No atomics, one summation order: two runs give the same bits.
+ * mv_mha_mp_supported: dh 32 / 64 and 1 <= N <= 256.  Anything else is MV_E_UNSUPPORTED, a NULL or not 16-byte aligned pointer or
+ * scale <= 0 is MV_E_INVALID; either is returned before any HIP call and leaves the destinations untouched. */
+int mv_mha_mp_supported(int N, int dh);
+int mv_mha_mp_fwd(const float* qkv, float* out, float* lse, float* probs, int B, int N, int H, int dh, float scale, mv_stream_t stream);
+int mv_mha_mp_bwd(const float* qkv, const float* out, const float* dout, const float* lse, float* dqkv, int B, int N, int H, int dh,
+                  float scale, mv_stream_t stream);
+
 /* hipGraph capture of a whole forward (replaces the reference's eqx.filter_jit executable) */
 int mv_graph_begin_capture(mv_stream_t stream);
 int mv_graph_end_capture(mv_stream_t stream, void** graph_exec);

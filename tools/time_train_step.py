@@ -3,7 +3,9 @@ apply_updates, model in training mode) on the HIP path, fp32.  The backward half
 asks "loss is not NaN"), so this is a record of where it stands, not a bench line.
 --matmul-dtype bf16: the Linear layers' three products on the bf16 matrix cores (filter_value_and_grad's `matmul_dtype`).
 --conv-dtype bf16: the Conv2d layers' (groups == 1) three products likewise (filter_value_and_grad's `conv_dtype`).
-usage: time_train_step.py [MODEL=resnet18] [BATCH=8] [STEPS=5] [--matmul-dtype fp32|bf16] [--conv-dtype fp32|bf16]"""
+--attn-dtype bf16: ViT's attention core, forward and backward, likewise, with a log-sum-exp kept instead of the probabilities
+(filter_value_and_grad's `attn_dtype`).  The line ends with the peak device memory of the run (torch.cuda.max_memory_allocated).
+usage: time_train_step.py [MODEL=resnet18] [BATCH=8] [STEPS=5] [--matmul-dtype fp32|bf16] [--conv-dtype fp32|bf16] [--attn-dtype fp32|bf16]"""
 import sys, os, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
@@ -22,6 +24,11 @@ if "--conv-dtype" in argv:
     i = argv.index("--conv-dtype")
     conv_dtype = argv[i + 1]
     del argv[i:i + 2]
+attn_dtype = "fp32"
+if "--attn-dtype" in argv:
+    i = argv.index("--attn-dtype")
+    attn_dtype = argv[i + 1]
+    del argv[i:i + 2]
 model = argv[0] if len(argv) > 0 else "resnet18"
 B = int(argv[1]) if len(argv) > 1 else 8
 steps = int(argv[2]) if len(argv) > 2 else 5
@@ -31,7 +38,7 @@ y = np.arange(B) % 10
 keys = eqv.random.split(eqv.random.PRNGKey(1), B)
 
 
-@eqv.filter_value_and_grad(matmul_dtype=matmul_dtype, conv_dtype=conv_dtype)
+@eqv.filter_value_and_grad(matmul_dtype=matmul_dtype, conv_dtype=conv_dtype, attn_dtype=attn_dtype)
 def compute_loss(m, xx, yy):
     out = eqv.vmap(m, axis_name="batch")(xx, key=keys)
     return eqv.optim.softmax_cross_entropy(out, eqv.optim.one_hot(yy, 10)).mean()
@@ -47,4 +54,5 @@ for i in range(steps + 1):
     net = eqv.apply_updates(net, updates)
     torch.cuda.synchronize(); ts.append(time.perf_counter() - t0); losses.append(float(loss))
 ms = 1e3 * float(np.median(ts[1:]))
-print(f"{model} B={B} matmul_dtype={matmul_dtype} conv_dtype={conv_dtype}: training step {ms:.1f} ms ({B / ms * 1e3:.1f} img/s), first step {1e3 * ts[0]:.0f} ms; loss {losses[0]:.4f} -> {losses[-1]:.4f}")
+print(f"{model} B={B} matmul_dtype={matmul_dtype} conv_dtype={conv_dtype} attn_dtype={attn_dtype}: training step {ms:.1f} ms ({B / ms * 1e3:.1f} img/s), "
+      f"first step {1e3 * ts[0]:.0f} ms; loss {losses[0]:.4f} -> {losses[-1]:.4f}; peak device memory {torch.cuda.max_memory_allocated() / 2 ** 20:.0f} MiB")
