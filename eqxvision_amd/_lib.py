@@ -188,6 +188,10 @@ PROTOTYPES = {
     "mv_mha_mp_supported": [_i, _i],
     "mv_mha_mp_fwd": [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _vp],
     "mv_mha_mp_bwd": [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _vp],
+    "mv_swin_attn_mp_supported": [_i, _i],
+    "mv_swin_attn_mp_bwd_parts": [_i] * 6,
+    "mv_swin_attn_mp_fwd": [_vp] * 4 + [_i] * 9 + [_f, _vp],
+    "mv_swin_attn_mp_bwd": [_vp] * 7 + [_i] * 9 + [_f, _vp],
     "mv_swin_window_attn_bwd_f32": [_vp] * 5 + [_i] * 9 + [_vp],
     "mv_scatter_rows_sum_f32": [_vp, _vp, _vp, _i, _i, _i, _vp],
     "mv_patch_merge_gather_bwd_f32": [_vp, _vp, _i, _i, _i, _i, _vp],

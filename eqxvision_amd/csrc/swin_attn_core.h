@@ -27,6 +27,15 @@ __device__ __forceinline__ bf16x8 p_frag(const f32x16& s, int half) {
     return __builtin_bit_cast(bf16x8, f);
 }
 
+// One logit, the rule every window-attention kernel shares: s * scale + relative-position bias, -100 like the reference where the
+// key's mask region is not the query's, and -inf on a padded key of the tile -- padding is EXCLUDED, not masked.
+__device__ __forceinline__ float win_logit(float s, float scale, float bias, bool masked, bool padded) {
+    float v = fmaf(s, scale, bias);
+    if (masked) v += -100.0f;
+    if (padded) v = -INFINITY;
+    return v;
+}
+
 // Scores -> unnormalised probabilities, in place; returns 1 / their sum.  s * scale + relative-position bias (bias_row: the query's
 // 64 fp32 entries) + shift mask (-100 like the reference where key_regions[key] != qreg), exp(. - row max).
 // GUARD (swin_attn.hip: any window of <= 64 tokens, bias padded with zeros): region ids are read only if `shifted`, keys >= n get
@@ -49,9 +58,7 @@ __device__ __forceinline__ float win_softmax(f32x16 (&s)[2], float scale, const 
             const int rr[4] = {kr.x, kr.y, kr.z, kr.w};
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
-                float v = fmaf(s[kt][4 * gq + e], scale, bb[e]);
-                if (mask && rr[e] != qreg) v += -100.0f;
-                if (GUARD && key0 + e >= n) v = -INFINITY;
+                const float v = win_logit(s[kt][4 * gq + e], scale, bb[e], mask && rr[e] != qreg, GUARD && key0 + e >= n);
                 s[kt][4 * gq + e] = v;
                 mx = fmaxf(mx, v);
             }

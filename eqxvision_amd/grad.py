@@ -822,12 +822,21 @@ def g_swin_rel_bias(attn) -> torch.Tensor:
 
 @_op
 def g_swin_window_attention(qkv: Act, bias: torch.Tensor, heads: int, window, shift, drop=None) -> Act:
+    """Shifted-window attention on the qkv map (swin.py:123-250); the bias-table gradient is a column sum, a transpose and a scatter.
+
+    Under filter_value_and_grad(..., attn_dtype="bf16"), for dh 32 / 64 and windows of at most 64 tokens (mv_swin_attn_mp_supported),
+    both directions run on the bf16 matrix cores (mv_swin_attn_mp_fwd / mv_swin_attn_mp_bwd).  What is kept is qkv, out and one
+    log-sum-exp per window row; the backward recomputes the probabilities and leaves the logit gradients summed into
+    mv_swin_attn_mp_bwd_parts(...) parts [P, heads, n, n] instead of one [heads, n, n] per window -- or nowhere, when the bias table is
+    frozen or absent.  Any other shape, and the default setting, launch the fp32 pair."""
     if drop is not None:
         raise NotImplementedError("Swin attention dropout has no backward yet")
     B, Hf, Wf, C3 = qkv.t.shape
     C = C3 // 3
     wh, ww, sh, sw = int(window[0]), int(window[1]), int(shift[0]), int(shift[1])
     out = _new((B, Hf, Wf, C))
+    if tape().attn_dtype == "bf16" and _lib.load().mv_swin_attn_mp_supported(wh * ww, C // heads):
+        return _swin_window_attention_mp(qkv, bias, out, heads, (wh, ww, sh, sw))
     _call("mv_swin_window_attn_fwd", _p(qkv.t), _p(bias), _p(out), B, Hf, Wf, C, heads, wh, ww, sh, sw, F32, _S())
     qt = qkv.t
     info = tape().leaf_of.get(bias.data_ptr())
@@ -840,6 +849,36 @@ def g_swin_window_attention(qkv: Act, bias: torch.Tensor, heads: int, window, sh
         if info is not None and _trainable(info[0]):
             table, idx, T = info
             db = _colsum(gw, None, heads * n * n)                         # [heads][n * n]: summed over images and windows
+            dbt = _transpose(db, heads, n * n)                            # [n * n][heads]
+            dt = _new((T, heads))
+            _call("mv_scatter_rows_sum_f32", _p(dbt), _p(idx), _p(dt), n * n, heads, T, _S())
+            _acc_param(table, dt)
+        return (dqkv,)
+    return _mk(out, "map", qkv.batched, [_node(qkv)], backward, leaves=(info[0],) if info is not None else ())
+
+
+def _swin_window_attention_mp(qkv: Act, bias: torch.Tensor, out: torch.Tensor, heads: int, geom) -> Act:
+    """The attn_dtype="bf16" branch of g_swin_window_attention."""
+    wh, ww, sh, sw = geom
+    B, Hf, Wf, C3 = qkv.t.shape
+    C = C3 // 3
+    n, nW, scale = wh * ww, (Hf // wh) * (Wf // ww), float((C // heads) ** -0.5)
+    lse = _new((B * nW, heads, n))
+    qt = qkv.t
+    _call("mv_swin_attn_mp_fwd", _p(qt), _p(bias), _p(out), _p(lse), B, Hf, Wf, C, heads, wh, ww, sh, sw, scale, _S())
+    info = tape().leaf_of.get(bias.data_ptr())
+
+    def backward(g):
+        dqkv = _new((B, Hf, Wf, C3))
+        want = info is not None and _trainable(info[0])
+        parts = None
+        if want:
+            parts = _new((_lib.load().mv_swin_attn_mp_bwd_parts(B, Hf, Wf, heads, wh, ww), heads * n * n))
+        _call("mv_swin_attn_mp_bwd", _p(qt), _p(bias), _p(out), _p(g.contiguous()), _p(lse), _p(dqkv), _p(parts), B, Hf, Wf, C, heads, wh, ww,
+              sh, sw, scale, _S())
+        if want:
+            table, idx, T = info
+            db = _colsum(parts, None, heads * n * n)                      # [heads][n * n]: the parts summed
             dbt = _transpose(db, heads, n * n)                            # [n * n][heads]
             dt = _new((T, heads))
             _call("mv_scatter_rows_sum_f32", _p(dbt), _p(idx), _p(dt), n * n, heads, T, _S())
@@ -1234,9 +1273,12 @@ def filter_value_and_grad(fn: Optional[Callable] = None, *, arg=None, matmul_dty
     and 64 and at most 256 tokens: q, k, v, the gradient of the output and the probabilities are rounded to bf16 on their way into
     the products, sums and the softmax are fp32, and the backward keeps a log-sum-exp per query row and recomputes the
     probabilities, so no [B, heads, N, N] tensor is saved (one is written only for a caller that asked for the attention).  Other
-    shapes take the fp32 path silently.  Swin's window attention (49 tokens, relative-position bias, shift mask, a table gradient)
-    stays fp32 under either value, and so does the qkv projection unless `matmul_dtype` says otherwise.  Any other value raises
-    ValueError here, when the decorator is applied."""
+    shapes take the fp32 path silently.  It also runs Swin's shifted-window attention (`g_swin_window_attention`: relative-position
+    bias, shift mask, a table gradient) on the matrix cores in both directions, for head widths 32 and 64 and windows of at most 64
+    tokens, with the same roundings; q is rounded as stored and the scale applied to the fp32 product, the logit gradient that
+    feeds the bias table is summed un-rounded in fp32 in a fixed order, and no per-window [heads, n, n] tensor is written (none
+    at all when the table is frozen).  Swin V2 has no backward; the qkv projection stays fp32 unless `matmul_dtype` says otherwise.
+    Any other value raises ValueError here, when the decorator is applied."""
     if matmul_dtype not in MATMUL_DTYPES:
         raise ValueError(f"filter_value_and_grad: matmul_dtype must be one of {MATMUL_DTYPES}, got {matmul_dtype!r}")
     if conv_dtype not in CONV_DTYPES:

@@ -1035,6 +1035,31 @@ int mv_mha_mp_fwd(const float* qkv, float* out, float* lse, float* probs, int B,
 int mv_mha_mp_bwd(const float* qkv, const float* out, const float* dout, const float* lse, float* dqkv, int B, int N, int H, int dh,
                   float scale, mv_stream_t stream);
 
+/* ---- mixed-precision Swin shifted-window attention for the training step (the same keyword, attn_dtype="bf16"; swin.py:123-250, the op
+ * of mv_swin_window_attn_fwd / mv_swin_window_attn_bwd_f32).  qkv and dqkv are fp32 NHWC [B, Hf, Wf, 3C], columns [q|k|v][head][dh];
+ * out and dout fp32 [B, Hf, Wf, C]; bias fp32 [heads, n, n] (n = ws_h * ws_w); lse fp32 [B * nW, heads, n] in window order;
+ * dbias_parts fp32 [P, heads, n, n] with P = mv_swin_attn_mp_bwd_parts(...), or NULL.  r(.) as above; roll, partition and shift mask
+ * are index arithmetic, and the shift of an axis whose window covers the map is dropped.
+ *   fwd:  l_ij = scale sum_d r(q_id) r(k_jd) + bias[h][i][j] + (shifted and region_i != region_j ? -100 : 0)   (q is NOT pre-scaled)
+ *         pe_ij = exp(l_ij - max_j l_ij);  Z_i = sum_j pe_ij (un-rounded);  out_i = (sum_j r(pe_ij) r(v_j)) / Z_i;  lse_i = max_j l_ij + log Z_i
+ *   bwd:  p_ij = exp(l_ij - lse_i) recomputed from qkv, bias, mask and the given lse;  delta_i = sum_d dout_id out_id (fp32, un-rounded)
+ *         dp_ij = sum_d r(dout_id) r(v_jd);  g_ij = p_ij (dp_ij - delta_i);  dV_j = sum_i r(p_ij) r(dout_i)
+ *         dQ_i = scale sum_j r(g_ij) r(k_j);  dK_j = scale sum_i r(g_ij) r(q_i)
+ *         dbias_parts[p][h][i][j] = the sum of the un-rounded g_ij over the (image, window) pairs p, p + P, p + 2 P, .. in that order:
+ *         every element of every part is written (zeros where a part has no pair); the bias gradient is the sum of the parts
+ *         (mv_colsum_f32 over P rows).  With dbias_parts == NULL nothing is accumulated or written.  No atomics: two runs, same bits.
+ * P depends on the arguments of mv_swin_attn_mp_bwd_parts alone and is at most 2048 / heads (at least 1), whatever B is.
+ * mv_swin_attn_mp_supported: dh 32 / 64 and 1 <= n <= 64.  Anything else, or B * nW * heads >= 2^31, is MV_E_UNSUPPORTED; a NULL or
+ * not 16-byte aligned pointer, a window that does not divide the map, a shift outside the window or scale <= 0 is MV_E_INVALID;
+ * either is returned before any HIP call and leaves the destinations untouched. */
+int mv_swin_attn_mp_supported(int n_tokens, int dh);
+int mv_swin_attn_mp_bwd_parts(int B, int Hf, int Wf, int heads, int ws_h, int ws_w);
+int mv_swin_attn_mp_fwd(const float* qkv, const float* bias, float* out, float* lse, int B, int Hf, int Wf, int C, int heads, int ws_h,
+                        int ws_w, int shift_h, int shift_w, float scale, mv_stream_t stream);
+int mv_swin_attn_mp_bwd(const float* qkv, const float* bias, const float* out, const float* dout, const float* lse, float* dqkv,
+                        float* dbias_parts, int B, int Hf, int Wf, int C, int heads, int ws_h, int ws_w, int shift_h, int shift_w,
+                        float scale, mv_stream_t stream);
+
 /* hipGraph capture of a whole forward (replaces the reference's eqx.filter_jit executable) */
 int mv_graph_begin_capture(mv_stream_t stream);
 int mv_graph_end_capture(mv_stream_t stream, void** graph_exec);

@@ -3,8 +3,8 @@ apply_updates, model in training mode) on the HIP path, fp32.  The backward half
 asks "loss is not NaN"), so this is a record of where it stands, not a bench line.
 --matmul-dtype bf16: the Linear layers' three products on the bf16 matrix cores (filter_value_and_grad's `matmul_dtype`).
 --conv-dtype bf16: the Conv2d layers' (groups == 1) three products likewise (filter_value_and_grad's `conv_dtype`).
---attn-dtype bf16: ViT's attention core, forward and backward, likewise, with a log-sum-exp kept instead of the probabilities
-(filter_value_and_grad's `attn_dtype`).  The line ends with the peak device memory of the run (torch.cuda.max_memory_allocated).
+--attn-dtype bf16: ViT's attention core and Swin's window attention, forward and backward, likewise, with a log-sum-exp kept instead
+of the probabilities (filter_value_and_grad's `attn_dtype`).  The line ends with the peak device memory of the run (torch.cuda.max_memory_allocated).
 usage: time_train_step.py [MODEL=resnet18] [BATCH=8] [STEPS=5] [--matmul-dtype fp32|bf16] [--conv-dtype fp32|bf16] [--attn-dtype fp32|bf16]"""
 import sys, os, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
